@@ -2,10 +2,12 @@
 """bench.py -- pairs/s of the pairwise HMM decode path on MI355X, against its HBM roofline.
 
 N = 1 (default; BASELINE.json configs[1], "C2"): synthetic 1000 haplotypes x 50000 sites, 69 states, all 499500
-haplotype pairs, FastSMC-mode output (IBD segments + posterior-mean / MAP ages, no hashing), one GPU.  Behind the timed
-region the same line carries one step each of the other single-GPU configurations (`config.other_workloads`: the
-FASTSMC_EXAMPLE shape C1 as IBD decode and as sum over pairs, and the 256-state configuration C4) and the C2 step of a
-context that runs on the library's default workspace policy (`config.library_default_workspace`).
+haplotype pairs, FastSMC-mode output (IBD segments + posterior-mean / MAP ages, no hashing), one GPU.  With `--full`,
+behind the timed region the same line carries one step each of the other single-GPU configurations
+(`config.other_workloads`: the FASTSMC_EXAMPLE shape C1 as IBD decode and as sum over pairs, and the 256-state
+configuration C4), the C2 step of a context that runs on the library's default workspace policy
+(`config.library_default_workspace`) and the CPU port on the first pairs of the work list (`cpu_baseline`); a plain run
+sets up, warms up, times `--steps` steps and prints the line.
 
 N > 1 (one process per GPU under torch.distributed.run; BASELINE.json configs[2], "C3"): STRONG scaling of ONE
 problem -- synthetic 10000 haplotypes x 100000 sites, 69 states, a fixed seeded sub-list of 5 * 2^19 = 2 621 440 of the 49 995 000
@@ -20,7 +22,9 @@ and every rank's host threads are capped at cores / ranks.
 A "step" = one decode of the whole pair list with every input (model tables, packed haplotypes, work list) already
 resident in HBM; the step ends when the ordered IBD records are back on the host of rank 0.
 
-Prints ONE JSON line (see the contract in the task description) with `roofline` and, at N = 1, `cpu_baseline`.
+Prints ONE JSON line with `roofline` and `cpu_baseline` (null unless `--full` at N = 1).  `--dump-outputs DIR` writes
+what the last timed step returned to its caller as DIR/<name>.npy (write_outputs), so that two builds can be compared
+output for output: the inputs of a given command line are the same from run to run.
 """
 from __future__ import annotations
 
@@ -256,6 +260,37 @@ def algorithmic_bytes(n_pairs: int, S: int, K: int) -> float:
     return float(n_pairs) * S * (8 * K + 0.25)
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much (npy headers included)
+DUMP_SEED = 20261
+
+
+def write_outputs(out_dir: str, mode: str, merged, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, one float32 / float64 .npy per array.
+    ibd: the ordered IBD records, one file per field (`ibd_<field>.npy`; integer fields as float64, which holds them
+    exactly); sums: the [sites][states] plane (`sum_over_pairs.npy`).  Beyond `budget` bytes a fixed, seeded sample of
+    records (plane rows) is written, in their order, with the sampled indices as `<prefix>_sample_index.npy`.
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    if mode == "sums":
+        arrays, prefix = {"sum_over_pairs": np.asarray(merged, np.float32)}, "sum_over_pairs"
+    else:
+        rec = np.asarray(merged)
+        arrays = {f"ibd_{f}": rec[f].astype(np.float64 if rec.dtype[f].kind in "iu" else np.float32)
+                  for f in rec.dtype.names}
+        prefix = "ibd"
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values()) or 1
+    header = 128 * (len(arrays) + 1)
+    if n * row_bytes + header > budget:
+        m = max(0, (budget - header) // (row_bytes + 8))  # (+ 8: the index file's float64)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays[f"{prefix}_sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def _timed(fn, reps: int, ctx):
     """One untimed pass, then `reps` timed ones: (mean kernel ms by the library's HIP events, mean wall s of the call)."""
     ms, wall = [], []
@@ -397,18 +432,26 @@ def main() -> None:
                     help="chunks of a chunked window whose beta rows stay in the workspace (no rebuild): -1 = as many "
                          "as memory allows, 0 = none")
     ap.add_argument("--cpu-pairs", type=int, default=-1,
-                    help="pairs in the cpu_baseline sample (0 = skip, -1 = automatic: 128 per host core)")
+                    help="--full: pairs in the cpu_baseline sample (0 = skip, -1 = automatic: 128 per host core)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1: bring the process group up all the same (one rank) and send the records through the "
                          "path's collectives -- the rehearsal of the RCCL leg on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, the measurements the headline does not need: config.other_workloads "
+                         "and config.library_default_workspace (default N = 1 line only) and cpu_baseline (N = 1)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip config.other_workloads / config.library_default_workspace (default N = 1 line only)")
+                    help="--full: skip config.other_workloads / config.library_default_workspace")
     ap.add_argument("--startup-only", action="store_true",
                     help="build (or map) the problem and the work list, print the start-up time per rank and stop "
                          "before the first GPU call (measures the host start-up where there is no GPU)")
     ap.add_argument("--dump-records", default="", help="rank 0 writes the last step's gathered records to this .npy")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB (a seeded sample of the records beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     t_start = time.perf_counter()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -574,6 +617,8 @@ def main() -> None:
     if rank == 0:
         if args.dump_records and merged is not None:
             np.save(args.dump_records, merged)
+        if args.dump_outputs and merged is not None:
+            write_outputs(args.dump_outputs, args.mode, merged)
         value = n_total * args.steps / elapsed
         k_s = my_kernel_ms / 1e3
         algo_bytes = algorithmic_bytes(n_mine, pm.S, pm.K)  # the launch this rank times: its own shard
@@ -616,9 +661,10 @@ def main() -> None:
             if ref and ref.get("workload_key") == workload_key:
                 out["config"]["n1_pairs_per_s_same_worklist"] = ref["value"]
                 out["config"]["speedup_vs_n1"] = value / ref["value"]
-        # the extra measurements ride on the DEFAULT line only: any option that shapes the workload or the plan makes
-        # the run a measurement of its own
-        default_line = (world == 1 and args.workload == "auto" and args.mode == "ibd" and not args.no_other_workloads
+        # the extra measurements ride on the DEFAULT line with --full only: any option that shapes the workload or the
+        # plan makes the run a measurement of its own
+        default_line = (args.full and world == 1 and args.workload == "auto" and args.mode == "ibd"
+                        and not args.no_other_workloads
                         and not args.diag_same_row and not args.haps and not args.sites and args.states == 69
                         and args.flags < 0 and not args.chunk_sites and not args.beta_stride
                         and args.resident_chunks < 0 and not args.force_collective)
@@ -643,7 +689,7 @@ def main() -> None:
             out["config"]["library_default_workspace"] = {
                 "kernel_ms": 1e3 * k2, "frac": algo_bytes / k2 / HBM_PEAK,
                 "resident_chunks": ctx.last_resident_chunks(), "chunk_sites": ctx.info()["chunk_sites"], "steps": 2}
-        if args.cpu_pairs != 0 and world == 1:
+        if args.full and args.cpu_pairs != 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(pm, bits, args.cpu_pairs, pairs)
         else:
             out["cpu_baseline"] = None

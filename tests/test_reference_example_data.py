@@ -130,11 +130,11 @@ def test_hashing_golden_names_pairs_of_the_whole_cohort(example_root):
     assert all(r[5] in pos and r[6] in pos and r[5] <= r[6] for r in recs)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/FILES/EXAMPLE"), reason="reference checkout not present")
 def test_asmc_format_readers_on_the_reference_array_example():
     """ASMC-format inputs (plink 4-column .map.gz, Data.cpp:162-210; haps without the FastSMC job logic) on
-    FILES/EXAMPLE/exampleFile.n300.array.* -- the data of TESTS/test_HMM.cpp / test_ASMC.cpp.  Build container only."""
-    root = "/root/reference/FILES/EXAMPLE/exampleFile.n300.array"
+    FILES/EXAMPLE/exampleFile.n300.array.* -- the data of TESTS/test_HMM.cpp / test_ASMC.cpp, copied to
+    tests/golden/exampleFile.n300.array.{hap.gz,map.gz,samples}."""
+    root = os.path.join(GOLD, "exampleFile.n300.array")
     p = api.DecodingParams()
     p.inFileRoot = root
     p.decodingModeString = "array"

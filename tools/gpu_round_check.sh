@@ -11,5 +11,5 @@ timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>
 RC=$?
 echo "pytest rc=$RC"; tail -5 $OUT/pytest_gpu.log
 if [ $RC -ne 0 ]; then exit $RC; fi
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench rc=$?"; tail -c 6000 $OUT/bench_default.json

@@ -34,5 +34,5 @@ python3 bench.py --workload c1 --steps 10 --warmup 2 --cpu-pairs 0 > $OUT/c1_ben
 python3 tools/measure_configs.py c5_job > $OUT/c5_job.json 2> $OUT/c5_job.err
 python3 tools/measure_configs.py ingest_c3 > $OUT/ingest_c3.json 2> $OUT/ingest_c3.err
 echo "host done"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "all done"

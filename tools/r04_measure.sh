@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box: the measurements of round 4 that are kept under profiles/ (stamped by tools/stamp_profiles.py).
-# Usage: tools/r04_measure.sh <part>   part = headline | pmc | round | all
+# Usage: tools/r04_measure.sh <part>   part = headline | pmc | round | all   (headline and all: RESULTS=<dir> in the environment)
 set -u
 cd $GRAFT_REPO_ROOT
 PART=${1:-all}
@@ -8,7 +8,8 @@ if [ $PART = headline ] || [ $PART = all ]; then
   # 1. the headline command under rocprofv3 --kernel-trace --stats and the two HBM-traffic counters (separate passes)
   bash tools/profile_bench.sh r04 --steps 3 --warmup 1 > gpurun_out/r04_headline.log 2>&1
   # ... and the default line itself (other workloads + the library-default workspace figure), untraced
-  python3 bench.py > gpurun_out/r04_bench_default.json 2> gpurun_out/r04_bench_default.err
+  : "${RESULTS:?the headline part writes r04_bench_default.json to the directory RESULTS names}"
+  python3 bench.py --full > "$RESULTS/r04_bench_default.json" 2> "$RESULTS/r04_bench_default.err"
   echo "headline done"
 fi
 if [ $PART = pmc ] || [ $PART = all ]; then
