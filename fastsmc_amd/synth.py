@@ -122,6 +122,8 @@ def make_model_tables(K: int = 69, N: float = 15000.0, mu: float = 1.0e-5, csfs_
             RR[ri, : K - 1] = 1.0
             continue
         a = 1.0 / N - 2.0 * r
+        if a == 0.0:  # r = 1/(2N): the closed forms of g and b divide by a
+            raise ValueError(f"genetic distance key {r!r} equals 1/(2N) for N = {N!r}: the closed forms divide by 0")
         g = 2.0 * r * np.expm1(a * s) / a
         e2a, e2b = np.exp(-2.0 * r * lo), np.exp(-2.0 * r * hi)
         b = (2.0 * r / (N * a)) * ((e2a - e2b) / (2.0 * r) - N * h)

@@ -254,3 +254,26 @@ def test_fastsmc_run_wide_model_matches_oracle_text(small_problem, tmp_path, K):
     want, n_pairs = _oracle_text(sp, list(range(32)), 1, 1)
     assert n_pairs == 2 * 32 * 32 - 32 and want.count("\n") > 50
     assert got == want
+
+
+def test_fastsmc_run_on_a_map_with_runs_of_equal_cm(tmp_path):
+    """A genetic map with consecutive sites at the same cM -- one pair, then a run of 150 -- read from the .map file:
+    those steps take the smallest key (roundMorgans' 1e-10 floor), and FastSMC.run() writes the text the oracle and
+    the reference's record format give."""
+    from conftest import build_small_problem
+
+    sp = build_small_problem()
+    cm = sp["haps"].cm.copy()
+    cm[20] = cm[19]
+    cm[300:450] = cm[300]
+    sp["haps"].cm = cm
+    sp["gen"] = (cm / 100.0).astype(np.float32)
+    keys = O.step_rows(sp["tables"].keys, sp["gen"])[1]
+    assert np.count_nonzero(keys[1:] == np.float32(1e-10)) >= 150
+    root = make_files(tmp_path, sp)
+    out = str(tmp_path / "flat")
+    api.FastSMC(_params(root, out)).run()
+    got = gzip.open(out + ".1.1.FastSMC.ibd.gz", "rt").read()
+    want, _ = _oracle_text(sp, list(range(32)), 1, 1)
+    assert want.count("\n") > 100
+    assert got == want

@@ -332,3 +332,60 @@ def test_ibd_text_of_many_records_is_the_text_of_few(small_problem, tmp_path):
     # every reader of gzip files sees one stream: zlib's own too
     import subprocess
     assert subprocess.run(["zcat", big], capture_output=True, check=True).stdout.decode() == text
+
+
+def _map_problem(cm, seq=False):
+    """64 haplotypes on the sites of ``cm`` (centimorgans; physical positions 300 bp apart unless sequence mode)."""
+    S = cm.size
+    haps = synth.make_haps(64, S, seed=13, cm_per_mb=25.0, bp_per_site=2500 if seq else 300, switch_per_cm=0.6)
+    haps.cm = np.asarray(cm, np.float64)
+    return haps
+
+
+def _host_and_oracle(haps, K=16, seq=False):
+    tables = synth.make_model_tables(K)
+    data = api.Data.from_arrays(haps.alleles, haps.bp, haps.cm, True, True)
+    dq = api.decoding_quantities_from_tables(tables)
+    p = _params(decodingSequence=True, decodingModeString="sequence") if seq else _params()
+    _, derived, _ = synth.fold_and_pack(haps.alleles)
+    gen = np.array(data.geneticPositions, np.float32)
+    host = lambda: api.HMM(data, dq, p).preparedModel()  # noqa: E731
+    oracle = lambda: O.prepare_model(tables, gen, haps.bp, derived, 64, time=50, decoding_sequence=seq)  # noqa: E731
+    return host, oracle
+
+
+def test_runs_of_equal_genetic_positions():
+    """Consecutive sites at the same cM -- one pair, a run of 150 -- take the smallest key (roundMorgans' 1e-10 floor):
+    the host's prepared model is the oracle's."""
+    cm = np.cumsum(np.full(400, 0.0075))
+    cm[20] = cm[19]
+    cm[100:250] = cm[100]
+    host, oracle = _host_and_oracle(_map_problem(cm))
+    want = oracle()
+    assert np.count_nonzero(O.step_rows(synth.genetic_distance_keys(), want.gen)[1] == np.float32(1e-10)) >= 150
+    _assert_same_model(host(), want)
+
+
+def test_gap_beyond_the_key_grid_raises():
+    """A step beyond the 0.3 M key grid: the reference throws std::out_of_range; the host raises, the oracle too."""
+    cm = np.cumsum(np.full(200, 0.0075))
+    cm[120:] += 40.0  # 0.4 M
+    host, oracle = _host_and_oracle(_map_problem(cm))
+    with pytest.raises(KeyError):
+        oracle()
+    with pytest.raises(Exception, match="genetic distance"):
+        host()
+
+
+def test_sequence_mode_physical_gap_beyond_the_homozygous_table_raises():
+    """Sequence mode: a physical gap beyond the homozygous emission table (2 Mb) has no entry; the host raises like the
+    oracle, and a gap inside the table still prepares the oracle's model."""
+    haps = _map_problem(np.cumsum(np.full(120, 0.0002)), seq=True)
+    host, oracle = _host_and_oracle(haps, seq=True)
+    _assert_same_sequence_rows(host(), oracle())
+    haps.bp[60:] += 3_000_000
+    host, oracle = _host_and_oracle(haps, seq=True)
+    with pytest.raises(KeyError):
+        oracle()
+    with pytest.raises(Exception, match="HomozygousEmissions"):
+        host()
