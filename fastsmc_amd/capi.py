@@ -34,6 +34,7 @@ SYMBOLS = [
     "fsmc_decode_ibd_launch", "fsmc_decode_ibd_fetch", "fsmc_sync", "fsmc_last_kernel_ms", "fsmc_phase_cycles",
     "fsmc_decode_ibd",
     "fsmc_decode_posteriors", "fsmc_decode_per_pair", "fsmc_decode_sums", "fsmc_decode_sums_batches",
+    "fsmc_decode_pair_posteriors", "fsmc_ctx_set_pair_posterior_slice", "fsmc_ctx_last_pair_posterior_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -119,6 +120,9 @@ def load():
         L.fsmc_decode_ibd.argtypes = [vp, vp, vp, sz, vp, sz, u32, vp, sz, C.POINTER(sz)]
         L.fsmc_decode_posteriors.argtypes = [vp, vp, vp, sz]
         L.fsmc_decode_per_pair.argtypes = [vp, vp, vp, vp, vp]
+        L.fsmc_decode_pair_posteriors.argtypes = [vp, vp, vp, vp, vp]
+        L.fsmc_ctx_set_pair_posterior_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_posterior_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -333,6 +337,44 @@ class Context:
         mp = np.zeros((self._n_pairs, model.S), np.int32) if want_map else None
         self._check(self._L.fsmc_decode_per_pair(self._h, model._h, _p(et), _p(mean), _p(mp)))
         return mean, mp
+
+    def decode_pair_posteriors(self, model: "Model", exp_coal_times, want_rows=True, sum_into=None, rows_out=None):
+        """The posterior tables of writePerPairOutput for the resident work list (fsmc_decode_pair_posteriors):
+        (rows [n_pairs][K][S] f32 or None, sum [K][S] f32 or None), every value posterior * exp_coal_times[k].
+        ``sum_into``: a [K][S] float32 array the pairs' values are added onto, pair after pair, in place (an earlier
+        call's sum continues); None = no sum.  ``rows_out``: n_pairs writable C-contiguous float32 arrays of K * S
+        values each to receive the rows instead of a new array (they are returned as they are)."""
+        et = np.ascontiguousarray(exp_coal_times, np.float32)
+        if et.shape != (model.K,):
+            raise ValueError(f"exp_coal_times: shape {et.shape}, expected {(model.K,)}")
+        rows = ptrs = None
+        if rows_out is not None:
+            rows = rows_out
+            if len(rows) != self._n_pairs:
+                raise ValueError("rows_out needs one array per pair of the work list")
+            for r in rows:
+                if r.dtype != np.float32 or not r.flags.c_contiguous or not r.flags.writeable or r.size != model.K * model.S:
+                    raise ValueError("rows_out: writable C-contiguous float32 arrays of K * S values")
+            ptrs = (C.c_void_p * self._n_pairs)(*[r.ctypes.data for r in rows])
+        elif want_rows:
+            rows = np.zeros((self._n_pairs, model.K, model.S), np.float32)
+            ptrs = (C.c_void_p * self._n_pairs)(*[rows.ctypes.data + i * rows.strides[0] for i in range(self._n_pairs)])
+        if sum_into is not None:
+            if (sum_into.dtype != np.float32 or not sum_into.flags.c_contiguous or not sum_into.flags.writeable
+                    or sum_into.shape != (model.K, model.S)):
+                raise ValueError("sum_into: a writable C-contiguous float32 array [K][S]")
+        self._check(self._L.fsmc_decode_pair_posteriors(self._h, model._h, _p(et), ptrs, _p(sum_into)))
+        return rows, sum_into
+
+    def set_pair_posterior_slice(self, groups: int):
+        """Groups fsmc_decode_pair_posteriors puts through the device at a time; 0 = automatic.  Results do not depend
+        on it."""
+        self._check(self._L.fsmc_ctx_set_pair_posterior_slice(self._h, groups))
+
+    def last_pair_posterior_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_posterior_slices(self._h, C.byref(v)))
+        return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):
         """augmentSumOverPairs for the resident work list: arrays [S][K] (sum, and 00/01/11 when asked).  ``into`` =

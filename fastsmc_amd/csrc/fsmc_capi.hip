@@ -19,6 +19,7 @@
 
 #include "fsmc_identify.h"
 #include "fsmc_instances.h"
+#include "fsmc_pair_posteriors.h"
 
 namespace fsmc
 {
@@ -124,6 +125,17 @@ struct fsmc_ctx {
   hipStream_t side = nullptr;   // the one-group-per-wave kernel of a paired decode runs here, beside the paired kernel
   hipEvent_t evFork = nullptr, evJoin = nullptr;
   DevBuf wsSide;
+
+  // fsmc_decode_pair_posteriors: the work list goes through the device in slices of groups
+  uint32_t ppSlice = 0;     // groups a slice, 0 = automatic
+  int lastPpSlices = 0;     // slices of the last call
+  DevBuf ppStage;           // the dump of one slice, [group][site][k][lane]
+  DevBuf ppRows;            // the rows of one slice, [pair][K][S]
+  DevBuf ppAcc;             // [expCoal K floats][sum K * S floats]
+  hipStream_t copyStream = nullptr; // the rows leave on this one, through the two pinned buffers
+  void* ppPinned[2] = {nullptr, nullptr};
+  size_t ppPinnedBytes = 0; // size of each
+  hipEvent_t evRows = nullptr, evCopied[2] = {nullptr, nullptr};
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -1030,6 +1042,16 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->evJoin) (void)hipEventDestroy(ctx->evJoin);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
   if (ctx->wsSide.p) (void)hipFree(ctx->wsSide.p);
+  if (ctx->copyStream) (void)hipStreamSynchronize(ctx->copyStream);
+  if (ctx->ppStage.p) (void)hipFree(ctx->ppStage.p);
+  if (ctx->ppRows.p) (void)hipFree(ctx->ppRows.p);
+  if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
+  for (int i = 0; i < 2; ++i) {
+    if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
+    if (ctx->evCopied[i]) (void)hipEventDestroy(ctx->evCopied[i]);
+  }
+  if (ctx->evRows) (void)hipEventDestroy(ctx->evRows);
+  if (ctx->copyStream) (void)hipStreamDestroy(ctx->copyStream);
   if (ctx->ownStream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -1136,6 +1158,24 @@ int fsmc_ctx_last_resident_chunks(const fsmc_ctx* ctx, int32_t* chunks)
     return FSMC_EINVAL;
   }
   *chunks = ctx->lastResident;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_pair_posterior_slice(fsmc_ctx* ctx, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->ppSlice = groups;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->lastPpSlices;
   return FSMC_OK;
 }
 
@@ -2058,6 +2098,208 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
   if (map) {
     FSMC_HIP(ctx, hipMemcpy(map, p.ppMap, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
+  return FSMC_OK;
+}
+
+// writePerPairOutput's posterior tables (HMM.cpp:1378-1392).  The work list goes through the device in slices of groups:
+// the dump consumers decode a slice into ppStage (the launch sees the slice as its whole group list: p.groups points at
+// the slice's first group of the resident list, dumpOffsets count from the slice's start), pair_posteriors_kernel turns
+// it into rows and continues the sum, and the rows of slice i leave through two pinned buffers on the copy stream
+// while slice i + 1 decodes.
+int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times,
+                                float* const* post_rows, float* sum)
+{
+  int rc = checkReady(ctx, m);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  if (!exp_coal_times || (!post_rows && !sum)) {
+    return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output (rows or sum)");
+  }
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "per-pair posteriors need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  if (post_rows) {
+    for (size_t i = 0; i < ctx->nPairs; ++i) {
+      if (!post_rows[i]) {
+        return fail(ctx, FSMC_EINVAL, "post_rows[" + std::to_string(i) + "] is null");
+      }
+    }
+  }
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t K = (size_t)m->K, S = (size_t)m->S;
+  const size_t plane = K * S;                      // floats of one pair's table, and of the sum
+  const size_t groupBytes = (size_t)kWave * plane * sizeof(float); // a group in the staging buffer; its rows at most
+  const bool wantRows = post_rows != nullptr;
+
+  // The slice: what a quarter of the card (or the caller's workspace limit) holds of staging and rows, and no more than
+  // the card has free beside a reserve -- the decode's workspace is allocated after this.
+  size_t slice = ctx->ppSlice;
+  if (slice == 0) {
+    uint64_t limit = ctx->wsLimit ? ctx->wsLimit : (uint64_t)(0.25 * (double)ctx->hbmBytes);
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+      const uint64_t room = (uint64_t)freeB + ctx->ppStage.bytes + ctx->ppRows.bytes;
+      const uint64_t reserve = 2ull << 30;
+      limit = std::min<uint64_t>(limit, room > reserve ? (room - reserve) / 2 : 0);
+    }
+    slice = (size_t)(limit / (groupBytes * (wantRows ? 2 : 1)));
+  }
+  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
+  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
+
+  KernelFn fn = pickKernel(kModeDump, false, m);
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
+  LaunchPlan plan;
+  earnWorkspace(ctx, m, kModeDump);
+  rc = planLaunch(ctx, m, kModeDump, fn, plan, &first);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  unsigned threads = blockThreads(kModeDump, m);
+  if (planTwoWaves(ctx, m, kModeDump, slice, fn, plan)) {
+    threads = 2 * kWave;
+  }
+  size_t slicePairsMax = 0;
+  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
+    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
+    slicePairsMax = std::max<size_t>(slicePairsMax, ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs -
+                                                      ctx->hGroups[g0].first_pair);
+  }
+  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * groupBytes);
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppAcc, (K + plane) * sizeof(float));
+  if (rc == FSMC_OK && wantRows) rc = ensure(ctx, ctx->ppRows, slicePairsMax * plane * sizeof(float));
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  // The way out for the rows: two pinned buffers of whole pairs each -- 128 MiB, or one pair's table if that is larger.
+  const size_t rowBytes = plane * sizeof(float);
+  size_t pairsPerCopy = 1;
+  if (wantRows) {
+    constexpr size_t kPinnedBytes = 128u << 20;
+    pairsPerCopy = std::max<size_t>(1, std::min<size_t>(kPinnedBytes / rowBytes, slicePairsMax));
+    const size_t need = pairsPerCopy * rowBytes;
+    if (ctx->ppPinnedBytes < need) {
+      for (int i = 0; i < 2; ++i) {
+        if (ctx->ppPinned[i]) {
+          (void)hipHostFree(ctx->ppPinned[i]);
+          ctx->ppPinned[i] = nullptr;
+        }
+      }
+      ctx->ppPinnedBytes = 0;
+      for (int i = 0; i < 2; ++i) {
+        const hipError_t e = hipHostMalloc(&ctx->ppPinned[i], need, hipHostMallocDefault);
+        if (e != hipSuccess) {
+          ctx->ppPinned[i] = nullptr;
+          return fail(ctx, FSMC_ENOMEM, std::string("hipHostMalloc of the row buffers failed: ") + hipGetErrorString(e));
+        }
+      }
+      ctx->ppPinnedBytes = need;
+    }
+    if (!ctx->copyStream) {
+      FSMC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copyStream, hipStreamNonBlocking));
+      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evRows, hipEventDisableTiming));
+      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[0], hipEventDisableTiming));
+      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[1], hipEventDisableTiming));
+    }
+  }
+
+  std::vector<size_t> offsets(slice);
+  for (size_t i = 0; i < slice; ++i) {
+    offsets[i] = i * (size_t)kWave * plane;
+  }
+  float* const dCoal = (float*)ctx->ppAcc.p;
+  float* const dSum = dCoal + K;
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(dCoal, exp_coal_times, K * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (sum) {
+    FSMC_HIP(ctx, hipMemcpyAsync(dSum, sum, plane * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets is a local, sum and exp_coal_times the caller's)
+
+  KParams p;
+  fillParams(ctx, m, plan, 0, p);
+  p.dumpOut = (float*)ctx->ppStage.p;
+  p.dumpOffsets = (const size_t*)ctx->aux.p;
+  PairPostParams q;
+  q.stage = (const float*)ctx->ppStage.p;
+  q.K = m->K;
+  q.S = m->S;
+  q.expCoal = dCoal;
+  q.rows = wantRows ? (float*)ctx->ppRows.p : nullptr;
+  q.sum = sum ? dSum : nullptr;
+  const dim3 grid((unsigned)((S + kWave - 1) / kWave), (unsigned)K);
+
+  // the rows of pairs [lo, hi) of the work list, which the device holds from row `lo - base` of ppRows on: copy by copy
+  // through the pinned buffers, the next copy in flight while the host moves the one before into the caller's rows
+  auto drain = [&](size_t base, size_t lo, size_t hi) -> int {
+    FSMC_HIP(ctx, hipStreamWaitEvent(ctx->copyStream, ctx->evRows, 0));
+    auto issue = [&](size_t c0, int b) -> int {
+      const size_t n = std::min(pairsPerCopy, hi - c0);
+      FSMC_HIP(ctx, hipMemcpyAsync(ctx->ppPinned[b], (const float*)ctx->ppRows.p + (c0 - base) * plane, n * rowBytes,
+                                   hipMemcpyDeviceToHost, ctx->copyStream));
+      FSMC_HIP(ctx, hipEventRecord(ctx->evCopied[b], ctx->copyStream));
+      return FSMC_OK;
+    };
+    int b = 0;
+    int r = issue(lo, b);
+    for (size_t c0 = lo; r == FSMC_OK && c0 < hi; c0 += pairsPerCopy, b ^= 1) {
+      const size_t n = std::min(pairsPerCopy, hi - c0);
+      if (c0 + pairsPerCopy < hi) {
+        r = issue(c0 + pairsPerCopy, b ^ 1);
+        if (r != FSMC_OK) {
+          break;
+        }
+      }
+      FSMC_HIP(ctx, hipEventSynchronize(ctx->evCopied[b]));
+      for (size_t i = 0; i < n; ++i) {
+        std::memcpy(post_rows[c0 + i], (const float*)ctx->ppPinned[b] + i * plane, rowBytes);
+      }
+    }
+    return r;
+  };
+
+  size_t prevLo = 0, prevHi = 0; // pairs of the slice whose rows are still on the device
+  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
+    const size_t nG = std::min(slice, ctx->nGroups - g0);
+    p.groups = ctx->dGroups + g0;
+    p.nGroups = (int)nG;
+    rc = launch(ctx, fn, p, (int)std::min<size_t>((size_t)plan.slots, nG), threads, 0, sl != 0);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+    if (prevHi > prevLo) { // (while this slice decodes; ppRows is free again when it returns)
+      rc = drain(prevLo, prevLo, prevHi);
+      if (rc != FSMC_OK) {
+        return rc;
+      }
+    }
+    q.groups = ctx->dGroups + g0;
+    q.nGroups = (int)nG;
+    q.firstPair = ctx->hGroups[g0].first_pair;
+    hipLaunchKernelGGL(pair_posteriors_kernel, grid, dim3(kWave), 0, ctx->stream, q);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every transposition)
+    if (wantRows) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+      prevLo = ctx->hGroups[g0].first_pair;
+      prevHi = ctx->hGroups[g0 + nG - 1].first_pair + ctx->hGroups[g0 + nG - 1].n_pairs;
+    }
+  }
+  if (prevHi > prevLo) {
+    rc = drain(prevLo, prevLo, prevHi);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (sum) {
+    FSMC_HIP(ctx, hipMemcpy(sum, dSum, plane * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  ctx->lastPpSlices = (int)nSlices;
   return FSMC_OK;
 }
 

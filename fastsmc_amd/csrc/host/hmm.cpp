@@ -942,7 +942,6 @@ void HMM::flush()
   if (!mParams.FastSMC && (storeAny || writeFiles)) {
     // writePerPairOutput (HMM.cpp:1360-1458)
     const size_t S = static_cast<size_t>(mData.sites);
-    const size_t K = mDq.states;
     auto& R = mPairsReturn;
     const size_t base = R.numWritten;
     if (storeAny && base + nPairs > static_cast<size_t>(R.numPairs)) {
@@ -956,26 +955,19 @@ void HMM::flush()
                                map.empty() ? nullptr : map.data()),
           "fsmc_decode_per_pair");
     if (mStorePosterior || mStoreSumOfPosterior) {
-      // full posteriors (times expected coalescence time, HMM.cpp:1382-1388) come from the posterior dump
-      std::vector<float> dump(static_cast<size_t>(64) * K * S * mGroups.size());
-      check(mCtx, fsmc_decode_posteriors(mCtx, mModel, dump.data(), dump.size()), "fsmc_decode_posteriors");
-      for (size_t g = 0; g < mGroups.size(); ++g) {
-        const float* gp = dump.data() + g * 64 * K * S;
-        for (uint32_t v = 0; v < mGroups[g].n_pairs; ++v) {
-          const size_t pairIdx = mGroups[g].first_pair + v;
-          for (size_t pos = 0; pos < S; ++pos) {
-            for (size_t k = 0; k < K; ++k) {
-              const float postValue = gp[(pos * K + k) * 64 + v] * mExpectedCoalTimes[k];
-              if (mStorePosterior) {
-                R.perPairPosteriors[base + pairIdx][k * S + pos] = postValue;
-              }
-              if (mStoreSumOfPosterior) {
-                R.sumOfPosteriors[k * S + pos] += postValue;
-              }
-            }
-          }
+      // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]
+      // table and continues the sum over pairs in pair order -- nothing but those tables crosses the bus
+      std::vector<float*> rows;
+      if (mStorePosterior) {
+        rows.resize(nPairs);
+        for (size_t i = 0; i < nPairs; ++i) {
+          rows[i] = R.perPairPosteriors[base + i].data();
         }
       }
+      check(mCtx,
+            fsmc_decode_pair_posteriors(mCtx, mModel, mExpectedCoalTimes.data(), mStorePosterior ? rows.data() : nullptr,
+                                        mStoreSumOfPosterior ? R.sumOfPosteriors.data() : nullptr),
+            "fsmc_decode_pair_posteriors");
     }
     if (writeFiles) {
       // HMM.cpp:1412-1420: `fout << matrix.topRows(actualBatchSize).format(m_eigenOutputFormat)` once per BATCH, with

@@ -16,6 +16,9 @@
  *   fsmc_decode_posteriors <- decodeBatch; result = m_alphaBuffer     (HMM.cpp:639-722)
  *   fsmc_decode_per_pair   <- decodeBatch + writePerPairOutput        (HMM.cpp:1360-1458)
  *   fsmc_decode_sums       <- decodeBatch + augmentSumOverPairs       (HMM.cpp:1044-1085)
+ *   fsmc_decode_pair_posteriors <- decodeBatch + the perPairPosteriors / sumOfPosteriors part of
+ *                             writePerPairOutput, the tables ASMC::decodePairs hands out
+ *                                                                    (HMM.cpp:1378-1392, ASMC.cpp:80-128)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -181,6 +184,12 @@ int fsmc_ctx_last_waves_per_window(const fsmc_ctx* ctx, int32_t* waves);
  * (K/4 + 1) KiB each beside the kernel's own -- a small job, whose waves would wait out every round trip of those sums
  * to L2.  The results do not depend on it. */
 int fsmc_ctx_last_segment_sums_in_lds(const fsmc_ctx* ctx, int32_t* in_lds);
+/* Tuning: groups of the work list that fsmc_decode_pair_posteriors decodes, transposes and copies out at a time (a
+ * "slice"); device memory, the pinned row buffers and nothing else are sized by it.  0 (default) = automatic: as many
+ * groups as a quarter of the card (or the workspace limit) and its free memory hold of the slice's dump and rows.
+ * Results do not depend on it.  fsmc_ctx_last_pair_posterior_slices: slices of the last such call. */
+int fsmc_ctx_set_pair_posterior_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -281,6 +290,20 @@ int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_
 /* writePerPairOutput: mean[n_pairs][S] = sum_k post*exp_times[k]; map[n_pairs][S] = first argmax_k post.
  * Either may be NULL.  Requires whole-sequence groups (from = 0, to = S), as in the reference (HMM.cpp:1378). */
 int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, float* mean, int32_t* map);
+
+/* writePerPairOutput's posterior tables (HMM.cpp:1378-1392; DecodePairsReturnStruct::perPairPosteriors and
+ * sumOfPosteriors) for the resident work list, in the layout the API hands out:
+ *   post_rows[i][k * S + pos] = posterior(pair i, pos, k) * exp_coal_times[k]   (one fp32 multiply; HMM.cpp:1382)
+ *   sum[k * S + pos]          = ((sum[k * S + pos] + v_0) + v_1) + ...          (the same values, added pair after pair
+ *                               in work-list order onto what the caller passes in)
+ * post_rows: n_pairs pointers to [K][S] floats each, or NULL; sum: [K][S], read AND written, or NULL; at least one of
+ * the two.  Several calls over consecutive parts of a pair list, each continuing the sum of the one before, give the
+ * bits of one call over the whole list.  The work list goes through the device in slices of groups
+ * (fsmc_ctx_set_pair_posterior_slice), the rows leave through pinned buffers while the next slice decodes: memory is
+ * bounded by the slice, and with sum alone only [K][S] floats cross the bus each way.  Requires whole-sequence groups
+ * (from = 0, to = S; FSMC_EINVAL otherwise), as in the reference. */
+int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times,
+                                float* const* post_rows, float* sum);
 
 /* augmentSumOverPairs: sums[S][K] += sum over the pairs of the work list of the posterior
  * (and the 00/01/11 split when the pointers are non-NULL).  Whole-sequence groups only. */
