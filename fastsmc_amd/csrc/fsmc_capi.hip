@@ -68,7 +68,7 @@ struct fsmc_ctx {
   uint64_t hbmBytes = 0;
   uint64_t wsLimit = 0;
   double wsEarned = 0; // bytes of workspace the launches so far (and the announced job) have paid for and not yet
-                       // spent on an allocation (earnWorkspace, fsmc_ctx_expect_work, planLaunch)
+                       // spent on an allocation (earnWorkspace, fsmc_ctx_expect_work, holdWorkspace)
   double wsAnnounced = 0; // estimated kernel seconds of announced work not launched yet (it has earned already)
   double wsAnnouncedCredit = 0; // ... and the bytes of credit that part of the announcement was given
   std::string err;
@@ -320,15 +320,6 @@ template <int KT> KernelFn pickMember(int mode, bool track, bool seq, bool half,
   }
 }
 
-// Beta stride 2 (every second beta row stored, the others recomputed in the alpha sweep): array-mode IBD decode and
-// array-mode sums over pairs (round 5: at size the sums moved 8K bytes a pair-site at the rate the CUs' path to memory
-// delivers -- the IBD decode's situation before stride 2) of the family members it is built for.
-bool halfAvailable(int mode, const fsmc_model* m)
-{
-  const int member = familyMember(m);
-  return !m->sequence && ((mode == kModeIbd && halfBuilt(member)) || (mode == kModeSums && halfSumsBuilt(member)));
-}
-
 // The wide-model kernel with lane = pair and several waves per group (fsmc_kernels_w2.h): 128 < K <= 1024, every
 // consumer, array and sequence mode.  fsmc_model_create picks the member (w2Member) and pads such a model's rows to
 // KP = waves x states per wave: four waves of 48 or 64 (two workgroups per CU) or 80 states, six to eight waves of 64,
@@ -396,12 +387,6 @@ template <int KH, int NW> KernelFn pickWaveGroupKernel(int mode, bool track, boo
   return seq ? pickWaveGroupKernelOf<KH, NW, true>(mode, track) : pickWaveGroupKernelOf<KH, NW, false>(mode, track);
 }
 
-// threads of a workgroup of the kernel pickKernel returns for this mode and model
-unsigned blockThreads(int mode, const fsmc_model* m)
-{
-  return waveGroups(mode, m) ? (unsigned)(m->w2NW * kWave) : (unsigned)kWave;
-}
-
 // more than 1024 states: the any-K kernel (fsmc_kernels_any.h)
 bool anyStates(const fsmc_model* m)
 {
@@ -424,46 +409,56 @@ template <bool SEQ> KernelFn pickAnyKernel(int mode, bool track)
   }
 }
 
-KernelFn pickKernel(int mode, bool track, const fsmc_model* m, bool dual = false)
+// What a launch needs to know of its kernel.  `member`: as fsmc_ctx::lastMember.  `stride`: the beta stride the kernel
+// is built for -- the plan lays the chunk buffer out for it, so everything downstream reads it from here.
+struct KernelChoice {
+  KernelFn fn = nullptr; // nullptr: no such kernel is built
+  unsigned threads = kWave;
+  int member = 0;
+  int stride = 1;
+};
+
+// The one-wave kernel of a model and mode.  `wantStride`: as fsmc_ctx::betaStride (the context's setting or the
+// caller's own decision).  `dual`: two half-groups per wave.  Writes nothing.
+// Beta stride 2 (every second beta row stored, the others recomputed in the alpha sweep): array-mode IBD decode and
+// array-mode sums over pairs (round 5: at size the sums moved 8K bytes a pair-site at the rate the CUs' path to memory
+// delivers -- the IBD decode's situation before stride 2) of the family members it is built for.
+KernelChoice chooseKernel(const fsmc_model* m, int mode, bool track, bool dual, uint32_t wantStride)
 {
+  KernelChoice k;
   if (anyStates(m)) {
-    if (mode == kModeIbd) {
-      m->ctx->lastStride = 1;
-    }
-    m->ctx->lastMember = 0;
-    return m->sequence ? pickAnyKernel<true>(mode, track) : pickAnyKernel<false>(mode, track);
+    k.fn = m->sequence ? pickAnyKernel<true>(mode, track) : pickAnyKernel<false>(mode, track);
+    return k;
   }
-  if (waveGroups(mode, m)) {
-    if (mode == kModeIbd) {
-      m->ctx->lastStride = 1;
-    }
+  if (waveGroups(mode, m)) { // a workgroup of NW waves takes a group
     const int NW = m->w2NW, KH = m->KP / NW;
+    k.threads = (unsigned)(NW * kWave);
     // 1048 ... 1112: four waves per group of 48 ... 112 states; 5064 ... 8064: five ... eight waves of 64
-    m->ctx->lastMember = NW == kW2NW ? 1000 + KH : 1000 * NW + KH; // (2128: two waves of 128)
+    k.member = NW == kW2NW ? 1000 + KH : 1000 * NW + KH; // (2128: two waves of 128)
 #define FSMC_PICK_W2(KHX, NWX)                                                                                          \
   if (KH == KHX && NW == NWX) {                                                                                        \
-    return pickWaveGroupKernel<KHX, NWX>(mode, track, m->sequence != 0);                                               \
+    k.fn = pickWaveGroupKernel<KHX, NWX>(mode, track, m->sequence != 0);                                               \
   }
     FSMC_ALL_W2(FSMC_PICK_W2)
 #undef FSMC_PICK_W2
-    return nullptr;
+    return k;
   }
-  const bool half = halfAvailable(mode, m) && m->ctx->betaStride != 1; // (also with two half-groups per wave)
-  if (mode == kModeIbd || mode == kModeSums) {
-    m->ctx->lastStride = half ? 2 : 1;
-  }
-  const int member = familyMember(m);
-  m->ctx->lastMember = member;
-  switch (member) {
+  k.member = familyMember(m);
+  const bool half = wantStride != 1 && !m->sequence && // (also with two half-groups per wave)
+                    ((mode == kModeIbd && halfBuilt(k.member)) || (mode == kModeSums && halfSumsBuilt(k.member)));
+  k.stride = half ? 2 : 1;
+  switch (k.member) {
 #define FSMC_PICK_CASE(KTX)                                                                                             \
   case KTX:                                                                                                            \
-    return pickMember<KTX>(mode, track, m->sequence, half, dual);
+    k.fn = pickMember<KTX>(mode, track, m->sequence, half, dual);                                                      \
+    break;
     FSMC_ALL_KT(FSMC_PICK_CASE)
     FSMC_EXACT_KT(FSMC_PICK_CASE)
 #undef FSMC_PICK_CASE
   default:
-    return nullptr; // (no such model passes fsmc_model_create: K <= 128 has a member, 128 < K <= 256 the wave-group kernel)
+    break; // (no such model passes fsmc_model_create: K <= 128 has a member, 128 < K <= 256 the wave-group kernel)
   }
+  return k;
 }
 
 // Two waves per window (fsmc_kernels_bidir.h): the dump / per-pair / sums consumers of the lane-per-pair family in
@@ -481,36 +476,65 @@ template <int KT> KernelFn pickBidirMember(int mode)
     return nullptr;
   }
 }
-KernelFn pickBidirKernel(int mode, const fsmc_model* m)
+KernelChoice chooseTwoWaveKernel(const fsmc_model* m, int mode)
 {
+  KernelChoice k{nullptr, 2 * kWave, familyMember(m), 1};
   if (m->sequence || anyStates(m) || waveGroups(mode, m)) {
-    return nullptr;
+    return k;
   }
-  switch (familyMember(m)) {
+  switch (k.member) {
 #define FSMC_PICK_BIDIR(KTX)                                                                                            \
   case KTX:                                                                                                            \
-    return pickBidirMember<KTX>(mode);
+    k.fn = pickBidirMember<KTX>(mode);                                                                                 \
+    break;
     FSMC_ALL_KT(FSMC_PICK_BIDIR)
     FSMC_EXACT_KT(FSMC_PICK_BIDIR)
 #undef FSMC_PICK_BIDIR
   default:
-    return nullptr;
+    break;
   }
+  return k;
 }
 
+// A diagnostic switch that lowers a count: NAME=<n> gives n / divisor where that is at least 1 and below `value`.
+size_t loweredByEnv(const char* name, size_t value, int divisor = 1)
+{
+  const char* s = std::getenv(name);
+  const long v = s ? std::atol(s) / divisor : 0;
+  return v >= 1 && (size_t)v < value ? (size_t)v : value;
+}
+
+// Workgroups of a kernel that a CU holds at once, as the runtime counts them, `most` at the most.  `capDivisor` > 0:
+// and no more than FSMC_DIAG_WAVES_PER_CU / capDivisor (occupancy experiments only).  The one occupancy query of the
+// launch path; 0 comes back for a kernel that cannot run at all.
+hipError_t workgroupsPerCU(const KernelChoice& k, int most, int capDivisor, int& perCU)
+{
+  perCU = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k.fn, (int)k.threads, 0);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return e;
+  }
+  perCU = std::min(perCU, most);
+  if (capDivisor > 0) {
+    perCU = (int)loweredByEnv("FSMC_DIAG_WAVES_PER_CU", (size_t)std::max(perCU, 0), capDivisor);
+  }
+  return hipSuccess;
+}
+
+// A launch, self-describing: its kernel (chunkRows is computed for its beta stride), a slot's layout, slots, bytes.
 struct LaunchPlan {
+  KernelChoice k;
   int chunk = 0;
   int chunkRows = 0; // rows of the chunk buffer (chunk, or half of it with beta stride 2)
   int maxChunks = 0;
   int residentChunks = 0; // chunk buffers beyond the first: chunks whose rows pass B keeps (no rebuild)
   size_t wsSlot = 0; // float4 per slot
   int slots = 0;
+  int wavesPerWindow = 1; // 2: the two-waves-per-window kernel, a workgroup per slot
+  size_t bytes = 0;       // of workspace: wsSlot float4 for every slot
 };
 
-// Decide chunking of the beta stream and the number of resident waves.
-// `items`: the list the waves will pull from when it is not the uploaded group list.  `paired`: two half-groups per
-// wave, `items` holding the union of each pair's windows.
-// `share`: the launch runs beside another one and may take 1/share of the workspace limit, in `ws`.
 // What a decode may spend on its workspace.
 // The most it can have (`hard`): the caller's limit if one is set (fsmc_ctx_set_workspace_limit); otherwise 80 % of the
 // card where that much is free (the card has 288 GB; the model, the haplotypes and the records are small), at least 40 %.
@@ -613,53 +637,40 @@ void earnWorkspace(fsmc_ctx* ctx, const fsmc_model* m, int mode)
   ctx->wsEarned += earnScale() * kEarnFraction * seconds * kAllocBytesPerSecond;
 }
 
-int planLaunch(fsmc_ctx* ctx, const fsmc_model* m, int mode, KernelFn fn, LaunchPlan& plan,
-               const std::vector<fsmc_group>* items = nullptr, bool paired = false, unsigned share = 1,
-               DevBuf* ws = nullptr)
+// Decide chunking of the beta stream and the number of resident waves of kernel `k` over `list`, the
+// groups its waves pull from.  `paired`: two half-groups per wave, `list` holding the union of each pair's windows.
+// `share`: the launch runs beside another one and may take 1/share of the budget.  Computes only: allocates nothing,
+// leaves the context as it is (holdWorkspace, recordLaunch).  `why`: the message of a status other than FSMC_OK.
+int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const KernelChoice& k,
+                const std::vector<fsmc_group>& list, bool paired, const WsBudget& budget, unsigned share,
+                LaunchPlan& plan, std::string& why)
 {
-  const std::vector<fsmc_group>& list = items ? *items : ctx->hGroups;
-  if (!fn) {
-    return fail(ctx, FSMC_EUNSUPPORTED, "no kernel for this model");
+  if (!k.fn) {
+    why = "no kernel for this model";
+    return FSMC_EUNSUPPORTED;
   }
-  int blocksPerCU = 0;
-  FSMC_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, fn, (int)blockThreads(mode, m), 0));
-  if (blocksPerCU < 1) {
-    blocksPerCU = 1;
-  }
-  if (blocksPerCU > 8) {
-    blocksPerCU = 8;
-  }
-  if (anyStates(m) && blocksPerCU > 4) {
-    // the any-K kernel streams its K-vectors through the caches: with four waves per CU more of them stay there
-    // (600 x 3000 list, K = 300: 1 / 2 / 4 / 8 waves per CU run 10.3 / 6.9 / 5.0 / 6.5 s)
-    blocksPerCU = 4;
-  }
-  if (const char* cap = std::getenv("FSMC_DIAG_WAVES_PER_CU")) { // occupancy experiments only
-    const int v = std::atoi(cap);
-    if (v >= 1 && v < blocksPerCU) {
-      blocksPerCU = v;
-    }
+  // the any-K kernel streams its K-vectors through the caches: with four waves per CU more of them stay there
+  // (600 x 3000 list, K = 300: 1 / 2 / 4 / 8 waves per CU run 10.3 / 6.9 / 5.0 / 6.5 s)
+  int perCU = 0;
+  const hipError_t e = workgroupsPerCU(k, anyStates(m) ? 4 : 8, 1, perCU);
+  if (e != hipSuccess) {
+    why = std::string("occupancy query of the decode kernel: ") + hipGetErrorString(e);
+    return FSMC_EHIP;
   }
   const bool w2 = waveGroups(mode, m); // a workgroup of four waves takes a group, lane = pair
-  size_t slots = (size_t)ctx->nCU * blocksPerCU;
-  slots = std::min(slots, list.size());
-  if (slots < 1) {
-    slots = 1;
-  }
+  const size_t slots = std::max<size_t>(1, std::min((size_t)ctx->nCU * std::max(perCU, 1), list.size()));
   size_t L = 1;
   for (const fsmc_group& g : list) {
     const size_t aEnd = (mode == kModeIbd) ? g.scan_to : g.to;
     L = std::max<size_t>(L, aEnd - g.from);
   }
   // float4 per lane of a stored K-vector: a padded family member (and the wave-group kernel) stores its ghosts too
-  const int member = familyMember(m);
-  // (the any-K kernel's rows carry their scale in one more float4)
-  const size_t K4 = w2 ? (size_t)m->KP / 4 : (size_t)((member > 0 ? member : m->K) + 3) / 4 + (anyStates(m) ? 1 : 0);
+  // (the any-K kernel, member 0, stores K states; its rows carry their scale in one more float4)
+  const size_t K4 = w2 ? (size_t)m->KP / 4 : (size_t)((k.member > 0 ? k.member : m->K) + 3) / 4 + (anyStates(m) ? 1 : 0);
   const size_t vecBytes = K4 * kWave * sizeof(float4);
-  const WsBudget budget = workspaceBudget(ctx, ws ? *ws : ctx->ws);
   const uint64_t limit = budget.hard / share;
   // Rows a chunk of C sites needs in the chunk buffer: with beta stride 2 only every second site's row is stored.
-  const bool half = halfAvailable(mode, m) && ctx->betaStride != 1;
+  const bool half = k.stride == 2;
   auto chunkRows = [&](size_t c) { return half ? (c + 1) / 2 : c; };
   const size_t rowsAvail = (size_t)(limit / (vecBytes * slots)); // rows one resident wave may hold
   const size_t rowsSoft = (size_t)(budget.soft / share / (vecBytes * slots)); // ... and may have earned so far
@@ -690,7 +701,8 @@ int planLaunch(fsmc_ctx* ctx, const fsmc_model* m, int mode, KernelFn fn, Launch
     }
     maxChunks = (L + C - 1) / C;
     if (!fits(C)) {
-      return fail(ctx, FSMC_ENOMEM, "workspace limit too small for the decode window");
+      why = "workspace limit too small for the decode window";
+      return FSMC_ENOMEM;
     }
   }
   // Resident chunks (fsmc_kernels.h): a chunked window rebuilds every chunk's rows from a checkpoint -- one of its 3.5
@@ -719,27 +731,21 @@ int planLaunch(fsmc_ctx* ctx, const fsmc_model* m, int mode, KernelFn fn, Launch
   plan.residentChunks = (int)resident;
   plan.wsSlot = (chunkRows(C) * (1 + resident) + maxChunks + 2 + (sideRows - 2)) * K4 * kWave;
   plan.slots = (int)slots;
-  ctx->lastChunk = plan.chunk;
-  ctx->lastMaxChunks = plan.maxChunks;
-  ctx->lastResident = plan.residentChunks;
-  DevBuf& buf = ws ? *ws : ctx->ws;
-  const size_t held = buf.bytes;
-  const int rc = ensure(ctx, buf, plan.wsSlot * sizeof(float4) * slots);
-  if (rc == FSMC_OK && buf.bytes != held) {
-    payForWorkspace(ctx, buf.bytes);
-  }
-  return rc;
+  plan.k = k;
+  plan.wavesPerWindow = 1;
+  plan.bytes = plan.wsSlot * sizeof(float4) * slots;
+  return FSMC_OK;
 }
 
 // A launch of the two-waves-per-window kernel, if this one qualifies: `nItems` workgroups (groups; batches of the sums)
 // that are ALL resident at once -- so the launch has at most half as many items as the chip holds waves of this member,
 // the case in which the one-wave kernel leaves every wave alone on a SIMD (or SIMDs idle) -- and whose whole windows fit
-// the workspace (to - from rows a workgroup; the same rule as planLaunch's whole windows: inside the hard budget, and
+// the workspace (to - from rows a workgroup; the same rule as planOneWave's whole windows: inside the hard budget, and
 // inside what the context has earned unless the window is no longer than a chunk would be).
-bool planTwoWaves(fsmc_ctx* ctx, const fsmc_model* m, int mode, size_t nItems, KernelFn& fn, LaunchPlan& plan)
+// twoWavesWanted: what can be said before the budget is read; planTwoWaves: the plan, false if it does not fit.
+bool twoWavesWanted(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems)
 {
-  ctx->lastWavesPerWindow = 1;
-  if (ctx->twoWaves == 1 || nItems == 0) {
+  if (ctx->twoWaves == 1 || nItems == 0 || !k2.fn) {
     return false;
   }
   if (const char* v = std::getenv("FSMC_DIAG_TWO_WAVE_WINDOWS")) { // tests: the whole suite on the one-wave kernels
@@ -747,57 +753,74 @@ bool planTwoWaves(fsmc_ctx* ctx, const fsmc_model* m, int mode, size_t nItems, K
       return false;
     }
   }
-  KernelFn f = pickBidirKernel(mode, m);
-  if (!f) {
-    return false;
-  }
-  int blocksPerCU = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, f, 2 * kWave, 0) != hipSuccess || blocksPerCU < 1) {
-    (void)hipGetLastError();
-    return false;
-  }
-  blocksPerCU = std::min(blocksPerCU, 4);
-  if (const char* cap = std::getenv("FSMC_DIAG_WAVES_PER_CU")) { // occupancy experiments only
-    const int v = std::atoi(cap) / 2;
-    if (v >= 1 && v < blocksPerCU) {
-      blocksPerCU = v;
-    }
-  }
-  if (nItems > (size_t)ctx->nCU * blocksPerCU) {
-    return false;
-  }
+  int perCU = 0;
+  return workgroupsPerCU(k2, 4, 2, perCU) == hipSuccess && perCU >= 1 && nItems <= (size_t)ctx->nCU * perCU;
+}
+
+bool planTwoWaves(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems, const WsBudget& budget, LaunchPlan& plan)
+{
   size_t L = 1;
   for (const fsmc_group& g : ctx->hGroups) {
     L = std::max<size_t>(L, g.to - g.from);
   }
-  const int member = familyMember(m);
-  const size_t K4 = (size_t)(member + 3) / 4;
-  const size_t vecBytes = K4 * kWave * sizeof(float4);
-  const WsBudget budget = workspaceBudget(ctx, ctx->ws);
-  const uint64_t need = (uint64_t)L * vecBytes * nItems;
-  if (need > budget.hard || (need > budget.soft && L > 512)) {
-    return false;
-  }
+  const size_t K4 = (size_t)(k2.member + 3) / 4;
   plan = LaunchPlan();
+  plan.k = k2;
   plan.chunk = (int)L;
   plan.chunkRows = (int)L;
   plan.maxChunks = 1;
   plan.wsSlot = L * K4 * kWave;
   plan.slots = (int)nItems;
-  const size_t held = ctx->ws.bytes;
-  if (ensure(ctx, ctx->ws, need) != FSMC_OK) {
-    ctx->err.clear();
-    return false;
+  plan.wavesPerWindow = 2;
+  plan.bytes = plan.wsSlot * sizeof(float4) * nItems;
+  return plan.bytes <= budget.hard && (plan.bytes <= budget.soft || L <= 512);
+}
+
+// The one place the decode's workspace is allocated: `buf` holds at least `bytes` afterwards, or nothing.  A buffer
+// that grows is freed first (it may be 80 % of the card: the two do not fit side by side) and debited from the credit.
+// (diagnostic: FSMC_DIAG_WS_ALLOC_MAX=<bytes>: a request above it goes the way of a hipMalloc that failed after the
+//  buffer held was released -- tests of what a launch does then)
+int holdWorkspace(fsmc_ctx* ctx, DevBuf& buf, size_t bytes)
+{
+  const char* most = std::getenv("FSMC_DIAG_WS_ALLOC_MAX");
+  if (most && bytes > std::strtoull(most, nullptr, 10) && !(buf.p && buf.bytes >= bytes)) {
+    if (buf.p) {
+      (void)hipFree(buf.p);
+    }
+    buf = DevBuf();
+    return fail(ctx, FSMC_ENOMEM, "workspace of " + std::to_string(bytes) + " bytes refused (FSMC_DIAG_WS_ALLOC_MAX)");
   }
-  if (ctx->ws.bytes != held) {
-    payForWorkspace(ctx, ctx->ws.bytes);
+  const size_t held = buf.bytes;
+  const int rc = ensure(ctx, buf, bytes);
+  if (rc != FSMC_OK) {
+    (void)hipGetLastError(); // (the failed hipMalloc's: a later launch's check must not find it)
+  } else if (buf.bytes != held) {
+    payForWorkspace(ctx, buf.bytes);
   }
+  return rc;
+}
+
+// One one-wave launch planned for `buf` and its workspace held.
+int planAndHold(fsmc_ctx* ctx, const fsmc_model* m, int mode, const KernelChoice& k, const std::vector<fsmc_group>& list,
+                bool paired, unsigned share, DevBuf& buf, LaunchPlan& plan)
+{
+  std::string why;
+  const int rc = planOneWave(ctx, m, mode, k, list, paired, workspaceBudget(ctx, buf), share, plan, why);
+  return rc != FSMC_OK ? fail(ctx, rc, why) : holdWorkspace(ctx, buf, plan.bytes);
+}
+
+// The launch the getters describe (fsmc_ctx_last_kernel, _last_beta_stride, _last_plan, _last_resident_chunks,
+// _last_waves_per_window, fsmc_ctx_info's n_slots): written here, where a launch is committed, and nowhere else.
+// `slotsBeside`: the workgroups of a second kernel that runs beside this one.
+void recordLaunch(fsmc_ctx* ctx, const KernelChoice& k, const LaunchPlan& plan, int slotsBeside = 0)
+{
+  ctx->lastMember = k.member;
+  ctx->lastStride = k.stride;
   ctx->lastChunk = plan.chunk;
-  ctx->lastMaxChunks = 1;
-  ctx->lastResident = 0;
-  ctx->lastWavesPerWindow = 2;
-  fn = f;
-  return true;
+  ctx->lastMaxChunks = plan.maxChunks;
+  ctx->lastResident = plan.residentChunks;
+  ctx->lastWavesPerWindow = plan.wavesPerWindow;
+  ctx->lastSlots = plan.slots + slotsBeside;
 }
 
 int checkReady(fsmc_ctx* ctx, const fsmc_model* m)
@@ -880,44 +903,114 @@ void fillParams(const fsmc_ctx* ctx, const fsmc_model* m, const LaunchPlan& plan
   p.recCap = (unsigned)ctx->recCap;
 }
 
+// The one shape the kernels cannot check: every workgroup of the grid indexes its own wsSlot float4 of the workspace.
+int checkWorkspace(fsmc_ctx* ctx, const KParams& p, int slots)
+{
+  const DevBuf& buf = p.ws == (float4*)ctx->wsSide.p ? ctx->wsSide : ctx->ws;
+  if (!p.ws || p.ws != (float4*)buf.p || slots < 1 || buf.bytes / sizeof(float4) / (size_t)slots < p.wsSlot) {
+    return fail(ctx, FSMC_ESTATE, "the workspace does not hold the launch planned for it");
+  }
+  return FSMC_OK;
+}
+
 // `continues`: a later launch of one call's sequence (the sums' batches, `slots` a launch): the timed span started with
 // the first one and ends behind the last (fsmc_last_kernel_ms: the whole sequence, its plane additions included).
-int launch(fsmc_ctx* ctx, KernelFn fn, const KParams& p, int slots, unsigned threads = kWave, size_t dynLds = 0,
-           bool continues = false)
+int launch(fsmc_ctx* ctx, const KernelChoice& k, const KParams& p, int slots, size_t dynLds = 0, bool continues = false)
 {
+  if (checkWorkspace(ctx, p, slots) != FSMC_OK) {
+    return FSMC_ESTATE;
+  }
   FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
   if (!continues) {
     FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)slots), dim3(threads), dynLds, ctx->stream, p);
+  hipLaunchKernelGGL(k.fn, dim3((unsigned)slots), dim3(k.threads), dynLds, ctx->stream, p);
   FSMC_HIP(ctx, hipGetLastError());
   FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
-  ctx->lastSlots = slots;
   return FSMC_OK;
 }
 
 // One decode as two kernels side by side: `pSide` (one group per wave; the long windows, so it starts first) on the
 // side stream and `pMain` (two half-groups per wave) on the context's stream.  They share the record buffer and its
 // counter and have a queue head each; the timed span covers both.
-int launchBeside(fsmc_ctx* ctx, KernelFn fnSide, KParams& pSide, int slotsSide, KernelFn fnMain, KParams& pMain,
-                 int slotsMain)
+int launchBeside(fsmc_ctx* ctx, const KernelChoice& kSide, KParams& pSide, int slotsSide, const KernelChoice& kMain,
+                 KParams& pMain, int slotsMain)
 {
+  if (checkWorkspace(ctx, pSide, slotsSide) != FSMC_OK || checkWorkspace(ctx, pMain, slotsMain) != FSMC_OK) {
+    return FSMC_ESTATE;
+  }
   FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
   FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   FSMC_HIP(ctx, hipEventRecord(ctx->evFork, ctx->stream));
   FSMC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->evFork, 0));
   pMain.groupBase = 0;
   pSide.groupBase = 2;
-  hipLaunchKernelGGL(fnSide, dim3((unsigned)slotsSide), dim3(kWave), 0, ctx->side, pSide);
+  hipLaunchKernelGGL(kSide.fn, dim3((unsigned)slotsSide), dim3(kSide.threads), 0, ctx->side, pSide);
   FSMC_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(fnMain, dim3((unsigned)slotsMain), dim3(kWave), 0, ctx->stream, pMain);
+  hipLaunchKernelGGL(kMain.fn, dim3((unsigned)slotsMain), dim3(kMain.threads), 0, ctx->stream, pMain);
   FSMC_HIP(ctx, hipGetLastError());
   FSMC_HIP(ctx, hipEventRecord(ctx->evJoin, ctx->side));
   FSMC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->evJoin, 0));
   FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
-  ctx->lastSlots = slotsSide + slotsMain;
+  return FSMC_OK;
+}
+
+// What output staging beside the workspace may take (the sums' planes, the pair posteriors' slices): the caller's
+// workspace limit or a quarter of the card, and no more than 1/`parts` of what the card has free -- `held`, the staging
+// this context holds already, counted as free -- beside a reserve of 2 GiB.
+uint64_t stagingLimit(const fsmc_ctx* ctx, uint64_t held, unsigned parts)
+{
+  uint64_t limit = ctx->wsLimit ? ctx->wsLimit : (uint64_t)(0.25 * (double)ctx->hbmBytes);
+  size_t freeB = 0, totalB = 0;
+  if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+    const uint64_t room = (uint64_t)freeB + held;
+    const uint64_t reserve = 2ull << 30;
+    limit = std::min<uint64_t>(limit, room > reserve ? (room - reserve) / parts : 0);
+  }
+  return limit;
+}
+
+// What the dump / per-pair / pair-posterior / sums entry points share: the kernel, the credit the launch earns, the
+// one-wave plan over `list` and its workspace; then, if a launch of `nItems` workgroups qualifies for two waves per
+// window, that plan and its workspace; the record of what was committed.  The one-wave workspace is held first: the
+// two-wave budget and the sums' plane limit count what is held, and a buffer only grows (a whole-window one-wave plan
+// needs no less than the two-wave plan: one allocation).  If the two-wave buffer cannot be had, the one-wave buffer is
+// taken again and the launch runs on that plan; FSMC_ENOMEM if that fails too.
+// `stagingPerItem` (the sums): bytes of output staging a workgroup needs beside the workspace; the slots are cut to the
+// items whose staging fits stagingLimit (and FSMC_DIAG_SUMS_SLOTS -- tests: many launches on a small problem), and two
+// waves, whose items are all resident at once, are taken only if that leaves all of them.
+int prepareDecode(fsmc_ctx* ctx, const fsmc_model* m, int mode, uint32_t wantStride,
+                  const std::vector<fsmc_group>& list, size_t nItems, size_t stagingPerItem, LaunchPlan& plan)
+{
+  const KernelChoice k = chooseKernel(m, mode, false, false, wantStride);
+  earnWorkspace(ctx, m, mode);
+  int rc = planAndHold(ctx, m, mode, k, list, false, 1, ctx->ws, plan);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  size_t staged = nItems;
+  if (stagingPerItem) {
+    staged = std::max<size_t>(1, (size_t)(stagingLimit(ctx, ctx->out.bytes, 1) / stagingPerItem));
+    staged = loweredByEnv("FSMC_DIAG_SUMS_SLOTS", staged);
+    plan.slots = (int)std::min({(size_t)plan.slots, nItems, staged});
+  }
+  const KernelChoice k2 = chooseTwoWaveKernel(m, mode);
+  LaunchPlan plan2;
+  if (staged >= nItems && twoWavesWanted(ctx, k2, nItems) &&
+      planTwoWaves(ctx, k2, nItems, workspaceBudget(ctx, ctx->ws), plan2)) {
+    if (holdWorkspace(ctx, ctx->ws, plan2.bytes) == FSMC_OK) {
+      plan = plan2;
+    } else {
+      ctx->err.clear();
+      rc = holdWorkspace(ctx, ctx->ws, plan.bytes);
+      if (rc != FSMC_OK) {
+        return rc;
+      }
+    }
+  }
+  recordLaunch(ctx, plan.k, plan);
   return FSMC_OK;
 }
 
@@ -1585,10 +1678,10 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   // The queues.  Two half-groups per wave for the half-full groups that pair up
   // (decode_kernel<..., DUAL>, with beta stride 2 where that is built); the other groups one per wave, in a kernel that
   // runs beside it.
-  KernelFn fnDual = nullptr;
+  KernelChoice kDual;
   uint64_t maxLen = 0, maxLenAlone = 0; // pairing budgets: beside a second kernel (half the workspace) / on its own
   if (ctx->pairing != 0 && !m->sequence && familyMember(m) > 0) {
-    fnDual = pickKernel(kModeIbd, track, m, true);
+    kDual = chooseKernel(m, kModeIbd, track, true, ctx->betaStride);
     // (the paired kernel has the chunked layout too: how long a window may be is no longer a question of memory)
     maxLen = maxLenAlone = 1u << 30;
   }
@@ -1636,19 +1729,22 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   const bool beside = q.dual && haveRest;
   LaunchPlan planDual, plan;
   if (q.dual) {
-    rc = planLaunch(ctx, m, kModeIbd, fnDual, planDual, &q.unions, true, q.alone ? 1 : 2);
+    rc = planAndHold(ctx, m, kModeIbd, kDual, q.unions, true, q.alone ? 1 : 2, ctx->ws, planDual);
     if (rc != FSMC_OK) {
       return rc;
     }
   }
-  KernelFn fn = pickKernel(kModeIbd, track, m, false); // (after the paired pick: last_kernel / last_beta_stride name this one)
+  const KernelChoice k = chooseKernel(m, kModeIbd, track, false, ctx->betaStride);
   if (haveRest) {
-    rc = planLaunch(ctx, m, kModeIbd, fn, plan, q.reordered ? &q.rest : nullptr, false, beside ? 2 : 1,
-                    beside ? &ctx->wsSide : nullptr);
+    rc = planAndHold(ctx, m, kModeIbd, k, q.reordered ? q.rest : ctx->hGroups, false, beside ? 2 : 1,
+                     beside ? ctx->wsSide : ctx->ws, plan);
     if (rc != FSMC_OK) {
       return rc;
     }
   }
+  // The getters describe the one-group-per-wave kernel (member, stride; also when every group rides in the paired
+  // kernel) and its plan -- the paired kernel's plan where there is no other -- with the workgroups of both kernels.
+  recordLaunch(ctx, k, haveRest ? plan : planDual, beside ? planDual.slots : 0);
   ctx->lastItems = q.dual ? (int)q.unions.size() : 0;
   if (ctx->recCap == 0) {
     ctx->recCap = std::max<size_t>(1u << 16, 8 * ctx->nPairs);
@@ -1678,10 +1774,9 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   // dynamic LDS a wave.  (A wave alone on its SIMD waits out every round trip of those sums to L2: C1 shape 40.6 -> 3x ms.)
   size_t spsLdsBytes = 0;
   if (!beside && !q.dual && track && !waveGroups(kModeIbd, m) && !anyStates(m) && !m->sequence) {
-    const int member = familyMember(m);
-    const size_t dyn = (size_t)((member > 0 ? member : m->K) + 3) / 4 * kWave * sizeof(float4);
+    const size_t dyn = (size_t)(k.member + 3) / 4 * kWave * sizeof(float4);
     hipFuncAttributes fa;
-    FSMC_HIP(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(fn)));
+    FSMC_HIP(ctx, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k.fn)));
     const size_t perWave = fa.sharedSizeBytes + dyn;
     constexpr size_t kLdsPerCU = 160u << 10, kLdsPerWorkgroup = 64u << 10;
     if (perWave <= kLdsPerWorkgroup && (size_t)plan.slots * perWave <= (size_t)ctx->nCU * kLdsPerCU &&
@@ -1691,9 +1786,8 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
     }
   }
   ctx->lastSpsLds = spsLdsBytes != 0;
-  rc = beside ? launchBeside(ctx, fn, p, plan.slots, fnDual, pDual, planDual.slots)
-              : q.dual ? launch(ctx, fnDual, pDual, planDual.slots)
-                       : launch(ctx, fn, p, plan.slots, blockThreads(kModeIbd, m), spsLdsBytes);
+  rc = beside ? launchBeside(ctx, k, p, plan.slots, kDual, pDual, planDual.slots)
+              : q.dual ? launch(ctx, kDual, pDual, planDual.slots) : launch(ctx, k, p, plan.slots, spsLdsBytes);
   if (rc != FSMC_OK) {
     return rc;
   }
@@ -2021,14 +2115,8 @@ int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_
   if (total > out_floats) {
     return fail(ctx, FSMC_EOVERFLOW, "posterior dump needs " + std::to_string(total) + " floats");
   }
-  KernelFn fn = pickKernel(kModeDump, false, m);
   LaunchPlan plan;
-  earnWorkspace(ctx, m, kModeDump);
-  rc = planLaunch(ctx, m, kModeDump, fn, plan);
-  unsigned threads = blockThreads(kModeDump, m);
-  if (rc == FSMC_OK && planTwoWaves(ctx, m, kModeDump, ctx->nGroups, fn, plan)) {
-    threads = 2 * kWave;
-  }
+  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan);
   if (rc == FSMC_OK) rc = ensure(ctx, ctx->aux, offsets.size() * sizeof(size_t));
   if (rc == FSMC_OK) rc = ensure(ctx, ctx->out, total * sizeof(float));
   if (rc != FSMC_OK) {
@@ -2040,7 +2128,7 @@ int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_
   fillParams(ctx, m, plan, 0, p);
   p.dumpOut = (float*)ctx->out.p;
   p.dumpOffsets = (const size_t*)ctx->aux.p;
-  rc = launch(ctx, fn, p, plan.slots, threads);
+  rc = launch(ctx, plan.k, p, plan.slots);
   if (rc != FSMC_OK) {
     return rc;
   }
@@ -2059,16 +2147,10 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
     return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output");
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
-  KernelFn fn = pickKernel(kModePerPair, false, m);
   LaunchPlan plan;
-  earnWorkspace(ctx, m, kModePerPair);
-  rc = planLaunch(ctx, m, kModePerPair, fn, plan);
+  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan);
   if (rc != FSMC_OK) {
     return rc;
-  }
-  unsigned threads = blockThreads(kModePerPair, m);
-  if (planTwoWaves(ctx, m, kModePerPair, ctx->nGroups, fn, plan)) {
-    threads = 2 * kWave;
   }
   const size_t n = ctx->nPairs * (size_t)m->S;
   const size_t coalBytes = (size_t)m->KP * sizeof(float);
@@ -2087,7 +2169,7 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
   p.expCoal = (const float*)base;
   p.ppMean = mean ? (float*)(base + coalBytes) : nullptr;
   p.ppMap = map ? (int*)(base + coalBytes + n * sizeof(float)) : nullptr;
-  rc = launch(ctx, fn, p, plan.slots, threads);
+  rc = launch(ctx, plan.k, p, plan.slots);
   if (rc != FSMC_OK) {
     return rc;
   }
@@ -2134,33 +2216,21 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
   const size_t groupBytes = (size_t)kWave * plane * sizeof(float); // a group in the staging buffer; its rows at most
   const bool wantRows = post_rows != nullptr;
 
-  // The slice: what a quarter of the card (or the caller's workspace limit) holds of staging and rows, and no more than
-  // the card has free beside a reserve -- the decode's workspace is allocated after this.
+  // The slice: what stagingLimit holds of staging and rows, of half the room the card has free -- the decode's
+  // workspace is allocated after this.
   size_t slice = ctx->ppSlice;
   if (slice == 0) {
-    uint64_t limit = ctx->wsLimit ? ctx->wsLimit : (uint64_t)(0.25 * (double)ctx->hbmBytes);
-    size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-      const uint64_t room = (uint64_t)freeB + ctx->ppStage.bytes + ctx->ppRows.bytes;
-      const uint64_t reserve = 2ull << 30;
-      limit = std::min<uint64_t>(limit, room > reserve ? (room - reserve) / 2 : 0);
-    }
-    slice = (size_t)(limit / (groupBytes * (wantRows ? 2 : 1)));
+    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes, 2) / (groupBytes * (wantRows ? 2 : 1)));
   }
   slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
   const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
 
-  KernelFn fn = pickKernel(kModeDump, false, m);
+  // (one wave per window: planned from the first slice's groups; two waves: a workgroup for each group of a slice)
   const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
   LaunchPlan plan;
-  earnWorkspace(ctx, m, kModeDump);
-  rc = planLaunch(ctx, m, kModeDump, fn, plan, &first);
+  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
   if (rc != FSMC_OK) {
     return rc;
-  }
-  unsigned threads = blockThreads(kModeDump, m);
-  if (planTwoWaves(ctx, m, kModeDump, slice, fn, plan)) {
-    threads = 2 * kWave;
   }
   size_t slicePairsMax = 0;
   for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
@@ -2267,7 +2337,7 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
     const size_t nG = std::min(slice, ctx->nGroups - g0);
     p.groups = ctx->dGroups + g0;
     p.nGroups = (int)nG;
-    rc = launch(ctx, fn, p, (int)std::min<size_t>((size_t)plan.slots, nG), threads, 0, sl != 0);
+    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
     if (rc != FSMC_OK) {
       return rc;
     }
@@ -2341,73 +2411,34 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
     }
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
-  KernelFn fn = pickKernel(kModeSums, false, m);
-  bool strideForced = false;
-  if (fn && ctx->betaStride == 0 && ctx->lastStride == 2) {
+  uint32_t wantStride = ctx->betaStride;
+  if (wantStride == 0) {
     // Beta stride 2 pays where the launch fills the chip (C2: 2762 -> 2454 ms: the rows' traffic was the bound); a wave
     // alone on its SIMD only gets the recomputed half sweep on top (C1 shape: 41.2 -> 43.3 ms).  Left to itself
-    // (fsmc_ctx_set_beta_stride 0) a launch of fewer batches than the chip holds waves keeps stride 1 -- the kernel AND
-    // its plan (planLaunch reads the same setting).
-    int blocksPerCU = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCU, fn, (int)blockThreads(kModeSums, m), 0) == hipSuccess &&
-        blocksPerCU >= 1 && n_batches < (size_t)ctx->nCU * (size_t)std::min(blocksPerCU, 8)) {
-      ctx->betaStride = 1;
-      strideForced = true;
-      fn = pickKernel(kModeSums, false, m);
+    // (fsmc_ctx_set_beta_stride 0) a launch of fewer batches than the chip holds waves keeps stride 1.
+    const KernelChoice k2 = chooseKernel(m, kModeSums, false, false, 0);
+    int perCU = 0;
+    if (k2.fn && k2.stride == 2 && workgroupsPerCU(k2, 8, 0, perCU) == hipSuccess && perCU >= 1 &&
+        n_batches < (size_t)ctx->nCU * (size_t)perCU) {
+      wantStride = 1;
     }
-  }
-  LaunchPlan plan;
-  earnWorkspace(ctx, m, kModeSums);
-  rc = planLaunch(ctx, m, kModeSums, fn, plan);
-  if (strideForced) {
-    ctx->betaStride = 0;
-  }
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  // a launch of few batches (at most half the chip's waves): two waves per window, a workgroup per batch
-  const KernelFn fnOne = fn;
-  const LaunchPlan planOne = plan;
-  unsigned threads = blockThreads(kModeSums, m);
-  if (planTwoWaves(ctx, m, kModeSums, n_batches, fn, plan)) {
-    threads = 2 * kWave;
   }
   // One launch decodes up to `slots` batches (one per wave; slots = resident waves, fewer if the planes would not fit)
   // and leaves each batch's sums in its own plane (the groups of a batch of more than 64 pairs in turn, each continuing
   // the running sums of the one before); add_planes_in_order_kernel then adds the planes to the accumulator in batch
   // order.  The accumulator starts from the caller's arrays, so that several calls (flushes)
   // continue the same sequential sum.
+  // A launch of few batches (at most half the chip's waves) whose planes all fit: two waves per window, a workgroup per
+  // batch (prepareDecode).
   const size_t plane = (size_t)m->S * m->K;
   const int nP = mm ? 4 : 1; // planes per group: the sum, or the sum and its 00 / 01 / 11 split
-  // what the planes may take: the caller's limit (or a quarter of the card) -- and no more than the card has left
-  // beside the workspace this context already holds
-  uint64_t limit = ctx->wsLimit ? ctx->wsLimit : (uint64_t)(0.25 * (double)ctx->hbmBytes);
-  {
-    size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-      const uint64_t room = (uint64_t)freeB + ctx->out.bytes;
-      const uint64_t reserve = 2ull << 30;
-      limit = std::min<uint64_t>(limit, room > reserve ? room - reserve : 0);
-    }
-  }
   const size_t slotFloats = (size_t)nP * plane; // a slot holds the planes the launch was asked for
-  size_t slots = std::min<size_t>((size_t)plan.slots, n_batches);
-  slots = std::max<size_t>(1, std::min<size_t>(slots, limit / (slotFloats * sizeof(float))));
-  if (const char* cap = std::getenv("FSMC_DIAG_SUMS_SLOTS")) { // tests: force many launches on a small problem
-    const long v = std::atol(cap);
-    if (v >= 1 && (size_t)v < slots) {
-      slots = (size_t)v;
-    }
+  LaunchPlan plan;
+  rc = prepareDecode(ctx, m, kModeSums, wantStride, ctx->hGroups, n_batches, slotFloats * sizeof(float), plan);
+  if (rc != FSMC_OK) {
+    return rc;
   }
-  if (threads != blockThreads(kModeSums, m) && slots < n_batches) {
-    // (the planes of all the batches do not fit one launch: the one-wave kernel, several launches)
-    fn = fnOne;
-    plan = planOne;
-    threads = blockThreads(kModeSums, m);
-    ctx->lastWavesPerWindow = 1;
-    ctx->lastChunk = plan.chunk;
-    ctx->lastMaxChunks = plan.maxChunks;
-  }
+  const size_t slots = (size_t)plan.slots;
   rc = ensure(ctx, ctx->out, (slots + 1) * slotFloats * sizeof(float));
   if (rc != FSMC_OK) {
     return rc;
@@ -2437,7 +2468,7 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   for (size_t base = 0; base < n_batches; base += slots) {
     const size_t n = std::min(slots, n_batches - base);
     p.groupBase = (int)base;
-    rc = launch(ctx, fn, p, (int)n, threads, 0, base != 0);
+    rc = launch(ctx, plan.k, p, (int)n, 0, base != 0);
     if (rc != FSMC_OK) {
       return rc;
     }

@@ -81,7 +81,7 @@ def _check(case, stride=0, chunk=0, resident=None, consumers=True, waves=None):
     for flags in ALL_FLAGS:
         got = ctx.decode_ibd(model, pr, groups, flags)
         assert ctx.last_kernel() == expected_member(K), what
-        if stride:  # (sequence mode has no stride-2 kernels: halfAvailable, csrc/fsmc_capi.hip)
+        if stride:  # (sequence mode has no stride-2 kernels: chooseKernel, csrc/fsmc_capi.hip)
             assert ctx.last_beta_stride() == (1 if seq else stride), what
         if chunk:
             assert ctx.info()["max_chunks"] > 1, what

@@ -191,3 +191,132 @@ def test_large_launches_and_other_models_keep_one_wave():
     ctx.decode_sums(model)
     assert ctx.last_waves_per_window() == 1
     ctx.close()
+
+
+def _oracle_consumers(sp, pairs):
+    """Dump, per-pair rows and sums of the oracle for whole-sequence groups of 64 pairs."""
+    pm, folded = sp["model"], sp["folded"]
+    posts, means, maps = [], [], []
+    sums = [np.zeros((pm.S, pm.K), np.float32) for _ in range(4)]
+    for b0 in range(0, len(pairs), 64):
+        sub = pairs[b0:b0 + 64]
+        ob = np.stack([folded[a] ^ folded[b] for a, b in sub])
+        hb = np.stack([folded[a] & folded[b] for a, b in sub])
+        post, _ = O.decode_batch(pm, ob, hb, 0, pm.S)
+        mean, mp, _ = O.per_pair_output(pm, post, len(sub))
+        O.augment_sum_over_pairs(pm, post, len(sub), ob, hb, *sums)
+        posts.append(post)
+        means.append(mean)
+        maps.append(mp)
+    return posts, np.concatenate(means), np.concatenate(maps), sums
+
+
+def test_sums_whose_planes_do_not_fit_report_the_one_wave_plan_they_ran(small_problem, monkeypatch):
+    """Three batches qualify for two waves per window, but FSMC_DIAG_SUMS_SLOTS=2 leaves room for the planes of two: the
+    launches run the one-wave kernel on its chunked plan with resident chunks, and every getter says so -- the same
+    with two-wave windows automatic and switched off."""
+    pm = small_problem["model"]
+    pairs = O.enumerate_all_pairs(32)[:192]
+    want = _oracle_consumers(small_problem, pairs)[3]
+    monkeypatch.setenv("FSMC_DIAG_SUMS_SLOTS", "2")
+    seen = {}
+    for mode in (0, 1):  # automatic, never
+        ctx = capi.Context(0)
+        ctx.set_two_wave_windows(mode)
+        ctx.set_workspace_limit(1 << 30)
+        ctx.set_chunk_sites(64)  # 640 sites: ten chunks; 1 GiB over three slots leaves room for every one of them
+        model = ctx.create_model(pm)
+        ctx.upload_haps(small_problem["bits"], pm.S)
+        ctx.upload_worklist(_pairs_array(pairs), capi.whole_sequence_groups(len(pairs), pm.S))
+        s, mm = ctx.decode_sums(model, major_minor=True)
+        info = ctx.info()
+        seen[mode] = (ctx.last_waves_per_window(), ctx.last_resident_chunks(), ctx.last_beta_stride(),
+                      info["chunk_sites"], info["max_chunks"])
+        ctx.close()
+        np.testing.assert_array_equal(s, want[0], err_msg=f"mode {mode}")
+        for got, w in zip(mm, want[1:]):
+            np.testing.assert_array_equal(got, w, err_msg=f"mode {mode}")
+    assert seen[0] == seen[1]
+    assert seen[1][0] == 1 and seen[1][1] > 0 and seen[1][3] == 64 and seen[1][4] == 10
+
+
+def test_two_wave_workspace_that_cannot_be_had_falls_back_to_the_one_wave_plan(small_problem, monkeypatch):
+    """FSMC_DIAG_WS_ALLOC_MAX between the one-wave plan's workspace and the two-wave plan's: the larger request goes the
+    way of a failed allocation (the buffer held is gone by then), the one-wave buffer is taken again and every consumer
+    runs one wave per window with the results it always has.  Below the one-wave need too, the call fails with
+    FSMC_ENOMEM and the context serves the next call."""
+    pm = small_problem["model"]
+    pairs = O.enumerate_all_pairs(32)[:151]  # 64 + 64 + 23
+    groups = capi.whole_sequence_groups(len(pairs), pm.S)
+    w_post, w_mean, w_map, w_sums = _oracle_consumers(small_problem, pairs)
+    row = (69 + 3) // 4 * 64 * 16  # bytes of a stored K-vector of the 69-state member: float4 per lane
+
+    def context(mode):
+        ctx = capi.Context(0)
+        ctx.set_two_wave_windows(mode)
+        ctx.set_chunk_sites(64)  # the one-wave plan: a chunk, a checkpoint per chunk and four side rows a slot ...
+        ctx.set_resident_chunks(0)  # ... and nothing else
+        model = ctx.create_model(pm)
+        ctx.upload_haps(small_problem["bits"], pm.S)
+        ctx.upload_worklist(_pairs_array(pairs), groups)
+        return ctx, model
+
+    def consumers(ctx, model):
+        post = ctx.decode_posteriors(model)
+        waves = [ctx.last_waves_per_window()]
+        mean, mp = ctx.decode_per_pair(model, pm.exp_times)
+        waves.append(ctx.last_waves_per_window())
+        s, mm = ctx.decode_sums(model, major_minor=True)
+        waves.append(ctx.last_waves_per_window())
+        return waves, post, mean, mp, s, mm
+
+    def same(got, want):
+        for a, b in zip(got[1], want[1]):
+            np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(got[2], want[2])
+        np.testing.assert_array_equal(got[3], want[3])
+        np.testing.assert_array_equal(got[4], want[4])
+        for a, b in zip(got[5], want[5]):
+            np.testing.assert_array_equal(a, b)
+
+    ctx, model = context(1)
+    ctx.decode_posteriors(model)
+    info = ctx.info()
+    ctx.close()
+    assert (info["chunk_sites"], info["max_chunks"], info["n_slots"]) == (64, 10, 3)
+    need_one = (info["chunk_sites"] + info["max_chunks"] + 4) * row * info["n_slots"]
+    ctx, model = context(0)
+    plain = consumers(ctx, model)
+    info = ctx.info()
+    ctx.close()
+    assert plain[0] == [2, 2, 2] and (info["chunk_sites"], info["max_chunks"], info["n_slots"]) == (pm.S, 1, 3)
+    need_two = info["chunk_sites"] * row * info["n_slots"]
+    assert need_one < need_two
+    for gi, wp in enumerate(w_post):
+        np.testing.assert_array_equal(plain[1][gi][:, :, :wp.shape[2]], wp)
+    np.testing.assert_array_equal(plain[2], w_mean)
+    np.testing.assert_array_equal(plain[3], w_map)
+    np.testing.assert_array_equal(plain[4], w_sums[0])
+    for a, b in zip(plain[5], w_sums[1:]):
+        np.testing.assert_array_equal(a, b)
+
+    monkeypatch.setenv("FSMC_DIAG_WS_ALLOC_MAX", str((need_one + need_two) // 2))
+    ctx, model = context(0)
+    fell_back = consumers(ctx, model)
+    assert fell_back[0] == [1, 1, 1]
+    assert (ctx.info()["chunk_sites"], ctx.info()["max_chunks"]) == (64, 10)
+    same(fell_back, plain)
+    ctx.close()
+
+    monkeypatch.setenv("FSMC_DIAG_WS_ALLOC_MAX", str(need_one // 2))
+    ctx, model = context(0)
+    for call in (lambda: ctx.decode_posteriors(model), lambda: ctx.decode_per_pair(model, pm.exp_times),
+                 lambda: ctx.decode_sums(model, major_minor=True)):
+        with pytest.raises(capi.FsmcError) as err:
+            call()
+        assert err.value.code == -4  # FSMC_ENOMEM
+    monkeypatch.delenv("FSMC_DIAG_WS_ALLOC_MAX")
+    served = consumers(ctx, model)
+    assert served[0] == [2, 2, 2]
+    same(served, plain)
+    ctx.close()
