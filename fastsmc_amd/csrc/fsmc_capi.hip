@@ -1887,7 +1887,11 @@ int fsmc_identify_ex(fsmc_ctx* ctx, const uint64_t* words, uint32_t n_haps, uint
   p.job = *job;
   p.gen = (const float*)b.p[2];
   p.nSites = n_sites;
-  p.gap = gap;
+  // An interval is reported before the end only when end < cur - gap with 0 <= end and cur < n_words: never for
+  // gap >= n_words, so every such gap is the same as gap = n_words.  Clamped, end + gap + 1 (the word at which an
+  // interval runs out, id_match_kernel) stays far from INT_MAX and flush_word never exceeds n_words, the bound
+  // idSortCandidates sizes its keys by.
+  p.gap = (int)std::min<uint32_t>((uint32_t)gap, n_words);
   p.skip = skip;
   p.minM = min_m;
   p.dupBits = (unsigned*)b.p[3];

@@ -235,7 +235,9 @@ typedef struct {
 /* words: [n_haps][n_words] host, word w of haplotype h (bit s%64 of word s/64 = allele of site s); global_ids:
  * [n_haps] haplotype numbers in the whole file (2 * sample line + 0/1); gen_pos: [n_sites] Morgans.  Fills `out` with
  * the candidates ordered by (flush_word, hap_a * n_haps + hap_b) -- the order in which fastsmc_amd hands them to
- * HMM::decodeFromHashing.  FSMC_EOVERFLOW: cap too small, *n_out = the number of candidates. */
+ * HMM::decodeFromHashing.  FSMC_EOVERFLOW: cap too small, *n_out = the number of candidates.
+ * gap: any value >= 0.  A gap of n_words or more can never run out before the last word, so every such value means
+ * the same as n_words and is taken as n_words (flush_word is then n_words for every candidate). */
 int fsmc_identify(fsmc_ctx* ctx, const uint64_t* words, uint32_t n_haps, uint32_t n_words, const uint32_t* global_ids,
                   const fsmc_job_window* job, const float* gen_pos, uint32_t n_sites, int32_t gap, float skip,
                   float min_m, fsmc_candidate* out, size_t cap, size_t* n_out);

@@ -8,7 +8,10 @@ Checkers, all integer-exact (the candidate list must be EQUAL, order included):
 Cases: the options the reference exposes (min_m, gap, skip, min_maf, folding off), job windows (jobs = 4, 9: per job
 equal to the restatement, over all jobs a partition of the single-job list), ragged shapes through the raw C ABI
 (haplotypes and words that do not fill a tile, fewer than two haplotypes, no complete word), low-complexity words,
-the overflow protocol, and a cohort big enough to fill the machine."""
+the overflow protocol, and a cohort big enough to fill the machine.
+The inputs here are founder mosaics; the kernels' own edges (chunk boundaries, the LDS stage, the buffer protocol, the
+deepest seed split, huge gaps) are built on purpose in tests/identify_edges.py and run by
+tests/test_gpu_identify_edges.py (tests/test_identify_edges.py: the same cases on the CPU)."""
 import numpy as np
 import pytest
 
