@@ -35,6 +35,7 @@ SYMBOLS = [
     "fsmc_decode_ibd",
     "fsmc_decode_posteriors", "fsmc_decode_per_pair", "fsmc_decode_sums", "fsmc_decode_sums_batches",
     "fsmc_decode_pair_posteriors", "fsmc_ctx_set_pair_posterior_slice", "fsmc_ctx_last_pair_posterior_slices",
+    "fsmc_decode_pair_minima", "fsmc_ctx_set_pair_minima_slice", "fsmc_ctx_last_pair_minima_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -123,6 +124,9 @@ def load():
         L.fsmc_decode_pair_posteriors.argtypes = [vp, vp, vp, vp, vp]
         L.fsmc_ctx_set_pair_posterior_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_posterior_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_minima.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
+        L.fsmc_ctx_set_pair_minima_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_minima_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -374,6 +378,44 @@ class Context:
     def last_pair_posterior_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_posterior_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_minima(self, model: "Model", exp_coal_times, pair_base=0, want_mean=True, want_map=True, state=None):
+        """Per site the smallest posterior mean / MAP over the pairs of the resident work list and the first pair that
+        has it (fsmc_decode_pair_minima): (min_mean [S] f32, argmin_mean [S] i32, min_map [S] i32, argmin_map [S] i32),
+        None for an output that was not asked for; argmin = ``pair_base`` + position in the work list.  ``state``: four
+        such arrays (None where not wanted), written in place and returned as they are; with ``pair_base`` > 0 they are
+        the chain's state after the pairs before this list and must be given, with ``pair_base`` == 0 what they hold
+        is ignored."""
+        et = np.ascontiguousarray(exp_coal_times, np.float32)
+        if et.shape != (model.K,):
+            raise ValueError(f"exp_coal_times: shape {et.shape}, expected {(model.K,)}")
+        if state is None:
+            if pair_base:
+                raise ValueError("pair_base > 0 continues a chain: pass its state")
+            state = (np.zeros(model.S, np.float32) if want_mean else None,
+                     np.zeros(model.S, np.int32) if want_mean else None,
+                     np.zeros(model.S, np.int32) if want_map else None,
+                     np.zeros(model.S, np.int32) if want_map else None)
+        state = tuple(state)
+        if len(state) != 4:
+            raise ValueError("state: (min_mean, argmin_mean, min_map, argmin_map)")
+        for a, dt in zip(state, (np.float32, np.int32, np.int32, np.int32)):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable
+                                  or a.shape != (model.S,)):
+                raise ValueError("state: writable C-contiguous arrays [S], float32 for min_mean, int32 for the others")
+        self._check(self._L.fsmc_decode_pair_minima(self._h, model._h, _p(et), int(pair_base), _p(state[0]),
+                                                    _p(state[1]), _p(state[2]), _p(state[3])))
+        return state
+
+    def set_pair_minima_slice(self, groups: int):
+        """Groups fsmc_decode_pair_minima puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_minima_slice(self._h, groups))
+
+    def last_pair_minima_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_minima_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):

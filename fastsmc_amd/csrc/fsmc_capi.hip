@@ -19,6 +19,7 @@
 
 #include "fsmc_identify.h"
 #include "fsmc_instances.h"
+#include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
 
 namespace fsmc
@@ -136,6 +137,11 @@ struct fsmc_ctx {
   void* ppPinned[2] = {nullptr, nullptr};
   size_t ppPinnedBytes = 0; // size of each
   hipEvent_t evRows = nullptr, evCopied[2] = {nullptr, nullptr};
+
+  // fsmc_decode_pair_minima: slices of groups as above; the slice's mean / MAP rows share ppStage
+  uint32_t pmSlice = 0;     // groups a slice, 0 = automatic
+  int lastPmSlices = 0;     // slices of the last call
+  DevBuf pmAcc;             // [expCoal KP floats][the carried state, 4 x S][the ranges' partials, 4 x nRanges x S]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -1139,6 +1145,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->ppStage.p) (void)hipFree(ctx->ppStage.p);
   if (ctx->ppRows.p) (void)hipFree(ctx->ppRows.p);
   if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
+  if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   for (int i = 0; i < 2; ++i) {
     if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
     if (ctx->evCopied[i]) (void)hipEventDestroy(ctx->evCopied[i]);
@@ -1269,6 +1276,24 @@ int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices)
     return FSMC_EINVAL;
   }
   *slices = ctx->lastPpSlices;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_pair_minima_slice(fsmc_ctx* ctx, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->pmSlice = groups;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->lastPmSlices;
   return FSMC_OK;
 }
 
@@ -2374,6 +2399,150 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
     FSMC_HIP(ctx, hipMemcpy(sum, dSum, plane * sizeof(float), hipMemcpyDeviceToHost));
   }
   ctx->lastPpSlices = (int)nSlices;
+  return FSMC_OK;
+}
+
+// finaliseCalculations' column-wise min / first argmin of the per-pair means and MAPs (hmm.cpp:151-184) without the
+// rows: the per-pair consumers decode a slice of groups into ppStage (p.groups points at the slice's first group of the
+// resident list; the consumers index rows by pair of the work list, so the launch gets the staging pointers moved back
+// by the slice's first pair), pair_minima_kernel reduces the slice's rows range by range, pair_minima_combine_kernel
+// continues the chain in the device copy of the state (fsmc_pair_minima.h).
+int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, uint64_t pair_base,
+                            float* min_mean, int32_t* argmin_mean, int32_t* min_map, int32_t* argmin_map)
+{
+  int rc = checkReady(ctx, m);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  const bool wantMean = min_mean || argmin_mean, wantMap = min_map || argmin_map;
+  if (!exp_coal_times || (!wantMean && !wantMap)) {
+    return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output (mean or MAP minima)");
+  }
+  if ((wantMean && !(min_mean && argmin_mean)) || (wantMap && !(min_map && argmin_map))) {
+    return fail(ctx, FSMC_EINVAL, "a minimum and its argmin come together");
+  }
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "per-pair minima need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  if (pair_base > (uint64_t)INT32_MAX || pair_base + (uint64_t)ctx->nPairs > (uint64_t)INT32_MAX) {
+    return fail(ctx, FSMC_EINVAL, "pair_base + pairs of the work list exceeds the range of the int32 argmin");
+  }
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t S = (size_t)m->S;
+  const int nOut = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
+  const size_t groupBytes = (size_t)kWave * S * sizeof(float) * (size_t)nOut; // a full group's rows in the staging buffer
+
+  // The slice: what stagingLimit holds of rows, of half the room the card has free -- the decode's workspace is
+  // allocated after this.
+  size_t slice = ctx->pmSlice;
+  if (slice == 0) {
+    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes, 2) / groupBytes);
+  }
+  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
+  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
+
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
+  LaunchPlan plan;
+  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, first, slice, 0, plan);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  auto pairsOfSlice = [&](size_t g0) {
+    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
+    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
+  };
+  size_t slicePairsMax = 0;
+  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
+    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
+  }
+  // The ranges: a wave owns 64 sites of one range.  A large slice is cut so that every SIMD of the chip gets a few waves
+  // (4 x 4 x CUs of them over the site blocks), a range no shorter than 16 pairs: the partials stay a small fraction of
+  // the rows.  FSMC_DIAG_MINIMA_RANGE=<pairs> -- tests: several ranges on a small problem.
+  const size_t siteBlocks = (S + kWave - 1) / kWave;
+  const size_t wavesWanted = (size_t)16 * (size_t)ctx->nCU;
+  const size_t rangesWanted = std::max<size_t>(1, (wavesWanted + siteBlocks - 1) / siteBlocks);
+  size_t rangeLen = std::max<size_t>(16, (slicePairsMax + rangesWanted - 1) / rangesWanted);
+  rangeLen = loweredByEnv("FSMC_DIAG_MINIMA_RANGE", rangeLen);
+  const size_t rangesMax = (slicePairsMax + rangeLen - 1) / rangeLen;
+  if (rangesMax * siteBlocks > (size_t)INT32_MAX) {
+    return fail(ctx, FSMC_EINVAL, "too many ranges for one launch (FSMC_DIAG_MINIMA_RANGE)");
+  }
+
+  const size_t coalBytes = (size_t)m->KP * sizeof(float);
+  const size_t vec = S * sizeof(float); // one [S] vector of floats or int32s
+  rc = ensure(ctx, ctx->ppStage, slicePairsMax * S * sizeof(float) * (size_t)nOut);
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pmAcc, coalBytes + 4 * vec + 4 * rangesMax * vec);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  char* const acc = (char*)ctx->pmAcc.p;
+  std::vector<float> coal((size_t)m->KP, 0.f);
+  std::memcpy(coal.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
+  FSMC_HIP(ctx, hipMemcpyAsync(acc, coal.data(), coalBytes, hipMemcpyHostToDevice, ctx->stream));
+  void* const dState[4] = {acc + coalBytes, acc + coalBytes + vec, acc + coalBytes + 2 * vec, acc + coalBytes + 3 * vec};
+  void* const hState[4] = {min_mean, argmin_mean, min_map, argmin_map};
+  if (pair_base > 0) { // the chain continues: the caller's arrays are its state
+    for (int i = 0; i < 4; ++i) {
+      if (hState[i]) {
+        FSMC_HIP(ctx, hipMemcpyAsync(dState[i], hState[i], vec, hipMemcpyHostToDevice, ctx->stream));
+      }
+    }
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (coal is a local, the state the caller's)
+
+  float* const stageMean = wantMean ? (float*)ctx->ppStage.p : nullptr;
+  int* const stageMap = wantMap ? (int*)ctx->ppStage.p + (wantMean ? slicePairsMax * S : 0) : nullptr;
+  char* const parts = acc + coalBytes + 4 * vec;
+  KParams p;
+  fillParams(ctx, m, plan, 0, p);
+  p.expCoal = (const float*)acc;
+  PairMinimaParams q;
+  q.mean = stageMean;
+  q.map = stageMap;
+  q.S = m->S;
+  q.rangeLen = (int)rangeLen;
+  q.partMinMean = (float*)parts;
+  q.partArgMean = (int*)(parts + rangesMax * vec);
+  q.partMinMap = (int*)(parts + 2 * rangesMax * vec);
+  q.partArgMap = (int*)(parts + 3 * rangesMax * vec);
+  q.minMean = (float*)dState[0];
+  q.argMean = (int*)dState[1];
+  q.minMap = (int*)dState[2];
+  q.argMap = (int*)dState[3];
+
+  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
+    const size_t nG = std::min(slice, ctx->nGroups - g0);
+    const size_t firstPair = ctx->hGroups[g0].first_pair;
+    const size_t n = pairsOfSlice(g0);
+    p.groups = ctx->dGroups + g0;
+    p.nGroups = (int)nG;
+    // (row `pair` of the work list is row `pair - firstPair` of the staging buffer)
+    p.ppMean = stageMean ? stageMean - firstPair * S : nullptr;
+    p.ppMap = stageMap ? stageMap - firstPair * S : nullptr;
+    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+    q.n = (int)n;
+    q.nRanges = (int)((n + rangeLen - 1) / rangeLen);
+    q.seeded = (pair_base == 0 && sl == 0) ? 1 : 0;
+    q.firstIndex = (int)(pair_base + firstPair);
+    hipLaunchKernelGGL(pair_minima_kernel, dim3((unsigned)((size_t)q.nRanges * siteBlocks)), dim3(kWave), 0, ctx->stream,
+                       q);
+    FSMC_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(pair_minima_combine_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, q);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < 4; ++i) {
+    if (hState[i]) {
+      FSMC_HIP(ctx, hipMemcpy(hState[i], dState[i], vec, hipMemcpyDeviceToHost));
+    }
+  }
+  ctx->lastPmSlices = (int)nSlices;
   return FSMC_OK;
 }
 

@@ -33,7 +33,8 @@ DecodingReturnValues ASMC::decodeAllInJob()
 }
 
 void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
-                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs)
+                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
+                       bool minPosteriorMeans, bool minMAPs)
 {
   if (hapIndicesA.empty() || hapIndicesA.size() != hapIndicesB.size()) {
     throw std::runtime_error("Vector of A indices (" + std::to_string(hapIndicesA.size()) +
@@ -42,18 +43,21 @@ void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std:
   }
   mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA, hapIndicesB, mHmm.getData().sites,
                                                mHmm.getDecodingQuantities().states, perPairPosteriors, sumOfPosteriors,
-                                               perPairPosteriorMeans, perPairMAPs);
+                                               perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs);
   mHmm.setStorePerPairPosteriorMean(perPairPosteriorMeans);
   mHmm.setStorePerPairMap(perPairMAPs);
   mHmm.setStorePerPairPosterior(perPairPosteriors);
   mHmm.setStoreSumOfPosterior(sumOfPosteriors);
+  mHmm.setStoreMinPosteriorMean(minPosteriorMeans);
+  mHmm.setStoreMinMap(minMAPs);
   mHmm.decodeHapPairs(hapIndicesA, hapIndicesB);
   mHmm.finishDecoding();
   mHmm.getDecodePairsReturnStruct().finaliseCalculations();
 }
 
 void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
-                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs)
+                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
+                       bool minPosteriorMeans, bool minMAPs)
 {
   if (hapIdsA.size() != hapIdsB.size()) {
     throw std::runtime_error("Vector of A IDs (" + std::to_string(hapIdsA.size()) +
@@ -67,7 +71,7 @@ void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vecto
     a[i] = dipToHapId(getIndIdxFromIdString(ids, strA), hapA);
     b[i] = dipToHapId(getIndIdxFromIdString(ids, strB), hapB);
   }
-  decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs);
+  decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs);
 }
 
 FastSMC::FastSMC(DecodingParams params) : mParams(withDeviceStarting(std::move(params))), mHmm(Data(mParams), mParams) {}

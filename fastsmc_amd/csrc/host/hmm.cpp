@@ -111,7 +111,7 @@ unsigned long getIndIdxFromIdString(const std::vector<std::string>& ids, const s
 
 void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>&,
                                          long sites, long states, bool fullPosteriors, bool sumOfPost,
-                                         bool perPairMeans, bool perPairMaps)
+                                         bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps)
 {
   numWritten = 0;
   numPairs = static_cast<long>(hapsA.size());
@@ -121,6 +121,8 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
   storeSumOfPosteriors = sumOfPost;
   storePerPairPosteriorMeans = perPairMeans;
   storePerPairMAPs = perPairMaps;
+  storeMinPosteriorMeans = minMeans;
+  storeMinMAPs = minMaps;
   perPairIndices.assign(static_cast<size_t>(numPairs), {});
   perPairPosteriors.clear();
   sumOfPosteriors.clear();
@@ -143,6 +145,15 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
   }
   if (perPairMaps) {
     perPairMAPs.assign(static_cast<size_t>(numPairs * sites), 0);
+    minMAPs.assign(static_cast<size_t>(sites), 0);
+    argminMAPs.assign(static_cast<size_t>(sites), 0);
+  }
+  // the minima alone: the four [sites] vectors without the [pairs][sites] matrices
+  if (minMeans && !perPairMeans) {
+    minPosteriorMeans.assign(static_cast<size_t>(sites), 0.f);
+    argminPosteriorMeans.assign(static_cast<size_t>(sites), 0);
+  }
+  if (minMaps && !perPairMaps) {
     minMAPs.assign(static_cast<size_t>(sites), 0);
     argminMAPs.assign(static_cast<size_t>(sites), 0);
   }
@@ -224,6 +235,12 @@ void HMM::init(int scalingSkip)
   mBatchSize = mParams.batchSize;
   if (mBatchSize <= 0) {
     throw std::runtime_error("batchSize must be positive");
+  }
+  if (const char* v = std::getenv("FSMC_DIAG_FLUSH_PAIRS")) { // tests: several flushes of one call on a small list
+    const long n = std::atol(v);
+    if (n >= 1 && static_cast<size_t>(n) < mFlushThreshold) {
+      mFlushThreshold = static_cast<size_t>(n);
+    }
   }
   mFromBatch.assign(static_cast<size_t>(mBatchSize), 0u);
   mToBatch.assign(static_cast<size_t>(mBatchSize), static_cast<unsigned>(mData.sites));
@@ -608,6 +625,20 @@ void HMM::setStoreSumOfPosterior(bool v)
   updateOutputStructures();
 }
 
+void HMM::setStoreMinPosteriorMean(bool v)
+{
+  flush(); // (what is queued was decoded under the old setting)
+  mStoreMinMean = v;
+  updateOutputStructures();
+}
+
+void HMM::setStoreMinMap(bool v)
+{
+  flush(); // (what is queued was decoded under the old setting)
+  mStoreMinMap = v;
+  updateOutputStructures();
+}
+
 void HMM::setWritePerPairPosteriorMean(bool v)
 {
   flush(); // (what is queued was decoded under the old setting in the reference)
@@ -938,7 +969,10 @@ void HMM::flush()
           "fsmc_decode_sums_batches");
   }
   const bool writeFiles = mMeanFile || mMapFile;
-  const bool storeAny = mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior;
+  // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
+  const bool minMeanOnDevice = mStoreMinMean && !mStoreMean, minMapOnDevice = mStoreMinMap && !mStoreMap;
+  const bool storeAny =
+      mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice || minMapOnDevice;
   if (!mParams.FastSMC && (storeAny || writeFiles)) {
     // writePerPairOutput (HMM.cpp:1360-1458)
     const size_t S = static_cast<size_t>(mData.sites);
@@ -950,10 +984,27 @@ void HMM::flush()
     const bool wantMean = mStoreMean || mStorePosterior || mStoreSumOfPosterior || mMeanFile;
     std::vector<float> mean(wantMean ? nPairs * S : 0);
     std::vector<int32_t> map(mStoreMap || mStoreMean || mMapFile ? nPairs * S : 0);
-    check(mCtx,
-          fsmc_decode_per_pair(mCtx, mModel, mExpectedCoalTimes.data(), mean.empty() ? nullptr : mean.data(),
-                               map.empty() ? nullptr : map.data()),
-          "fsmc_decode_per_pair");
+    if (!mean.empty() || !map.empty()) {
+      check(mCtx,
+            fsmc_decode_per_pair(mCtx, mModel, mExpectedCoalTimes.data(), mean.empty() ? nullptr : mean.data(),
+                                 map.empty() ? nullptr : map.data()),
+            "fsmc_decode_per_pair");
+    }
+    if (minMeanOnDevice || minMapOnDevice) {
+      // the chain of finaliseCalculations over all pairs of the call, flush after flush: 4 * S bytes per output cross
+      // the bus, the rows stay on the device
+      if ((minMeanOnDevice && R.minPosteriorMeans.size() != S) || (minMapOnDevice && R.minMAPs.size() != S)) {
+        throw std::runtime_error("the return structure was not initialised for the minima asked for");
+      }
+      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
+      check(mCtx,
+            fsmc_decode_pair_minima(mCtx, mModel, mExpectedCoalTimes.data(), static_cast<uint64_t>(base),
+                                    minMeanOnDevice ? R.minPosteriorMeans.data() : nullptr,
+                                    minMeanOnDevice ? R.argminPosteriorMeans.data() : nullptr,
+                                    minMapOnDevice ? R.minMAPs.data() : nullptr,
+                                    minMapOnDevice ? R.argminMAPs.data() : nullptr),
+            "fsmc_decode_pair_minima");
+    }
     if (mStorePosterior || mStoreSumOfPosterior) {
       // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]
       // table and continues the sum over pairs in pair order -- nothing but those tables crosses the bus

@@ -51,10 +51,13 @@ struct DecodePairsReturnStruct {
   long numPairs = 0, numSites = 0, numStates = 0;
   bool storeFullPosteriors = false, storeSumOfPosteriors = false, storePerPairPosteriorMeans = false,
        storePerPairMAPs = false;
+  // the four [sites] minima without the [pairs][sites] matrices (computed on the device, fsmc_decode_pair_minima)
+  bool storeMinPosteriorMeans = false, storeMinMAPs = false;
   size_t numWritten = 0;
 
   void initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>& hapsB, long sites,
-                  long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps);
+                  long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps,
+                  bool minMeans = false, bool minMaps = false);
   void finaliseCalculations();
 };
 
@@ -132,6 +135,10 @@ public:
   void setStorePerPairMap(bool v);
   void setStorePerPairPosterior(bool v);
   void setStoreSumOfPosterior(bool v);
+  // per site the smallest posterior mean / MAP over the decoded pairs and the first pair that has it, into the return
+  // structure's min / argmin vectors; where the rows themselves are stored as well, finaliseCalculations makes them
+  void setStoreMinPosteriorMean(bool v);
+  void setStoreMinMap(bool v);
   // HMM.hpp:287,293: per-pair posterior means / MAP states of every decoded pair as text, one row per pair, to
   // <outFileRoot>.perPairPosteriorMeans.gz / .perPairMAP.gz (ASMC mode; opened by resetDecoding, HMM.cpp:259-271,
   // written batch by batch, HMM.cpp:1412-1420, closed by finishDecoding, HMM.cpp:515-524)
@@ -227,6 +234,7 @@ private:
   DecodingReturnValues mReturn;
   DecodePairsReturnStruct mPairsReturn;
   bool mStoreMean = false, mStoreMap = false, mStorePosterior = false, mStoreSumOfPosterior = false;
+  bool mStoreMinMean = false, mStoreMinMap = false;
   bool mWriteMean = false, mWriteMap = false;
   gzFile mMeanFile = nullptr, mMapFile = nullptr;
   int mMeanFd = -1, mMapFd = -1; // their descriptors (blocks of rows go out as gzip members of their own)

@@ -380,6 +380,12 @@ PYBIND11_MODULE(_pyasmc, m)
            "ASMC mode: write <outFileRoot>.perPairMAP.gz, one row per decoded pair (HMM.hpp:293, HMM.cpp:1417-1420)")
       .def("setStorePerPairPosteriorMean", &HMM::setStorePerPairPosteriorMean, "storePerPairPosteriorMean"_a = true)
       .def("setStorePerPairMap", &HMM::setStorePerPairMap, "storePerPairMAP"_a = true)
+      .def("setStoreMinPosteriorMean", &HMM::setStoreMinPosteriorMean, "storeMinPosteriorMean"_a = true,
+           "per site the smallest posterior mean over the decoded pairs and the first pair that has it, computed on "
+           "the device where the per-pair rows are not stored")
+      .def("setStoreMinMap", &HMM::setStoreMinMap, "storeMinMAP"_a = true,
+           "per site the smallest MAP state over the decoded pairs and the first pair that has it, computed on the "
+           "device where the per-pair rows are not stored")
       .def("getExpectedCoalTimes", &HMM::getExpectedCoalTimes,
            "expected coalescence times the per-pair posterior means use: the intervals file's second column when "
            "DecodingParams.expectedCoalTimesFile names one, else the decoding quantities' (HMM.cpp:1736-1748)")
@@ -519,14 +525,16 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("decodeAllInJob", &ASMC::decodeAllInJob)
       .def("decodePairs",
            py::overload_cast<const std::vector<unsigned long>&, const std::vector<unsigned long>&, bool, bool, bool,
-                             bool>(&ASMC::decodePairs),
+                             bool, bool, bool>(&ASMC::decodePairs),
            "hap_indices_a"_a, "hap_indices_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
-           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false)
+           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
+           "min_MAPs"_a = false)
       .def("decodePairs",
-           py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool>(
-               &ASMC::decodePairs),
+           py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool,
+                             bool, bool>(&ASMC::decodePairs),
            "hap_ids_a"_a, "hap_ids_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
-           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false)
+           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
+           "min_MAPs"_a = false)
       .def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

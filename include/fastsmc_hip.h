@@ -19,6 +19,9 @@
  *   fsmc_decode_pair_posteriors <- decodeBatch + the perPairPosteriors / sumOfPosteriors part of
  *                             writePerPairOutput, the tables ASMC::decodePairs hands out
  *                                                                    (HMM.cpp:1378-1392, ASMC.cpp:80-128)
+ *   fsmc_decode_pair_minima <- decodeBatch + writePerPairOutput + the column-wise min / argmin of
+ *                             DecodePairsReturnStruct::finaliseCalculations
+ *                                                  (HMM.cpp:1360-1458, DecodePairsReturnStruct.hpp:105-118)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -190,6 +193,11 @@ int fsmc_ctx_last_segment_sums_in_lds(const fsmc_ctx* ctx, int32_t* in_lds);
  * Results do not depend on it.  fsmc_ctx_last_pair_posterior_slices: slices of the last such call. */
 int fsmc_ctx_set_pair_posterior_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_minima: groups whose mean / MAP rows the device holds at a time.  0 (default) =
+ * automatic: as many groups as a quarter of the card (or the workspace limit) and half its free memory hold of rows
+ * (64 * S * 4 bytes a group and output).  Results do not depend on it. */
+int fsmc_ctx_set_pair_minima_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -306,6 +314,24 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
  * (from = 0, to = S; FSMC_EINVAL otherwise), as in the reference. */
 int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times,
                                 float* const* post_rows, float* sum);
+
+/* Per site, the smallest posterior mean / MAP state over the pairs of the resident work list and which pair has it:
+ * what DecodePairsReturnStruct::finaliseCalculations computes from the [pairs][sites] matrices of writePerPairOutput
+ * (DecodePairsReturnStruct.hpp:105-118), without those matrices leaving the device.  Exactly that loop in work-list
+ * order: pair 0 seeds (best, arg); pair i replaces them only when v_i < best (a strict fp32 / int32 compare: ties keep
+ * the earlier pair, -0.f does not beat +0.f, a NaN never replaces anything and a NaN seed stays); arg = pair_base + i.
+ *   min_mean / argmin_mean: [S] each, both or neither; min_map / argmin_map: [S] each, both or neither; at least one
+ *   pair of outputs.
+ *   pair_base == 0: the first pair of the work list is the seed, what the arrays hold is ignored.
+ *   pair_base  > 0: the arrays are the state of a chain that earlier calls began (over pairs 0 .. pair_base - 1 of a
+ *                   longer list) and this call continues: a carried value that ties with a new one stays.  Several
+ *                   calls over consecutive parts of a list give the bits of one call over the whole list.
+ * The work list goes through the device in slices of groups (fsmc_ctx_set_pair_minima_slice); 4 * S bytes per output
+ * cross the bus each way (in: only when pair_base > 0).  fsmc_last_kernel_ms spans every decode and every reduction of
+ * the call.  FSMC_EINVAL: no output pair or half of one; a group that is not the whole sequence (from = 0, to = S), as
+ * in the reference; pair_base + n_pairs beyond INT32_MAX. */
+int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, uint64_t pair_base,
+                            float* min_mean, int32_t* argmin_mean, int32_t* min_map, int32_t* argmin_map);
 
 /* augmentSumOverPairs: sums[S][K] += sum over the pairs of the work list of the posterior
  * (and the 00/01/11 split when the pointers are non-NULL).  Whole-sequence groups only. */
