@@ -15,7 +15,7 @@ from ._pyasmc import (ASMC, BinaryDataReader, Data, DecodePairsReturnStruct, Dec
 __all__ = ["ASMC", "BinaryDataReader", "IbdPairDataLine", "Data", "DecodePairsReturnStruct", "DecodingMode", "DecodingModeOverall", "DecodingParams",
            "DecodingQuantities", "DecodingReturnValues", "FastSMC", "HMM", "Individual", "PairObservations", "Match", "cmBetween",
            "hashingCandidates", "hashingCandidatesDevice", "hashingWords",
-           "decoding_quantities_from_tables", "PreparedModelView"]
+           "decoding_quantities_from_tables", "PreparedModelView", "site_bins"]
 
 
 def decoding_quantities_from_tables(t) -> DecodingQuantities:
@@ -33,3 +33,24 @@ class PreparedModelView:
     def __init__(self, d: dict):
         self.__dict__.update(d)
         self.probability_threshold = np.float32(d["probability_threshold"])
+
+
+def site_bins(positions, width) -> np.ndarray:
+    """Bin edges for ``ASMC.decodePairs(..., site_bins=...)`` that cut the sites into windows of ``width``: ``positions``
+    are the sites' coordinates in ascending order (cM or bp, any unit ``width`` is in), window ``w`` is
+    ``[positions[0] + w * width, positions[0] + (w + 1) * width)``.  Returns int32 edges ``e`` with ``e[0] = 0`` and
+    ``e[-1] = len(positions)``; bin ``b`` is sites ``[e[b], e[b + 1])``.  Windows that hold no site are dropped, so the
+    edges are strictly ascending (a bin is then one window, never several)."""
+    pos = np.asarray(positions, np.float64).reshape(-1)
+    if pos.size == 0:
+        raise ValueError("site_bins: no positions")
+    if not np.isfinite(pos).all() or (np.diff(pos) < 0).any():
+        raise ValueError("site_bins: positions must be finite and ascending")
+    width = float(width)
+    if not width > 0 or not np.isfinite(width):
+        raise ValueError("site_bins: width must be positive")
+    n_windows = int(np.floor((pos[-1] - pos[0]) / width)) + 1
+    bounds = pos[0] + width * np.arange(n_windows + 1, dtype=np.float64)
+    edges = np.searchsorted(pos, bounds, side="left")
+    edges[0], edges[-1] = 0, pos.size  # (the last bound lies beyond the last site)
+    return np.unique(edges).astype(np.int32)

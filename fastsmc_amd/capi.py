@@ -36,6 +36,7 @@ SYMBOLS = [
     "fsmc_decode_posteriors", "fsmc_decode_per_pair", "fsmc_decode_sums", "fsmc_decode_sums_batches",
     "fsmc_decode_pair_posteriors", "fsmc_ctx_set_pair_posterior_slice", "fsmc_ctx_last_pair_posterior_slices",
     "fsmc_decode_pair_minima", "fsmc_ctx_set_pair_minima_slice", "fsmc_ctx_last_pair_minima_slices",
+    "fsmc_decode_pair_bins", "fsmc_ctx_set_pair_bins_slice", "fsmc_ctx_last_pair_bins_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -127,6 +128,9 @@ def load():
         L.fsmc_decode_pair_minima.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
         L.fsmc_ctx_set_pair_minima_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_minima_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_bins.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+        L.fsmc_ctx_set_pair_bins_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_bins_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -416,6 +420,46 @@ class Context:
     def last_pair_minima_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_minima_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_bins(self, model: "Model", exp_coal_times, bin_edges, want_mean=True, want_min_mean=True,
+                         want_min_map=True, out=None):
+        """Per pair of the resident work list, summaries of its posterior-mean / MAP row over the bins of sites
+        [bin_edges[b], bin_edges[b + 1]) (fsmc_decode_pair_bins): (bin_mean f32, bin_min_mean f32, bin_argmin_mean i32,
+        bin_min_map i32, bin_argmin_map i32), each [n_pairs][B], None for an output that was not asked for; an argmin is
+        an absolute site index.  ``out``: five such arrays (None where not wanted, at least n_pairs rows), written in
+        place and returned as they are -- the ``want_*`` switches are ignored then."""
+        et = np.ascontiguousarray(exp_coal_times, np.float32)
+        if et.shape != (model.K,):
+            raise ValueError(f"exp_coal_times: shape {et.shape}, expected {(model.K,)}")
+        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
+        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
+        if edges is not None and edges.size == 0:
+            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        n = self._n_pairs
+        dtypes = (np.float32, np.float32, np.int32, np.int32, np.int32)
+        if out is None:
+            wants = (want_mean, want_min_mean, want_min_mean, want_min_map, want_min_map)
+            out = tuple(np.zeros((n, n_bins), dt) if w else None for w, dt in zip(wants, dtypes))
+        out = tuple(out)
+        if len(out) != 5:
+            raise ValueError("out: (bin_mean, bin_min_mean, bin_argmin_mean, bin_min_map, bin_argmin_map)")
+        for a, dt in zip(out, dtypes):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 2
+                                  or a.shape[0] < n or a.shape[1] != n_bins):
+                raise ValueError("out: writable C-contiguous arrays [>= n_pairs][B], float32 for bin_mean and "
+                                 "bin_min_mean, int32 for the others")
+        self._check(self._L.fsmc_decode_pair_bins(self._h, model._h, _p(et), _p(edges), n_bins, *[_p(a) for a in out]))
+        return out
+
+    def set_pair_bins_slice(self, groups: int):
+        """Groups fsmc_decode_pair_bins puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_bins_slice(self._h, groups))
+
+    def last_pair_bins_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_bins_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):

@@ -19,6 +19,7 @@
 
 #include "fsmc_identify.h"
 #include "fsmc_instances.h"
+#include "fsmc_pair_bins.h"
 #include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
 
@@ -142,6 +143,11 @@ struct fsmc_ctx {
   uint32_t pmSlice = 0;     // groups a slice, 0 = automatic
   int lastPmSlices = 0;     // slices of the last call
   DevBuf pmAcc;             // [expCoal KP floats][the carried state, 4 x S][the ranges' partials, 4 x nRanges x S]
+
+  // fsmc_decode_pair_bins: slices of groups as above, the rows in ppStage
+  uint32_t pbSlice = 0;     // groups a slice, 0 = automatic
+  int lastPbSlices = 0;     // slices of the last call
+  DevBuf pbAcc;             // [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -1146,6 +1152,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->ppRows.p) (void)hipFree(ctx->ppRows.p);
   if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
+  if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
   for (int i = 0; i < 2; ++i) {
     if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
     if (ctx->evCopied[i]) (void)hipEventDestroy(ctx->evCopied[i]);
@@ -1294,6 +1301,24 @@ int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices)
     return FSMC_EINVAL;
   }
   *slices = ctx->lastPmSlices;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_pair_bins_slice(fsmc_ctx* ctx, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->pbSlice = groups;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->lastPbSlices;
   return FSMC_OK;
 }
 
@@ -2543,6 +2568,158 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
     }
   }
   ctx->lastPmSlices = (int)nSlices;
+  return FSMC_OK;
+}
+
+// Per pair, the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over bins of sites,
+// without the rows leaving the device: the per-pair consumers decode a slice of groups into ppStage exactly as for
+// fsmc_decode_pair_minima (the staging pointers moved back by the slice's first pair), pair_bins_kernel reduces the
+// slice's rows cell by cell (fsmc_pair_bins.h), and the slice's [pairs][B] outputs are copied to the caller's arrays at
+// the slice's first pair.  Slices are independent: nothing is carried.
+int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, const int32_t* bin_edges,
+                          size_t n_bins, float* bin_mean, float* bin_min_mean, int32_t* bin_argmin_mean,
+                          int32_t* bin_min_map, int32_t* bin_argmin_map)
+{
+  int rc = checkReady(ctx, m);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  const bool wantMean = bin_mean || bin_min_mean || bin_argmin_mean, wantMap = bin_min_map || bin_argmin_map;
+  if (!exp_coal_times || !bin_edges || (!wantMean && !wantMap)) {
+    return fail(ctx, FSMC_EINVAL, "need expected coalescence times, bin edges and at least one output");
+  }
+  if ((bin_min_mean != nullptr) != (bin_argmin_mean != nullptr) || (bin_min_map != nullptr) != (bin_argmin_map != nullptr)) {
+    return fail(ctx, FSMC_EINVAL, "a minimum and its argmin come together");
+  }
+  if (n_bins == 0) {
+    return fail(ctx, FSMC_EINVAL, "need one bin at least (n_bins + 1 edges)");
+  }
+  if (n_bins > (size_t)m->S) {
+    return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending: more bins than sites");
+  }
+  if (bin_edges[0] < 0 || bin_edges[n_bins] > m->S) {
+    return fail(ctx, FSMC_EINVAL, "bin edges must lie in [0, sites]");
+  }
+  for (size_t b = 0; b < n_bins; ++b) {
+    if (bin_edges[b] >= bin_edges[b + 1]) {
+      return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending");
+    }
+  }
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "per-pair bins need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t S = (size_t)m->S, B = n_bins;
+  const int nRows = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
+  void* const hOut[5] = {bin_mean, bin_min_mean, bin_argmin_mean, bin_min_map, bin_argmin_map};
+  size_t nOut = 0;
+  for (void* o : hOut) {
+    nOut += o ? 1 : 0;
+  }
+  // a full group's rows in the staging buffer and its cells in the output buffer
+  const size_t groupBytes = (size_t)kWave * sizeof(float) * (S * (size_t)nRows + B * nOut);
+
+  // The slice: what stagingLimit holds of rows and outputs, of half the room the card has free -- the decode's
+  // workspace is allocated after this.
+  size_t slice = ctx->pbSlice;
+  if (slice == 0) {
+    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->pbAcc.bytes, 2) / groupBytes);
+  }
+  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
+  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
+
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
+  LaunchPlan plan;
+  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, first, slice, 0, plan);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  auto pairsOfSlice = [&](size_t g0) {
+    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
+    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
+  };
+  size_t slicePairsMax = 0;
+  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
+    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
+  }
+  if (slicePairsMax > (size_t)INT32_MAX) {
+    return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_bins_slice)");
+  }
+
+  const size_t coalBytes = (size_t)m->KP * sizeof(float);
+  const size_t edgeBytes = (B + 1) * sizeof(int32_t);
+  const size_t outBytes = slicePairsMax * B * sizeof(float); // one output of the largest slice
+  rc = ensure(ctx, ctx->ppStage, slicePairsMax * S * sizeof(float) * (size_t)nRows);
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pbAcc, coalBytes + edgeBytes + nOut * outBytes);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  char* const acc = (char*)ctx->pbAcc.p;
+  std::vector<float> coal((size_t)m->KP, 0.f);
+  std::memcpy(coal.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
+  FSMC_HIP(ctx, hipMemcpyAsync(acc, coal.data(), coalBytes, hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(acc + coalBytes, bin_edges, edgeBytes, hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (coal is a local, the edges the caller's)
+
+  float* const stageMean = wantMean ? (float*)ctx->ppStage.p : nullptr;
+  int* const stageMap = wantMap ? (int*)ctx->ppStage.p + (wantMean ? slicePairsMax * S : 0) : nullptr;
+  void* dOut[5];
+  {
+    char* next = acc + coalBytes + edgeBytes;
+    for (int i = 0; i < 5; ++i) {
+      dOut[i] = hOut[i] ? next : nullptr;
+      next += hOut[i] ? outBytes : 0;
+    }
+  }
+  KParams p;
+  fillParams(ctx, m, plan, 0, p);
+  p.expCoal = (const float*)acc;
+  PairBinsParams q;
+  q.mean = stageMean;
+  q.map = stageMap;
+  q.edges = (const int*)(acc + coalBytes);
+  q.S = m->S;
+  q.B = (int)B;
+  q.binMean = (float*)dOut[0];
+  q.binMinMean = (float*)dOut[1];
+  q.binArgMean = (int*)dOut[2];
+  q.binMinMap = (int*)dOut[3];
+  q.binArgMap = (int*)dOut[4];
+  // waves of the reduction: one per cell, no more than fill the chip eight deep
+  const size_t wavesPerBlock = kPairBinsThreads / kWave;
+  const size_t blocksMax = (size_t)8 * (size_t)std::max(ctx->nCU, 1);
+
+  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
+    const size_t nG = std::min(slice, ctx->nGroups - g0);
+    const size_t firstPair = ctx->hGroups[g0].first_pair;
+    const size_t n = pairsOfSlice(g0);
+    p.groups = ctx->dGroups + g0;
+    p.nGroups = (int)nG;
+    // (row `pair` of the work list is row `pair - firstPair` of the staging buffer)
+    p.ppMean = stageMean ? stageMean - firstPair * S : nullptr;
+    p.ppMap = stageMap ? stageMap - firstPair * S : nullptr;
+    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+    q.n = (int)n;
+    const size_t blocks = std::min(blocksMax, (n * B + wavesPerBlock - 1) / wavesPerBlock);
+    hipLaunchKernelGGL(pair_bins_kernel, dim3((unsigned)blocks), dim3(kPairBinsThreads), 0, ctx->stream, q);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
+    // the slice's outputs go to the caller before the next slice overwrites them (20 bytes a cell at most against the
+    // 552 bytes a pair-site of the decode: no second buffer, no overlap)
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 5; ++i) {
+      if (hOut[i]) {
+        FSMC_HIP(ctx, hipMemcpy((char*)hOut[i] + firstPair * B * sizeof(float), dOut[i], n * B * sizeof(float),
+                                hipMemcpyDeviceToHost));
+      }
+    }
+  }
+  ctx->lastPbSlices = (int)nSlices;
   return FSMC_OK;
 }
 

@@ -34,16 +34,18 @@ DecodingReturnValues ASMC::decodeAllInJob()
 
 void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs)
+                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins)
 {
   if (hapIndicesA.empty() || hapIndicesA.size() != hapIndicesB.size()) {
     throw std::runtime_error("Vector of A indices (" + std::to_string(hapIndicesA.size()) +
                              ") must be the same size as vector of B indices (" +
                              std::to_string(hapIndicesB.size()) + ").\n");
   }
+  mHmm.setSiteBins(siteBins); // (first: edges it refuses leave the last call's results as they are)
   mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA, hapIndicesB, mHmm.getData().sites,
                                                mHmm.getDecodingQuantities().states, perPairPosteriors, sumOfPosteriors,
-                                               perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs);
+                                               perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
+                                               siteBins);
   mHmm.setStorePerPairPosteriorMean(perPairPosteriorMeans);
   mHmm.setStorePerPairMap(perPairMAPs);
   mHmm.setStorePerPairPosterior(perPairPosteriors);
@@ -57,7 +59,7 @@ void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std:
 
 void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs)
+                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins)
 {
   if (hapIdsA.size() != hapIdsB.size()) {
     throw std::runtime_error("Vector of A IDs (" + std::to_string(hapIdsA.size()) +
@@ -71,7 +73,8 @@ void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vecto
     a[i] = dipToHapId(getIndIdxFromIdString(ids, strA), hapA);
     b[i] = dipToHapId(getIndIdxFromIdString(ids, strB), hapB);
   }
-  decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs);
+  decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
+              siteBins);
 }
 
 FastSMC::FastSMC(DecodingParams params) : mParams(withDeviceStarting(std::move(params))), mHmm(Data(mParams), mParams) {}

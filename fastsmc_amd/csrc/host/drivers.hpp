@@ -20,12 +20,13 @@ public:
   DecodingReturnValues decodeAllInJob(); // ASMC.cpp:51-78
   void decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
                    bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
-                   bool perPairMAPs = false, bool minPosteriorMeans = false,
-                   bool minMAPs = false); // ASMC.cpp:80-100; the last two: the minima without the rows
+                   bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
+                   const std::vector<int>& siteBins = {}); // ASMC.cpp:80-100; minima: without the rows; siteBins: edges
+                                                           // of the per-pair summaries over bins of sites, {} = none
   void decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
                    bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
-                   bool perPairMAPs = false, bool minPosteriorMeans = false,
-                   bool minMAPs = false); // ASMC.cpp:102-128
+                   bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
+                   const std::vector<int>& siteBins = {}); // ASMC.cpp:102-128
   DecodePairsReturnStruct getCopyOfResults() { return mHmm.getDecodePairsReturnStruct(); }
   const DecodePairsReturnStruct& getRefOfResults() { return mHmm.getDecodePairsReturnStruct(); }
   HMM& hmm() { return mHmm; }

@@ -111,7 +111,8 @@ unsigned long getIndIdxFromIdString(const std::vector<std::string>& ids, const s
 
 void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>&,
                                          long sites, long states, bool fullPosteriors, bool sumOfPost,
-                                         bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps)
+                                         bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps,
+                                         const std::vector<int>& siteBins)
 {
   numWritten = 0;
   numPairs = static_cast<long>(hapsA.size());
@@ -157,6 +158,14 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
     minMAPs.assign(static_cast<size_t>(sites), 0);
     argminMAPs.assign(static_cast<size_t>(sites), 0);
   }
+  // the per-pair summaries over bins of sites: [pairs][bins]
+  binEdges = siteBins;
+  const size_t cells = siteBins.size() < 2 ? 0 : static_cast<size_t>(numPairs) * (siteBins.size() - 1);
+  binMeanPosteriorMeans.assign(cells, 0.f);
+  binMinPosteriorMeans.assign(cells, 0.f);
+  binArgminPosteriorMeans.assign(cells, 0);
+  binMinMAPs.assign(cells, 0);
+  binArgminMAPs.assign(cells, 0);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()
@@ -639,6 +648,26 @@ void HMM::setStoreMinMap(bool v)
   updateOutputStructures();
 }
 
+void HMM::setSiteBins(const std::vector<int>& edges)
+{
+  if (!edges.empty()) { // (the messages of fsmc_decode_pair_bins)
+    if (edges.size() < 2) {
+      throw std::runtime_error("need one bin at least (n_bins + 1 edges)");
+    }
+    if (edges.front() < 0 || static_cast<long>(edges.back()) > static_cast<long>(mData.sites)) {
+      throw std::runtime_error("bin edges must lie in [0, sites]");
+    }
+    for (size_t b = 0; b + 1 < edges.size(); ++b) {
+      if (edges[b] >= edges[b + 1]) {
+        throw std::runtime_error("bin edges must be strictly ascending");
+      }
+    }
+  }
+  flush(); // (what is queued was decoded under the old setting)
+  mSiteBins = edges;
+  updateOutputStructures();
+}
+
 void HMM::setWritePerPairPosteriorMean(bool v)
 {
   flush(); // (what is queued was decoded under the old setting in the reference)
@@ -971,8 +1000,9 @@ void HMM::flush()
   const bool writeFiles = mMeanFile || mMapFile;
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
   const bool minMeanOnDevice = mStoreMinMean && !mStoreMean, minMapOnDevice = mStoreMinMap && !mStoreMap;
-  const bool storeAny =
-      mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice || minMapOnDevice;
+  const bool binsOnDevice = !mSiteBins.empty();
+  const bool storeAny = mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice ||
+                        minMapOnDevice || binsOnDevice;
   if (!mParams.FastSMC && (storeAny || writeFiles)) {
     // writePerPairOutput (HMM.cpp:1360-1458)
     const size_t S = static_cast<size_t>(mData.sites);
@@ -1004,6 +1034,22 @@ void HMM::flush()
                                     minMapOnDevice ? R.minMAPs.data() : nullptr,
                                     minMapOnDevice ? R.argminMAPs.data() : nullptr),
             "fsmc_decode_pair_minima");
+    }
+    if (binsOnDevice) {
+      // per pair the summaries over the bins, flush after flush at the pairs written so far: 20 bytes a pair and bin
+      // cross the bus, the rows stay on the device (where the rows are stored as well, this decodes the flush again)
+      const size_t nBins = mSiteBins.size() - 1;
+      if (R.binEdges != mSiteBins || R.binMeanPosteriorMeans.size() != static_cast<size_t>(R.numPairs) * nBins) {
+        throw std::runtime_error("the return structure was not initialised for the site bins asked for");
+      }
+      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
+      const size_t at = base * nBins;
+      check(mCtx,
+            fsmc_decode_pair_bins(mCtx, mModel, mExpectedCoalTimes.data(), mSiteBins.data(), nBins,
+                                  R.binMeanPosteriorMeans.data() + at, R.binMinPosteriorMeans.data() + at,
+                                  R.binArgminPosteriorMeans.data() + at, R.binMinMAPs.data() + at,
+                                  R.binArgminMAPs.data() + at),
+            "fsmc_decode_pair_bins");
     }
     if (mStorePosterior || mStoreSumOfPosterior) {
       // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]

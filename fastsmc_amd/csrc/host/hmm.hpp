@@ -53,11 +53,16 @@ struct DecodePairsReturnStruct {
        storePerPairMAPs = false;
   // the four [sites] minima without the [pairs][sites] matrices (computed on the device, fsmc_decode_pair_minima)
   bool storeMinPosteriorMeans = false, storeMinMAPs = false;
+  // per pair, summaries of the mean / MAP rows over bins of sites (computed on the device, fsmc_decode_pair_bins): bin b
+  // is sites [binEdges[b], binEdges[b + 1]); the five matrices are [pairs][bins], empty without bins
+  std::vector<int> binEdges;
+  std::vector<float> binMeanPosteriorMeans, binMinPosteriorMeans;
+  std::vector<int> binArgminPosteriorMeans, binMinMAPs, binArgminMAPs;
   size_t numWritten = 0;
 
   void initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>& hapsB, long sites,
                   long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps,
-                  bool minMeans = false, bool minMaps = false);
+                  bool minMeans = false, bool minMaps = false, const std::vector<int>& siteBins = {});
   void finaliseCalculations();
 };
 
@@ -139,6 +144,10 @@ public:
   // structure's min / argmin vectors; where the rows themselves are stored as well, finaliseCalculations makes them
   void setStoreMinPosteriorMean(bool v);
   void setStoreMinMap(bool v);
+  // per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins of sites
+  // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
+  // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
+  void setSiteBins(const std::vector<int>& edges);
   // HMM.hpp:287,293: per-pair posterior means / MAP states of every decoded pair as text, one row per pair, to
   // <outFileRoot>.perPairPosteriorMeans.gz / .perPairMAP.gz (ASMC mode; opened by resetDecoding, HMM.cpp:259-271,
   // written batch by batch, HMM.cpp:1412-1420, closed by finishDecoding, HMM.cpp:515-524)
@@ -235,6 +244,7 @@ private:
   DecodePairsReturnStruct mPairsReturn;
   bool mStoreMean = false, mStoreMap = false, mStorePosterior = false, mStoreSumOfPosterior = false;
   bool mStoreMinMean = false, mStoreMinMap = false;
+  std::vector<int> mSiteBins; // bin edges of the per-pair summaries, empty = none
   bool mWriteMean = false, mWriteMap = false;
   gzFile mMeanFile = nullptr, mMapFile = nullptr;
   int mMeanFd = -1, mMapFd = -1; // their descriptors (blocks of rows go out as gzip members of their own)

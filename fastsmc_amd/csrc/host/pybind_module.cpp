@@ -84,6 +84,16 @@ namespace fsmc_host
 void bindContainers(py::module_& m); // pybind_containers.cpp: VectorBool ... UMapIntToVectorFloat (pybind.cpp:63-70)
 }
 
+// a [pairs][bins] matrix of the return structure's site-bin summaries ([0][0] without bins)
+template <typename T>
+py::array_t<T> binMatrix(const std::vector<T>& v, const DecodePairsReturnStruct& r)
+{
+  if (v.empty()) {
+    return py::array_t<T>(std::vector<py::ssize_t>{0, 0});
+  }
+  return toArray<T>(v, {static_cast<py::ssize_t>(r.numPairs), static_cast<py::ssize_t>(r.binEdges.size() - 1)});
+}
+
 PYBIND11_MODULE(_pyasmc, m)
 {
   m.doc() = "MI355X-native drop-in for the decode path of PalamaraLab/FastSMC (pyASMC-compatible names)";
@@ -128,7 +138,14 @@ PYBIND11_MODULE(_pyasmc, m)
                                return toArray<int>(r.perPairMAPs, {r.numPairs, r.numSites});
                              })
       .def_property_readonly("min_MAPs", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.minMAPs, {static_cast<py::ssize_t>(r.minMAPs.size())}); })
-      .def_property_readonly("argmin_MAPs", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.argminMAPs, {static_cast<py::ssize_t>(r.argminMAPs.size())}); });
+      .def_property_readonly("argmin_MAPs", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.argminMAPs, {static_cast<py::ssize_t>(r.argminMAPs.size())}); })
+      // per pair, summaries over the bins of sites [bin_edges[b], bin_edges[b + 1]): [pairs][bins], empty without bins
+      .def_property_readonly("bin_edges", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.binEdges, {static_cast<py::ssize_t>(r.binEdges.size())}); })
+      .def_property_readonly("bin_mean_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<float>(r.binMeanPosteriorMeans, r); })
+      .def_property_readonly("bin_min_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<float>(r.binMinPosteriorMeans, r); })
+      .def_property_readonly("bin_argmin_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminPosteriorMeans, r); })
+      .def_property_readonly("bin_min_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binMinMAPs, r); })
+      .def_property_readonly("bin_argmin_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminMAPs, r); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -386,6 +403,9 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setStoreMinMap", &HMM::setStoreMinMap, "storeMinMAP"_a = true,
            "per site the smallest MAP state over the decoded pairs and the first pair that has it, computed on the "
            "device where the per-pair rows are not stored")
+      .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
+           "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
+           "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")
       .def("getExpectedCoalTimes", &HMM::getExpectedCoalTimes,
            "expected coalescence times the per-pair posterior means use: the intervals file's second column when "
            "DecodingParams.expectedCoalTimesFile names one, else the decoding quantities' (HMM.cpp:1736-1748)")
@@ -525,16 +545,26 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("decodeAllInJob", &ASMC::decodeAllInJob)
       .def("decodePairs",
            py::overload_cast<const std::vector<unsigned long>&, const std::vector<unsigned long>&, bool, bool, bool,
-                             bool, bool, bool>(&ASMC::decodePairs),
+                             bool, bool, bool, const std::vector<int>&>(&ASMC::decodePairs),
            "hap_indices_a"_a, "hap_indices_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false)
+           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{},
+           "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
+           "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
+           "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
+           "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
+           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.")
       .def("decodePairs",
            py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool,
-                             bool, bool>(&ASMC::decodePairs),
+                             bool, bool, const std::vector<int>&>(&ASMC::decodePairs),
            "hap_ids_a"_a, "hap_ids_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false)
+           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{},
+           "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
+           "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
+           "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
+           "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
+           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.")
       .def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

@@ -22,6 +22,8 @@
  *   fsmc_decode_pair_minima <- decodeBatch + writePerPairOutput + the column-wise min / argmin of
  *                             DecodePairsReturnStruct::finaliseCalculations
  *                                                  (HMM.cpp:1360-1458, DecodePairsReturnStruct.hpp:105-118)
+ *   fsmc_decode_pair_bins   <- decodeBatch + writePerPairOutput, then per pair the mean / min / argmin of the rows over
+ *                             bins of sites (no counterpart in the reference: its callers reduce the rows in numpy)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -198,6 +200,11 @@ int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices);
  * (64 * S * 4 bytes a group and output).  Results do not depend on it. */
 int fsmc_ctx_set_pair_minima_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_bins.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of rows and binned outputs (64 * 4 bytes * (S a row kind + n_bins an
+ * output) a group).  Results do not depend on it. */
+int fsmc_ctx_set_pair_bins_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -332,6 +339,27 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
  * in the reference; pair_base + n_pairs beyond INT32_MAX. */
 int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, uint64_t pair_base,
                             float* min_mean, int32_t* argmin_mean, int32_t* min_map, int32_t* argmin_map);
+
+/* Per pair of the resident work list, summaries over bins of sites of the rows fsmc_decode_per_pair would write
+ * (mean[i][t], map[i][t]), without those rows leaving the device.  bin_edges: n_bins + 1 int32 values, strictly ascending,
+ * 0 <= bin_edges[0], bin_edges[n_bins] <= S; bin b is sites [bin_edges[b], bin_edges[b + 1]), n of them; sites outside
+ * [bin_edges[0], bin_edges[n_bins]) belong to no bin.  Outputs, [n_pairs][n_bins] each (work-list order) or NULL:
+ *   bin_mean: the mean of mean[i][t] over the bin in a defined fp64 order: slot j (0 <= j < 64) starts at +0.0 and adds
+ *     (double)mean[i][t] for t = bin_edges[b] + j, + 64, ... in ascending order; then for stride = 32, 16, 8, 4, 2, 1:
+ *     a[j] = a[j] + a[j + stride] for j < stride; the result is (float)(a[0] / (double)n): one fp64 divide, one
+ *     round-to-nearest conversion.
+ *   bin_min_mean / bin_argmin_mean (both or neither): the smallest mean[i][t] of the bin under `<` and the lowest
+ *     absolute site index t that has it (numpy's argmin on the slice; a NaN in the bin wins, lowest site first).
+ *   bin_min_map / bin_argmin_map (both or neither): the same for the MAP state.
+ * The mean rows are decoded only when a mean output is asked for, the MAP rows only when a MAP output is.  The work list
+ * goes through the device in slices of groups (fsmc_ctx_set_pair_bins_slice), which are independent; 4 * n_bins bytes a
+ * pair and output cross the bus.  fsmc_last_kernel_ms spans every decode and every reduction of the call (with several
+ * slices also the copies of their outputs in between).  FSMC_EINVAL: null times or edges; no output; a minimum without
+ * its argmin or the reverse; n_bins == 0; edges not strictly ascending or outside [0, S]; a group that is not the whole
+ * sequence (from = 0, to = S). */
+int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, const int32_t* bin_edges,
+                          size_t n_bins, float* bin_mean, float* bin_min_mean, int32_t* bin_argmin_mean,
+                          int32_t* bin_min_map, int32_t* bin_argmin_map);
 
 /* augmentSumOverPairs: sums[S][K] += sum over the pairs of the work list of the posterior
  * (and the 00/01/11 split when the pointers are non-NULL).  Whole-sequence groups only. */
