@@ -15,7 +15,7 @@ from ._pyasmc import (ASMC, BinaryDataReader, Data, DecodePairsReturnStruct, Dec
 __all__ = ["ASMC", "BinaryDataReader", "IbdPairDataLine", "Data", "DecodePairsReturnStruct", "DecodingMode", "DecodingModeOverall", "DecodingParams",
            "DecodingQuantities", "DecodingReturnValues", "FastSMC", "HMM", "Individual", "PairObservations", "Match", "cmBetween",
            "hashingCandidates", "hashingCandidatesDevice", "hashingWords",
-           "decoding_quantities_from_tables", "PreparedModelView", "site_bins"]
+           "decoding_quantities_from_tables", "PreparedModelView", "site_bins", "tail_states"]
 
 
 def decoding_quantities_from_tables(t) -> DecodingQuantities:
@@ -54,3 +54,25 @@ def site_bins(positions, width) -> np.ndarray:
     edges = np.searchsorted(pos, bounds, side="left")
     edges[0], edges[-1] = 0, pos.size  # (the last bound lies beyond the last site)
     return np.unique(edges).astype(np.int32)
+
+
+def tail_states(discretization, times) -> np.ndarray:
+    """State cuts for ``capi.Context.decode_pair_cdf(..., tail_states=...)`` from times in generations, as
+    ``ASMC.decodePairs(..., tail_times=...)`` makes them: the cut of time ``T`` is the number of states ``k < K`` whose
+    interval starts below it, ``discretization[k] < float32(T)`` -- the loop of HMM::getStateThreshold, so the decoding
+    time gives the IBD scan's state threshold.  ``discretization`` is ``DecodingQuantities.discretization``: K + 1
+    values, the K interval starts and the end of the last interval, which is no state's start and is left out.  A time at
+    or below ``discretization[0]`` has no state below it and is refused.  Returns int32 cuts in ``[1, K]``.
+
+    A quantile state ``s`` of the result becomes a time as ``expectedTimes[s]`` (the state's expected coalescence time)
+    or ``discretization[s + 1]`` (the end of its interval)."""
+    disc = np.asarray(discretization, np.float32).reshape(-1)
+    if disc.size < 2:
+        raise ValueError("tail_states: the discretization holds K + 1 values, K >= 1")
+    disc = disc[:-1]
+    t = np.asarray(times, np.float32).reshape(-1)
+    cuts = (disc[None, :] < t[:, None]).sum(axis=1).astype(np.int32)
+    if (cuts == 0).any():
+        bad = float(t[np.nonzero(cuts == 0)[0][0]])
+        raise ValueError(f"tail_states: tail time {bad}: no interval of the discretization starts below it")
+    return cuts

@@ -37,6 +37,7 @@ SYMBOLS = [
     "fsmc_decode_pair_posteriors", "fsmc_ctx_set_pair_posterior_slice", "fsmc_ctx_last_pair_posterior_slices",
     "fsmc_decode_pair_minima", "fsmc_ctx_set_pair_minima_slice", "fsmc_ctx_last_pair_minima_slices",
     "fsmc_decode_pair_bins", "fsmc_ctx_set_pair_bins_slice", "fsmc_ctx_last_pair_bins_slices",
+    "fsmc_decode_pair_cdf", "fsmc_ctx_set_pair_cdf_slice", "fsmc_ctx_last_pair_cdf_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -131,6 +132,9 @@ def load():
         L.fsmc_decode_pair_bins.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
         L.fsmc_ctx_set_pair_bins_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_bins_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_cdf.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+        L.fsmc_ctx_set_pair_cdf_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_cdf_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -460,6 +464,41 @@ class Context:
     def last_pair_bins_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_bins_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):
+        """Per pair of the resident work list and site, the running sum of the posterior over the states in ascending
+        order, fp32 (fsmc_decode_pair_cdf): (tail [n_tail][n_pairs][S] float32, qstate [n_q][n_pairs][S] int32).
+        tail[j] is the sum over the first tail_states[j] states (1 <= cut <= K), qstate[j] the smallest state whose
+        running sum reaches quantiles[j] (0 < q <= 1; K - 1 if none does).  ``out``: (tail, qstate) arrays of
+        [n_tail][>= n_pairs][S] and [n_q][>= n_pairs][S], written in place and returned as they are."""
+        cuts = np.ascontiguousarray(tail_states, np.int32).reshape(-1)
+        qs = np.ascontiguousarray(quantiles, np.float32).reshape(-1)
+        n, S = self._n_pairs, model.S
+        if out is None:
+            out = (np.zeros((cuts.size, n, S), np.float32), np.zeros((qs.size, n, S), np.int32))
+        tail, qstate = out
+        for a, dt, m in ((tail, np.float32, cuts.size), (qstate, np.int32, qs.size)):
+            if (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 3 or a.shape[0] != m
+                    or a.shape[1] < n or a.shape[2] != S):
+                raise ValueError("out: writable C-contiguous arrays (tail float32 [n_tail][>= n_pairs][S], qstate int32 "
+                                 "[n_q][>= n_pairs][S])")
+        tp = (C.c_void_p * max(cuts.size, 1))(*[tail[j].ctypes.data for j in range(cuts.size)])
+        qp = (C.c_void_p * max(qs.size, 1))(*[qstate[j].ctypes.data for j in range(qs.size)])
+        self._check(self._L.fsmc_decode_pair_cdf(self._h, model._h, _p(cuts) if cuts.size else None, cuts.size,
+                                                 C.cast(tp, C.c_void_p) if cuts.size else None,
+                                                 _p(qs) if qs.size else None, qs.size,
+                                                 C.cast(qp, C.c_void_p) if qs.size else None))
+        return tail, qstate
+
+    def set_pair_cdf_slice(self, groups: int):
+        """Groups fsmc_decode_pair_cdf puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_cdf_slice(self._h, groups))
+
+    def last_pair_cdf_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_cdf_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):

@@ -20,6 +20,7 @@
 #include "fsmc_identify.h"
 #include "fsmc_instances.h"
 #include "fsmc_pair_bins.h"
+#include "fsmc_pair_cdf.h"
 #include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
 
@@ -148,6 +149,11 @@ struct fsmc_ctx {
   uint32_t pbSlice = 0;     // groups a slice, 0 = automatic
   int lastPbSlices = 0;     // slices of the last call
   DevBuf pbAcc;             // [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
+
+  // fsmc_decode_pair_cdf: slices of groups as for the posterior tables -- the dump in ppStage, the rows in ppRows
+  uint32_t pcSlice = 0;     // groups a slice, 0 = automatic
+  int lastPcSlices = 0;     // slices of the last call
+  DevBuf pcSpec;            // the call's outputs, PairCdfSpec each
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -984,6 +990,36 @@ uint64_t stagingLimit(const fsmc_ctx* ctx, uint64_t held, unsigned parts)
   return limit;
 }
 
+// The way out for rows a slice leaves on the device (the posterior tables, the tail / quantile rows): two pinned buffers
+// of `need` bytes each at least, the copy stream and its events.
+int ensureRowCopies(fsmc_ctx* ctx, size_t need)
+{
+  if (ctx->ppPinnedBytes < need) {
+    for (int i = 0; i < 2; ++i) {
+      if (ctx->ppPinned[i]) {
+        (void)hipHostFree(ctx->ppPinned[i]);
+        ctx->ppPinned[i] = nullptr;
+      }
+    }
+    ctx->ppPinnedBytes = 0;
+    for (int i = 0; i < 2; ++i) {
+      const hipError_t e = hipHostMalloc(&ctx->ppPinned[i], need, hipHostMallocDefault);
+      if (e != hipSuccess) {
+        ctx->ppPinned[i] = nullptr;
+        return fail(ctx, FSMC_ENOMEM, std::string("hipHostMalloc of the row buffers failed: ") + hipGetErrorString(e));
+      }
+    }
+    ctx->ppPinnedBytes = need;
+  }
+  if (!ctx->copyStream) {
+    FSMC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copyStream, hipStreamNonBlocking));
+    FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evRows, hipEventDisableTiming));
+    FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[0], hipEventDisableTiming));
+    FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[1], hipEventDisableTiming));
+  }
+  return FSMC_OK;
+}
+
 // What the dump / per-pair / pair-posterior / sums entry points share: the kernel, the credit the launch earns, the
 // one-wave plan over `list` and its workspace; then, if a launch of `nItems` workgroups qualifies for two waves per
 // window, that plan and its workspace; the record of what was committed.  The one-wave workspace is held first: the
@@ -1150,6 +1186,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->copyStream) (void)hipStreamSynchronize(ctx->copyStream);
   if (ctx->ppStage.p) (void)hipFree(ctx->ppStage.p);
   if (ctx->ppRows.p) (void)hipFree(ctx->ppRows.p);
+  if (ctx->pcSpec.p) (void)hipFree(ctx->pcSpec.p);
   if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
@@ -1319,6 +1356,24 @@ int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices)
     return FSMC_EINVAL;
   }
   *slices = ctx->lastPbSlices;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->pcSlice = groups;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->lastPcSlices;
   return FSMC_OK;
 }
 
@@ -2305,29 +2360,9 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
   if (wantRows) {
     constexpr size_t kPinnedBytes = 128u << 20;
     pairsPerCopy = std::max<size_t>(1, std::min<size_t>(kPinnedBytes / rowBytes, slicePairsMax));
-    const size_t need = pairsPerCopy * rowBytes;
-    if (ctx->ppPinnedBytes < need) {
-      for (int i = 0; i < 2; ++i) {
-        if (ctx->ppPinned[i]) {
-          (void)hipHostFree(ctx->ppPinned[i]);
-          ctx->ppPinned[i] = nullptr;
-        }
-      }
-      ctx->ppPinnedBytes = 0;
-      for (int i = 0; i < 2; ++i) {
-        const hipError_t e = hipHostMalloc(&ctx->ppPinned[i], need, hipHostMallocDefault);
-        if (e != hipSuccess) {
-          ctx->ppPinned[i] = nullptr;
-          return fail(ctx, FSMC_ENOMEM, std::string("hipHostMalloc of the row buffers failed: ") + hipGetErrorString(e));
-        }
-      }
-      ctx->ppPinnedBytes = need;
-    }
-    if (!ctx->copyStream) {
-      FSMC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copyStream, hipStreamNonBlocking));
-      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evRows, hipEventDisableTiming));
-      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[0], hipEventDisableTiming));
-      FSMC_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied[1], hipEventDisableTiming));
+    rc = ensureRowCopies(ctx, pairsPerCopy * rowBytes);
+    if (rc != FSMC_OK) {
+      return rc;
     }
   }
 
@@ -2720,6 +2755,191 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
     }
   }
   ctx->lastPbSlices = (int)nSlices;
+  return FSMC_OK;
+}
+
+// Per pair and site, tail probabilities at state cuts and quantile states of the posterior (fsmc_pair_cdf.h), without the
+// [K][S] tables leaving the device.  The flow is that of fsmc_decode_pair_posteriors: the dump consumers decode a slice
+// of groups into ppStage, pair_cdf_kernel reduces it into ppRows, [output][pair of slice][S], and the rows of slice i
+// leave through the two pinned buffers on the copy stream while slice i + 1 decodes.  Slices are independent.
+int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
+                         float* const* tail_rows, const float* quantiles, size_t n_quantiles,
+                         int32_t* const* quantile_rows)
+{
+  int rc = checkReady(ctx, m);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  constexpr size_t kMaxOfAKind = 8;
+  if (n_tail == 0 && n_quantiles == 0) {
+    return fail(ctx, FSMC_EINVAL, "need at least one output (a tail state or a quantile)");
+  }
+  if (n_tail > kMaxOfAKind) {
+    return fail(ctx, FSMC_EINVAL, "at most 8 tail states a call");
+  }
+  if (n_quantiles > kMaxOfAKind) {
+    return fail(ctx, FSMC_EINVAL, "at most 8 quantiles a call");
+  }
+  if (n_tail && (!tail_states || !tail_rows)) {
+    return fail(ctx, FSMC_EINVAL, "tail_states or tail_rows is null");
+  }
+  if (n_quantiles && (!quantiles || !quantile_rows)) {
+    return fail(ctx, FSMC_EINVAL, "quantiles or quantile_rows is null");
+  }
+  std::vector<PairCdfSpec> spec;
+  std::vector<char*> hRows; // the caller's matrices, in the order of spec
+  for (size_t j = 0; j < n_tail; ++j) {
+    if (!tail_rows[j]) {
+      return fail(ctx, FSMC_EINVAL, "tail_rows[" + std::to_string(j) + "] is null");
+    }
+    if (tail_states[j] < 1 || tail_states[j] > m->K) {
+      return fail(ctx, FSMC_EINVAL, "tail state " + std::to_string(tail_states[j]) + " outside [1, K]");
+    }
+    spec.push_back(PairCdfSpec{tail_states[j], 0.f});
+    hRows.push_back((char*)tail_rows[j]);
+  }
+  for (size_t j = 0; j < n_quantiles; ++j) {
+    if (!quantile_rows[j]) {
+      return fail(ctx, FSMC_EINVAL, "quantile_rows[" + std::to_string(j) + "] is null");
+    }
+    if (!std::isfinite(quantiles[j]) || !(quantiles[j] > 0.f) || quantiles[j] > 1.f) {
+      return fail(ctx, FSMC_EINVAL, "quantile " + std::to_string(quantiles[j]) + " not finite or outside (0, 1]");
+    }
+    spec.push_back(PairCdfSpec{0, quantiles[j]});
+    hRows.push_back((char*)quantile_rows[j]);
+  }
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "per-pair tails and quantiles need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t K = (size_t)m->K, S = (size_t)m->S, nOut = spec.size();
+  const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
+  const size_t groupBytes = stageBytes + (size_t)kWave * S * sizeof(float) * nOut; // ... and its rows, at most
+  const size_t siteBlocks = (S + kWave - 1) / kWave;
+
+  // The slice: what stagingLimit holds of staging and rows, of half the room the card has free -- the decode's
+  // workspace is allocated after this.  (A slice's reduction is one launch of a workgroup per group and site block.)
+  size_t slice = ctx->pcSlice;
+  if (slice == 0) {
+    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes, 2) / groupBytes);
+  }
+  slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, (size_t)INT32_MAX / siteBlocks}));
+  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
+
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
+  LaunchPlan plan;
+  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  size_t slicePairsMax = 0;
+  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
+    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
+    slicePairsMax = std::max<size_t>(slicePairsMax, ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs -
+                                                      ctx->hGroups[g0].first_pair);
+  }
+  const size_t outCells = slicePairsMax * S; // cells of one output of the largest slice
+  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * stageBytes);
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppRows, nOut * outCells * sizeof(float));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pcSpec, nOut * sizeof(PairCdfSpec));
+  // the way out: two pinned buffers of 128 MiB, or one output of the largest slice if that is smaller
+  constexpr size_t kPinnedBytes = 128u << 20;
+  const size_t cellsPerCopy = std::min<size_t>(kPinnedBytes / sizeof(float), outCells);
+  if (rc == FSMC_OK) rc = ensureRowCopies(ctx, cellsPerCopy * sizeof(float));
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+
+  std::vector<size_t> offsets(slice);
+  for (size_t i = 0; i < slice; ++i) {
+    offsets[i] = i * (size_t)kWave * K * S;
+  }
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nOut * sizeof(PairCdfSpec), hipMemcpyHostToDevice,
+                               ctx->stream));
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets and spec are locals)
+
+  KParams p;
+  fillParams(ctx, m, plan, 0, p);
+  p.dumpOut = (float*)ctx->ppStage.p;
+  p.dumpOffsets = (const size_t*)ctx->aux.p;
+  PairCdfParams q;
+  q.stage = (const float*)ctx->ppStage.p;
+  q.K = m->K;
+  q.S = m->S;
+  q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
+  q.nOut = (int)nOut;
+  q.rows = (int*)ctx->ppRows.p;
+  q.rowsPerOut = slicePairsMax;
+
+  // the rows of pairs [lo, hi) of the work list, rows 0 ... hi - lo of every output on the device: output by output,
+  // copy by copy through the pinned buffers, the next copy in flight while the host moves the one before into the
+  // caller's matrix
+  auto drain = [&](size_t lo, size_t hi) -> int {
+    FSMC_HIP(ctx, hipStreamWaitEvent(ctx->copyStream, ctx->evRows, 0));
+    const size_t cells = (hi - lo) * S;
+    const size_t copiesPerOut = (cells + cellsPerCopy - 1) / cellsPerCopy, nCopies = copiesPerOut * nOut;
+    auto issue = [&](size_t c, int b) -> int {
+      const size_t o = c / copiesPerOut, c0 = (c % copiesPerOut) * cellsPerCopy;
+      FSMC_HIP(ctx, hipMemcpyAsync(ctx->ppPinned[b], (const float*)ctx->ppRows.p + o * outCells + c0,
+                                   std::min(cellsPerCopy, cells - c0) * sizeof(float), hipMemcpyDeviceToHost,
+                                   ctx->copyStream));
+      FSMC_HIP(ctx, hipEventRecord(ctx->evCopied[b], ctx->copyStream));
+      return FSMC_OK;
+    };
+    int b = 0;
+    int r = issue(0, b);
+    for (size_t c = 0; r == FSMC_OK && c < nCopies; ++c, b ^= 1) {
+      if (c + 1 < nCopies) {
+        r = issue(c + 1, b ^ 1);
+        if (r != FSMC_OK) {
+          break;
+        }
+      }
+      FSMC_HIP(ctx, hipEventSynchronize(ctx->evCopied[b]));
+      const size_t o = c / copiesPerOut, c0 = (c % copiesPerOut) * cellsPerCopy;
+      std::memcpy(hRows[o] + (lo * S + c0) * sizeof(float), ctx->ppPinned[b],
+                  std::min(cellsPerCopy, cells - c0) * sizeof(float));
+    }
+    return r;
+  };
+
+  size_t prevLo = 0, prevHi = 0; // pairs of the slice whose rows are still on the device
+  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
+    const size_t nG = std::min(slice, ctx->nGroups - g0);
+    p.groups = ctx->dGroups + g0;
+    p.nGroups = (int)nG;
+    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+    if (prevHi > prevLo) { // (while this slice decodes; ppRows is free again when it returns)
+      rc = drain(prevLo, prevHi);
+      if (rc != FSMC_OK) {
+        return rc;
+      }
+    }
+    q.groups = ctx->dGroups + g0;
+    q.nGroups = (int)nG;
+    q.firstPair = ctx->hGroups[g0].first_pair;
+    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(nG * siteBlocks)), dim3(kPairCdfThreads), 0, ctx->stream, q);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
+    FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+    prevLo = ctx->hGroups[g0].first_pair;
+    prevHi = ctx->hGroups[g0 + nG - 1].first_pair + ctx->hGroups[g0 + nG - 1].n_pairs;
+  }
+  if (prevHi > prevLo) {
+    rc = drain(prevLo, prevHi);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->lastPcSlices = (int)nSlices;
   return FSMC_OK;
 }
 

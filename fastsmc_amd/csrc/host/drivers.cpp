@@ -34,18 +34,22 @@ DecodingReturnValues ASMC::decodeAllInJob()
 
 void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins)
+                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
+                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles)
 {
   if (hapIndicesA.empty() || hapIndicesA.size() != hapIndicesB.size()) {
     throw std::runtime_error("Vector of A indices (" + std::to_string(hapIndicesA.size()) +
                              ") must be the same size as vector of B indices (" +
                              std::to_string(hapIndicesB.size()) + ").\n");
   }
-  mHmm.setSiteBins(siteBins); // (first: edges it refuses leave the last call's results as they are)
+  // (first: arguments these refuse leave the last call's results as they are)
+  const std::vector<int> tailStates = tailStatesOf(tailTimes);
+  mHmm.setPosteriorCdf(tailStates, quantiles);
+  mHmm.setSiteBins(siteBins);
   mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA, hapIndicesB, mHmm.getData().sites,
                                                mHmm.getDecodingQuantities().states, perPairPosteriors, sumOfPosteriors,
                                                perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-                                               siteBins);
+                                               siteBins, tailTimes, tailStates, quantiles);
   mHmm.setStorePerPairPosteriorMean(perPairPosteriorMeans);
   mHmm.setStorePerPairMap(perPairMAPs);
   mHmm.setStorePerPairPosterior(perPairPosteriors);
@@ -59,7 +63,8 @@ void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std:
 
 void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins)
+                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
+                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles)
 {
   if (hapIdsA.size() != hapIdsB.size()) {
     throw std::runtime_error("Vector of A IDs (" + std::to_string(hapIdsA.size()) +
@@ -74,7 +79,24 @@ void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vecto
     b[i] = dipToHapId(getIndIdxFromIdString(ids, strB), hapB);
   }
   decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-              siteBins);
+              siteBins, tailTimes, quantiles);
+}
+
+std::vector<int> ASMC::tailStatesOf(const std::vector<float>& tailTimes)
+{
+  const auto& dq = mHmm.getDecodingQuantities();
+  std::vector<int> cuts;
+  for (const float t : tailTimes) {
+    int c = 0;
+    while (c < static_cast<int>(dq.states) && dq.discretization[static_cast<size_t>(c)] < t) {
+      c++;
+    }
+    if (c == 0) {
+      throw std::runtime_error("tail time " + std::to_string(t) + ": no interval of the discretization starts below it");
+    }
+    cuts.push_back(c);
+  }
+  return cuts;
 }
 
 FastSMC::FastSMC(DecodingParams params) : mParams(withDeviceStarting(std::move(params))), mHmm(Data(mParams), mParams) {}

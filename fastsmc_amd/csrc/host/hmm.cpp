@@ -112,7 +112,8 @@ unsigned long getIndIdxFromIdString(const std::vector<std::string>& ids, const s
 void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>&,
                                          long sites, long states, bool fullPosteriors, bool sumOfPost,
                                          bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps,
-                                         const std::vector<int>& siteBins)
+                                         const std::vector<int>& siteBins, const std::vector<float>& tailTimesIn,
+                                         const std::vector<int>& tailStatesIn, const std::vector<float>& quantilesIn)
 {
   numWritten = 0;
   numPairs = static_cast<long>(hapsA.size());
@@ -166,6 +167,13 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
   binArgminPosteriorMeans.assign(cells, 0);
   binMinMAPs.assign(cells, 0);
   binArgminMAPs.assign(cells, 0);
+  // the per-pair tail probabilities and quantile states: [outputs][pairs][sites]
+  tailTimes = tailTimesIn;
+  tailStates = tailStatesIn;
+  quantiles = quantilesIn;
+  const size_t rowCells = static_cast<size_t>(numPairs) * static_cast<size_t>(sites);
+  perPairTailProbabilities.assign(tailStates.size() * rowCells, 0.f);
+  perPairQuantileStates.assign(quantiles.size() * rowCells, 0);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()
@@ -668,6 +676,31 @@ void HMM::setSiteBins(const std::vector<int>& edges)
   updateOutputStructures();
 }
 
+void HMM::setPosteriorCdf(const std::vector<int>& tailStates, const std::vector<float>& quantiles)
+{
+  // (the messages of fsmc_decode_pair_cdf)
+  if (tailStates.size() > 8) {
+    throw std::runtime_error("at most 8 tail states a call");
+  }
+  if (quantiles.size() > 8) {
+    throw std::runtime_error("at most 8 quantiles a call");
+  }
+  for (const int c : tailStates) {
+    if (c < 1 || c > static_cast<int>(mDq.states)) {
+      throw std::runtime_error("tail state " + std::to_string(c) + " outside [1, K]");
+    }
+  }
+  for (const float q : quantiles) {
+    if (!std::isfinite(q) || !(q > 0.f) || q > 1.f) {
+      throw std::runtime_error("quantile " + std::to_string(q) + " not finite or outside (0, 1]");
+    }
+  }
+  flush(); // (what is queued was decoded under the old setting)
+  mTailStates = tailStates;
+  mQuantiles = quantiles;
+  updateOutputStructures();
+}
+
 void HMM::setWritePerPairPosteriorMean(bool v)
 {
   flush(); // (what is queued was decoded under the old setting in the reference)
@@ -1001,8 +1034,9 @@ void HMM::flush()
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
   const bool minMeanOnDevice = mStoreMinMean && !mStoreMean, minMapOnDevice = mStoreMinMap && !mStoreMap;
   const bool binsOnDevice = !mSiteBins.empty();
+  const bool cdfOnDevice = !mTailStates.empty() || !mQuantiles.empty();
   const bool storeAny = mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice ||
-                        minMapOnDevice || binsOnDevice;
+                        minMapOnDevice || binsOnDevice || cdfOnDevice;
   if (!mParams.FastSMC && (storeAny || writeFiles)) {
     // writePerPairOutput (HMM.cpp:1360-1458)
     const size_t S = static_cast<size_t>(mData.sites);
@@ -1050,6 +1084,30 @@ void HMM::flush()
                                   R.binArgminPosteriorMeans.data() + at, R.binMinMAPs.data() + at,
                                   R.binArgminMAPs.data() + at),
             "fsmc_decode_pair_bins");
+    }
+    if (cdfOnDevice) {
+      // per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far:
+      // 4 bytes a pair-site and output cross the bus, the posterior tables stay on the device (where the tables are
+      // stored as well, this decodes the flush again)
+      const size_t rowCells = static_cast<size_t>(R.numPairs) * S;
+      if (R.tailStates != mTailStates || R.quantiles != mQuantiles ||
+          R.perPairTailProbabilities.size() != mTailStates.size() * rowCells ||
+          R.perPairQuantileStates.size() != mQuantiles.size() * rowCells) {
+        throw std::runtime_error("the return structure was not initialised for the tail states and quantiles asked for");
+      }
+      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
+      std::vector<float*> tailRows(mTailStates.size());
+      std::vector<int32_t*> quantileRows(mQuantiles.size());
+      for (size_t j = 0; j < tailRows.size(); ++j) {
+        tailRows[j] = R.perPairTailProbabilities.data() + j * rowCells + base * S;
+      }
+      for (size_t j = 0; j < quantileRows.size(); ++j) {
+        quantileRows[j] = R.perPairQuantileStates.data() + j * rowCells + base * S;
+      }
+      check(mCtx,
+            fsmc_decode_pair_cdf(mCtx, mModel, mTailStates.data(), mTailStates.size(), tailRows.data(), mQuantiles.data(),
+                                 mQuantiles.size(), quantileRows.data()),
+            "fsmc_decode_pair_cdf");
     }
     if (mStorePosterior || mStoreSumOfPosterior) {
       // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]

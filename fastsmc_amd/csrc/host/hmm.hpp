@@ -58,11 +58,21 @@ struct DecodePairsReturnStruct {
   std::vector<int> binEdges;
   std::vector<float> binMeanPosteriorMeans, binMinPosteriorMeans;
   std::vector<int> binArgminPosteriorMeans, binMinMAPs, binArgminMAPs;
+  // per pair and site, where the posterior mass lies (computed on the device, fsmc_decode_pair_cdf): the sum of the
+  // posterior over the first tailStates[j] states (tailTimes[j]: the time in generations the cut was made from), and the
+  // smallest state at which that running sum reaches quantiles[j]; [tails][pairs][sites] and [quantiles][pairs][sites]
+  std::vector<float> tailTimes;
+  std::vector<int> tailStates;
+  std::vector<float> quantiles;
+  std::vector<float> perPairTailProbabilities;
+  std::vector<int> perPairQuantileStates;
   size_t numWritten = 0;
 
   void initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>& hapsB, long sites,
                   long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps,
-                  bool minMeans = false, bool minMaps = false, const std::vector<int>& siteBins = {});
+                  bool minMeans = false, bool minMaps = false, const std::vector<int>& siteBins = {},
+                  const std::vector<float>& tailTimesIn = {}, const std::vector<int>& tailStatesIn = {},
+                  const std::vector<float>& quantilesIn = {});
   void finaliseCalculations();
 };
 
@@ -148,6 +158,11 @@ public:
   // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
   // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
   void setSiteBins(const std::vector<int>& edges);
+  // per pair and site the sum of the posterior over the first tailStates[j] states (1 <= cut <= states) and the smallest
+  // state at which the running sum over the states reaches quantiles[j] (0 < q <= 1), into the return structure's
+  // per_pair_tail_probabilities / per_pair_quantile_states (fsmc_decode_pair_cdf); both empty turns this off.  Throws
+  // what the ABI would refuse: more than 8 of either kind, a cut outside [1, states], a quantile outside (0, 1].
+  void setPosteriorCdf(const std::vector<int>& tailStates, const std::vector<float>& quantiles);
   // HMM.hpp:287,293: per-pair posterior means / MAP states of every decoded pair as text, one row per pair, to
   // <outFileRoot>.perPairPosteriorMeans.gz / .perPairMAP.gz (ASMC mode; opened by resetDecoding, HMM.cpp:259-271,
   // written batch by batch, HMM.cpp:1412-1420, closed by finishDecoding, HMM.cpp:515-524)
@@ -245,6 +260,8 @@ private:
   bool mStoreMean = false, mStoreMap = false, mStorePosterior = false, mStoreSumOfPosterior = false;
   bool mStoreMinMean = false, mStoreMinMap = false;
   std::vector<int> mSiteBins; // bin edges of the per-pair summaries, empty = none
+  std::vector<int> mTailStates;  // state cuts of the per-pair tail probabilities, empty = none
+  std::vector<float> mQuantiles; // quantiles of the per-pair quantile states, empty = none
   bool mWriteMean = false, mWriteMap = false;
   gzFile mMeanFile = nullptr, mMapFile = nullptr;
   int mMeanFd = -1, mMapFd = -1; // their descriptors (blocks of rows go out as gzip members of their own)

@@ -94,6 +94,17 @@ py::array_t<T> binMatrix(const std::vector<T>& v, const DecodePairsReturnStruct&
   return toArray<T>(v, {static_cast<py::ssize_t>(r.numPairs), static_cast<py::ssize_t>(r.binEdges.size() - 1)});
 }
 
+// an [outputs][pairs][sites] stack of the return structure's tail / quantile rows ([0][0][0] without outputs)
+template <typename T>
+py::array_t<T> cdfRows(const std::vector<T>& v, size_t nOut, const DecodePairsReturnStruct& r)
+{
+  if (v.empty()) {
+    return py::array_t<T>(std::vector<py::ssize_t>{0, 0, 0});
+  }
+  return toArray<T>(v, {static_cast<py::ssize_t>(nOut), static_cast<py::ssize_t>(r.numPairs),
+                        static_cast<py::ssize_t>(r.numSites)});
+}
+
 PYBIND11_MODULE(_pyasmc, m)
 {
   m.doc() = "MI355X-native drop-in for the decode path of PalamaraLab/FastSMC (pyASMC-compatible names)";
@@ -145,7 +156,14 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("bin_min_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<float>(r.binMinPosteriorMeans, r); })
       .def_property_readonly("bin_argmin_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminPosteriorMeans, r); })
       .def_property_readonly("bin_min_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binMinMAPs, r); })
-      .def_property_readonly("bin_argmin_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminMAPs, r); });
+      .def_property_readonly("bin_argmin_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminMAPs, r); })
+      // per pair and site: the posterior mass of the first tail_states[j] states (tail_times[j]: the generations asked
+      // for) and the smallest state whose running sum reaches quantiles[j]; [outputs][pairs][sites], empty without outputs
+      .def_property_readonly("tail_times", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.tailTimes, {static_cast<py::ssize_t>(r.tailTimes.size())}); })
+      .def_property_readonly("tail_states", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.tailStates, {static_cast<py::ssize_t>(r.tailStates.size())}); })
+      .def_property_readonly("quantiles", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.quantiles, {static_cast<py::ssize_t>(r.quantiles.size())}); })
+      .def_property_readonly("per_pair_tail_probabilities", [](const DecodePairsReturnStruct& r) { return cdfRows<float>(r.perPairTailProbabilities, r.tailStates.size(), r); })
+      .def_property_readonly("per_pair_quantile_states", [](const DecodePairsReturnStruct& r) { return cdfRows<int>(r.perPairQuantileStates, r.quantiles.size(), r); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -406,6 +424,10 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
            "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
            "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")
+      .def("setPosteriorCdf", &HMM::setPosteriorCdf, "tail_states"_a, "quantiles"_a,
+           "per pair and site the posterior mass of the first tail_states[j] states (1 <= cut <= states) and the smallest "
+           "state at which the running sum over the states reaches quantiles[j] (0 < q <= 1), computed on the device; up "
+           "to 8 of each, two empty lists turn this off")
       .def("getExpectedCoalTimes", &HMM::getExpectedCoalTimes,
            "expected coalescence times the per-pair posterior means use: the intervals file's second column when "
            "DecodingParams.expectedCoalTimesFile names one, else the decoding quantities' (HMM.cpp:1736-1748)")
@@ -545,26 +567,48 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("decodeAllInJob", &ASMC::decodeAllInJob)
       .def("decodePairs",
            py::overload_cast<const std::vector<unsigned long>&, const std::vector<unsigned long>&, bool, bool, bool,
-                             bool, bool, bool, const std::vector<int>&>(&ASMC::decodePairs),
+                             bool, bool, bool, const std::vector<int>&, const std::vector<float>&,
+                             const std::vector<float>&>(&ASMC::decodePairs),
            "hap_indices_a"_a, "hap_indices_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{},
+           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
+           "quantiles"_a = std::vector<float>{},
            "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
            "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
            "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
            "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
-           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.")
+           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.  "
+           "tail_times (generations, up to 8) / quantiles (in (0, 1], up to 8): per pair and site, computed on the device "
+           "from the posterior over the states summed in ascending order in fp32, per_pair_tail_probabilities "
+           "([tails][pairs][sites] float32: the probability of a coalescence in one of the states whose interval starts "
+           "below the time -- the cut of HMM::getStateThreshold, reported in tail_states; tail_times=[params.time] is the "
+           "IBD scan's per-site sum) and per_pair_quantile_states ([quantiles][pairs][sites] int32: the smallest state at "
+           "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
+           "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
+           "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
+           "each flush.")
       .def("decodePairs",
            py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool,
-                             bool, bool, const std::vector<int>&>(&ASMC::decodePairs),
+                             bool, bool, const std::vector<int>&, const std::vector<float>&,
+                             const std::vector<float>&>(&ASMC::decodePairs),
            "hap_ids_a"_a, "hap_ids_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{},
+           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
+           "quantiles"_a = std::vector<float>{},
            "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
            "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
            "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
            "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
-           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.")
+           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.  "
+           "tail_times (generations, up to 8) / quantiles (in (0, 1], up to 8): per pair and site, computed on the device "
+           "from the posterior over the states summed in ascending order in fp32, per_pair_tail_probabilities "
+           "([tails][pairs][sites] float32: the probability of a coalescence in one of the states whose interval starts "
+           "below the time -- the cut of HMM::getStateThreshold, reported in tail_states; tail_times=[params.time] is the "
+           "IBD scan's per-site sum) and per_pair_quantile_states ([quantiles][pairs][sites] int32: the smallest state at "
+           "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
+           "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
+           "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
+           "each flush.")
       .def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

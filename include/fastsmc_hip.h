@@ -24,6 +24,9 @@
  *                                                  (HMM.cpp:1360-1458, DecodePairsReturnStruct.hpp:105-118)
  *   fsmc_decode_pair_bins   <- decodeBatch + writePerPairOutput, then per pair the mean / min / argmin of the rows over
  *                             bins of sites (no counterpart in the reference: its callers reduce the rows in numpy)
+ *   fsmc_decode_pair_cdf    <- decodeBatch, then per pair and site the running sum of the posterior over the states: tail
+ *                             probabilities and quantile states (none: the reference's callers do this in numpy on
+ *                             perPairPosteriors; the sum's order is the IBD scan's, HMM.cpp:1207-1224)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -205,6 +208,11 @@ int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices);
  * output) a group).  Results do not depend on it. */
 int fsmc_ctx_set_pair_bins_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_cdf.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of staging and rows (64 * K * S * 4 bytes a group of staging plus
+ * 64 * S * 4 bytes a group and output).  Results do not depend on it. */
+int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -360,6 +368,25 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
 int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, const int32_t* bin_edges,
                           size_t n_bins, float* bin_mean, float* bin_min_mean, int32_t* bin_argmin_mean,
                           int32_t* bin_min_map, int32_t* bin_argmin_map);
+
+/* Per pair of the resident work list and site, where the posterior mass lies, without the [K][S] tables leaving the
+ * device.  post[k] is the pair's normalised fp32 posterior at the site over the model's K states (not multiplied by any
+ * time).  In fp32 and in ascending k only, one add a state (the IBD scan's order, HMM.cpp:1207-1224):
+ *   cdf[0] = 0.f + post[0];  cdf[k] = cdf[k-1] + post[k]
+ *   tail_rows[j][i * S + t] = cdf[c - 1] for the cut c = tail_states[j], 1 <= c <= K: the probability that pair i
+ *     coalesced in one of the first c states at site t.  c = K is allowed; the result is then 1 give or take an ulp.
+ *   quantile_rows[j][i * S + t] = the smallest k with cdf[k] >= q under an fp32 compare, q = quantiles[j], 0 < q <= 1;
+ *     K - 1 if no state reaches q (rounding can leave cdf[K-1] < 1; a NaN never compares true and gives K - 1 too).
+ * Up to 8 cuts and up to 8 quantiles a call, one at least in total, in any order, duplicates allowed.  tail_rows[j] and
+ * quantile_rows[j] each point at [n_pairs][S] caller memory in work-list order; every output is independent.  The work
+ * list goes through the device in slices of groups (fsmc_ctx_set_pair_cdf_slice); a slice's rows leave through pinned
+ * buffers while the next slice decodes; 4 bytes a pair-site and output cross the bus.  fsmc_last_kernel_ms spans every
+ * decode and every reduction of the call.  FSMC_EINVAL: no output at all; more than 8 of either kind; a null array where
+ * its count is non-zero; a null row pointer; a cut outside [1, K]; a quantile that is not finite or outside (0, 1]; a
+ * group that is not the whole sequence (from = 0, to = S). */
+int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
+                         float* const* tail_rows, const float* quantiles, size_t n_quantiles,
+                         int32_t* const* quantile_rows);
 
 /* augmentSumOverPairs: sums[S][K] += sum over the pairs of the work list of the posterior
  * (and the 00/01/11 split when the pointers are non-NULL).  Whole-sequence groups only. */
