@@ -15,7 +15,7 @@ from ._pyasmc import (ASMC, BinaryDataReader, Data, DecodePairsReturnStruct, Dec
 __all__ = ["ASMC", "BinaryDataReader", "IbdPairDataLine", "Data", "DecodePairsReturnStruct", "DecodingMode", "DecodingModeOverall", "DecodingParams",
            "DecodingQuantities", "DecodingReturnValues", "FastSMC", "HMM", "Individual", "PairObservations", "Match", "cmBetween",
            "hashingCandidates", "hashingCandidatesDevice", "hashingWords",
-           "decoding_quantities_from_tables", "PreparedModelView", "site_bins", "tail_states"]
+           "decoding_quantities_from_tables", "PreparedModelView", "site_bins", "tail_states", "site_widths"]
 
 
 def decoding_quantities_from_tables(t) -> DecodingQuantities:
@@ -76,3 +76,18 @@ def tail_states(discretization, times) -> np.ndarray:
         bad = float(t[np.nonzero(cuts == 0)[0][0]])
         raise ValueError(f"tail_states: tail time {bad}: no interval of the discretization starts below it")
     return cuts
+
+
+def site_widths(genetic_positions) -> np.ndarray:
+    """Weights for ``ASMC.decodePairs(..., tail_summary_times=..., site_bins=..., site_weights=...)`` that make
+    ``per_pair_bin_tail_lengths`` an expected length in centimorgans: the cM site ``t`` stands for, half the distance
+    between its neighbours, ``50 * (gen[min(t + 1, S - 1)] - gen[max(t - 1, 0)])`` with ``genetic_positions`` in Morgans
+    as ``Data.geneticPositions`` holds them (the first and the last site get half the distance to their one neighbour).
+    Computed in float64 and rounded once; returns float32 ``[S]``."""
+    gen = np.asarray(genetic_positions, np.float64).reshape(-1)
+    if gen.size == 0:
+        raise ValueError("site_widths: no positions")
+    if not np.isfinite(gen).all():
+        raise ValueError("site_widths: positions must be finite")
+    t = np.arange(gen.size)
+    return (50.0 * (gen[np.minimum(t + 1, gen.size - 1)] - gen[np.maximum(t - 1, 0)])).astype(np.float32)

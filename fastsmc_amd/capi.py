@@ -38,6 +38,7 @@ SYMBOLS = [
     "fsmc_decode_pair_minima", "fsmc_ctx_set_pair_minima_slice", "fsmc_ctx_last_pair_minima_slices",
     "fsmc_decode_pair_bins", "fsmc_ctx_set_pair_bins_slice", "fsmc_ctx_last_pair_bins_slices",
     "fsmc_decode_pair_cdf", "fsmc_ctx_set_pair_cdf_slice", "fsmc_ctx_last_pair_cdf_slices",
+    "fsmc_decode_pair_tail_summaries", "fsmc_ctx_set_pair_tail_slice", "fsmc_ctx_last_pair_tail_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -135,6 +136,9 @@ def load():
         L.fsmc_decode_pair_cdf.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
         L.fsmc_ctx_set_pair_cdf_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_cdf_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_tail_summaries.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+        L.fsmc_ctx_set_pair_tail_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_tail_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -499,6 +503,57 @@ class Context:
     def last_pair_cdf_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_cdf_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_tail_summaries(self, model: "Model", tail_states, bin_edges=None, site_weights=None, want_sum=True,
+                                   want_bin_mean=None, want_bin_length=None, out=None):
+        """The tail probabilities of ``decode_pair_cdf`` reduced on the device (fsmc_decode_pair_tail_summaries):
+        (tail_sum [n_tail][S] float64, bin_tail_mean [n_tail][n_pairs][B] float32, bin_tail_length, the same shape),
+        None for an output that was not asked for.  tail_sum is the fp64 sum over the pairs in work-list order;
+        bin_tail_mean the mean over the sites [bin_edges[b], bin_edges[b + 1]) in the defined fp64 order of
+        ``decode_pair_bins``' bin_mean; bin_tail_length the sum of tail * site_weights over the bin in that order.
+        ``want_bin_mean`` / ``want_bin_length`` default to "edges given" / "edges and weights given".  ``out``: three
+        such arrays (None where not wanted), written in place and returned as they are -- the ``want_*`` switches are
+        ignored then, and tail_sum CONTINUES from what the array holds (zeros start a sum)."""
+        cuts = np.ascontiguousarray(tail_states, np.int32).reshape(-1)
+        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
+        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
+        if edges is not None and edges.size == 0:
+            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        w = None if site_weights is None else np.ascontiguousarray(site_weights, np.float32).reshape(-1)
+        n, S = self._n_pairs, model.S
+        if w is not None and w.shape != (S,):
+            raise ValueError(f"site_weights: shape {w.shape}, expected {(S,)}")
+        if out is None:
+            if want_bin_mean is None:
+                want_bin_mean = edges is not None
+            if want_bin_length is None:
+                want_bin_length = edges is not None and w is not None
+            out = (np.zeros((cuts.size, S), np.float64) if want_sum else None,
+                   np.zeros((cuts.size, n, n_bins), np.float32) if want_bin_mean else None,
+                   np.zeros((cuts.size, n, n_bins), np.float32) if want_bin_length else None)
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("out: (tail_sum, bin_tail_mean, bin_tail_length)")
+        for a, dt, shape in zip(out, (np.float64, np.float32, np.float32),
+                                ((cuts.size, S), (cuts.size, n, n_bins), (cuts.size, n, n_bins))):
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.shape != shape):
+                raise ValueError("out: writable C-contiguous arrays (tail_sum float64 [n_tail][S], bin_tail_mean and "
+                                 "bin_tail_length float32 [n_tail][n_pairs][B])")
+        # (an empty array has no address worth passing: the library sees NULL only where the output is not wanted)
+        ptr = [None if a is None else C.c_void_p(a.ctypes.data or 1) for a in out]
+        self._check(self._L.fsmc_decode_pair_tail_summaries(self._h, model._h, _p(cuts) if cuts.size else None, cuts.size,
+                                                            ptr[0], _p(edges), n_bins, ptr[1], _p(w), ptr[2]))
+        return out
+
+    def set_pair_tail_slice(self, groups: int):
+        """Groups fsmc_decode_pair_tail_summaries puts through the device at a time; 0 = automatic.  Results do not
+        depend on it."""
+        self._check(self._L.fsmc_ctx_set_pair_tail_slice(self._h, groups))
+
+    def last_pair_tail_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_tail_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):

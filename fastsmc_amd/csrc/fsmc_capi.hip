@@ -21,6 +21,7 @@
 #include "fsmc_instances.h"
 #include "fsmc_pair_bins.h"
 #include "fsmc_pair_cdf.h"
+#include "fsmc_pair_tail.h"
 #include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
 
@@ -154,6 +155,11 @@ struct fsmc_ctx {
   uint32_t pcSlice = 0;     // groups a slice, 0 = automatic
   int lastPcSlices = 0;     // slices of the last call
   DevBuf pcSpec;            // the call's outputs, PairCdfSpec each
+
+  // fsmc_decode_pair_tail_summaries: slices of groups as for fsmc_decode_pair_cdf, whose rows stay in ppRows
+  uint32_t ptSlice = 0;     // groups a slice, 0 = automatic
+  int lastPtSlices = 0;     // slices of the last call
+  DevBuf ptAcc;             // [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -1187,6 +1193,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->ppStage.p) (void)hipFree(ctx->ppStage.p);
   if (ctx->ppRows.p) (void)hipFree(ctx->ppRows.p);
   if (ctx->pcSpec.p) (void)hipFree(ctx->pcSpec.p);
+  if (ctx->ptAcc.p) (void)hipFree(ctx->ptAcc.p);
   if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
@@ -1374,6 +1381,24 @@ int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices)
     return FSMC_EINVAL;
   }
   *slices = ctx->lastPcSlices;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->ptSlice = groups;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->lastPtSlices;
   return FSMC_OK;
 }
 
@@ -2940,6 +2965,218 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
   }
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->lastPcSlices = (int)nSlices;
+  return FSMC_OK;
+}
+
+// The tail probabilities of fsmc_decode_pair_cdf reduced over pairs per site and over bins of sites per pair
+// (fsmc_pair_tail.h), without the tail rows leaving the device.  The flow is that of fsmc_decode_pair_cdf up to the rows:
+// the dump consumers decode a slice of groups into ppStage, pair_cdf_kernel -- as it is -- reduces it into ppRows,
+// [cut][pair of slice][S]; then pair_tail_sum_kernel continues the fp64 chain of every site in the device copy of the
+// accumulator and pair_tail_bins_kernel reduces the rows cell by cell, and the slice's [cut][pairs][B] outputs are copied
+// to the caller's arrays at the slice's first pair.  Only the sum is carried from slice to slice.
+int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
+                                    double* tail_sum, const int32_t* bin_edges, size_t n_bins, float* bin_tail_mean,
+                                    const float* site_weights, float* bin_tail_length)
+{
+  int rc = checkReady(ctx, m);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  constexpr size_t kMaxCuts = 8;
+  const bool wantBins = bin_tail_mean || bin_tail_length;
+  if (!tail_sum && !wantBins) {
+    return fail(ctx, FSMC_EINVAL, "need at least one output (tail_sum, bin_tail_mean or bin_tail_length)");
+  }
+  if (n_tail == 0 || !tail_states) {
+    return fail(ctx, FSMC_EINVAL, "need one tail state at least");
+  }
+  if (n_tail > kMaxCuts) {
+    return fail(ctx, FSMC_EINVAL, "at most 8 tail states a call");
+  }
+  std::vector<PairCdfSpec> spec;
+  for (size_t j = 0; j < n_tail; ++j) {
+    if (tail_states[j] < 1 || tail_states[j] > m->K) {
+      return fail(ctx, FSMC_EINVAL, "tail state " + std::to_string(tail_states[j]) + " outside [1, K]");
+    }
+    spec.push_back(PairCdfSpec{tail_states[j], 0.f});
+  }
+  if (wantBins) {
+    if (!bin_edges) {
+      return fail(ctx, FSMC_EINVAL, "bin outputs need bin edges");
+    }
+    if (n_bins == 0) {
+      return fail(ctx, FSMC_EINVAL, "need one bin at least (n_bins + 1 edges)");
+    }
+    if (n_bins > (size_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending: more bins than sites");
+    }
+    if (bin_edges[0] < 0 || bin_edges[n_bins] > m->S) {
+      return fail(ctx, FSMC_EINVAL, "bin edges must lie in [0, sites]");
+    }
+    for (size_t b = 0; b < n_bins; ++b) {
+      if (bin_edges[b] >= bin_edges[b + 1]) {
+        return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending");
+      }
+    }
+  }
+  if (bin_tail_length) {
+    if (!site_weights) {
+      return fail(ctx, FSMC_EINVAL, "bin_tail_length needs site weights");
+    }
+    for (int t = 0; t < m->S; ++t) {
+      if (!std::isfinite(site_weights[t])) {
+        return fail(ctx, FSMC_EINVAL, "site weight " + std::to_string(t) + " is not finite");
+      }
+    }
+  }
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, "tail summaries need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t K = (size_t)m->K, S = (size_t)m->S, nT = n_tail, B = wantBins ? n_bins : 0;
+  const size_t nBinOut = (bin_tail_mean ? 1 : 0) + (bin_tail_length ? 1 : 0);
+  const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
+  // ... and its rows and its cells in the output buffer
+  const size_t groupBytes = stageBytes + (size_t)kWave * sizeof(float) * nT * (S + B * nBinOut);
+  const size_t siteBlocks = (S + kWave - 1) / kWave;
+
+  // The slice: what stagingLimit holds of staging, rows and outputs, of half the room the card has free -- the decode's
+  // workspace is allocated after this.
+  size_t slice = ctx->ptSlice;
+  if (slice == 0) {
+    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes + ctx->ptAcc.bytes, 2) / groupBytes);
+  }
+  slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, (size_t)INT32_MAX / siteBlocks}));
+  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
+
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
+  LaunchPlan plan;
+  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+  auto pairsOfSlice = [&](size_t g0) {
+    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
+    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
+  };
+  size_t slicePairsMax = 0;
+  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
+    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
+  }
+  if (slicePairsMax > (size_t)INT32_MAX) {
+    return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_tail_slice)");
+  }
+  const size_t sumBytes = nT * S * sizeof(double);
+  const size_t edgeBytes = wantBins ? ((B + 1) * sizeof(int32_t) + 7) / 8 * 8 : 0;
+  const size_t weightBytes = bin_tail_length ? (S * sizeof(float) + 7) / 8 * 8 : 0;
+  const size_t outBytes = nT * slicePairsMax * B * sizeof(float); // one output of the largest slice, every cut
+  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * stageBytes);
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppRows, nT * slicePairsMax * S * sizeof(float));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pcSpec, nT * sizeof(PairCdfSpec));
+  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ptAcc, sumBytes + edgeBytes + weightBytes + nBinOut * outBytes);
+  if (rc != FSMC_OK) {
+    return rc;
+  }
+
+  char* const acc = (char*)ctx->ptAcc.p;
+  double* const dSum = (double*)acc;
+  char* const dEdges = acc + sumBytes;
+  char* const dWeights = dEdges + edgeBytes;
+  float* const dMean = bin_tail_mean ? (float*)(dWeights + weightBytes) : nullptr;
+  float* const dLength = bin_tail_length ? (float*)(dWeights + weightBytes + (bin_tail_mean ? outBytes : 0)) : nullptr;
+  std::vector<size_t> offsets(slice);
+  for (size_t i = 0; i < slice; ++i) {
+    offsets[i] = i * (size_t)kWave * K * S;
+  }
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nT * sizeof(PairCdfSpec), hipMemcpyHostToDevice, ctx->stream));
+  if (tail_sum) { // the chain continues what the caller passes in
+    FSMC_HIP(ctx, hipMemcpyAsync(dSum, tail_sum, sumBytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (wantBins) {
+    FSMC_HIP(ctx, hipMemcpyAsync(dEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (bin_tail_length) {
+    FSMC_HIP(ctx, hipMemcpyAsync(dWeights, site_weights, S * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets and spec are locals, the rest the caller's)
+
+  KParams p;
+  fillParams(ctx, m, plan, 0, p);
+  p.dumpOut = (float*)ctx->ppStage.p;
+  p.dumpOffsets = (const size_t*)ctx->aux.p;
+  PairCdfParams q;
+  q.stage = (const float*)ctx->ppStage.p;
+  q.K = m->K;
+  q.S = m->S;
+  q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
+  q.nOut = (int)nT;
+  q.rows = (int*)ctx->ppRows.p;
+  q.rowsPerOut = slicePairsMax;
+  PairTailParams r;
+  r.rows = (const float*)ctx->ppRows.p;
+  r.rowsPerOut = slicePairsMax;
+  r.S = m->S;
+  r.nTail = (int)nT;
+  r.sum = tail_sum ? dSum : nullptr;
+  r.edges = wantBins ? (const int*)dEdges : nullptr;
+  r.weights = bin_tail_length ? (const float*)dWeights : nullptr;
+  r.B = (int)B;
+  r.binMean = dMean;
+  r.binLength = dLength;
+  // waves of the bin reduction: one per cell, no more than fill the chip eight deep over the cuts
+  const size_t wavesPerBlock = kPairBinsThreads / kWave;
+  const size_t blocksMax = std::max<size_t>(1, (size_t)8 * (size_t)std::max(ctx->nCU, 1) / nT);
+  float* const hOut[2] = {bin_tail_mean, bin_tail_length};
+  const float* const dOut[2] = {dMean, dLength};
+
+  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
+    const size_t nG = std::min(slice, ctx->nGroups - g0);
+    const size_t firstPair = ctx->hGroups[g0].first_pair;
+    const size_t n = pairsOfSlice(g0);
+    p.groups = ctx->dGroups + g0;
+    p.nGroups = (int)nG;
+    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
+    if (rc != FSMC_OK) {
+      return rc;
+    }
+    q.groups = ctx->dGroups + g0;
+    q.nGroups = (int)nG;
+    q.firstPair = (unsigned)firstPair;
+    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(nG * siteBlocks)), dim3(kPairCdfThreads), 0, ctx->stream, q);
+    FSMC_HIP(ctx, hipGetLastError());
+    r.n = (int)n;
+    if (tail_sum) {
+      hipLaunchKernelGGL(pair_tail_sum_kernel, dim3((unsigned)siteBlocks, (unsigned)nT), dim3(kWave), 0, ctx->stream, r);
+      FSMC_HIP(ctx, hipGetLastError());
+    }
+    if (wantBins) {
+      const size_t blocks = std::min(blocksMax, (n * B + wavesPerBlock - 1) / wavesPerBlock);
+      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3((unsigned)blocks, (unsigned)nT), dim3(kPairBinsThreads), 0,
+                         ctx->stream, r);
+      FSMC_HIP(ctx, hipGetLastError());
+    }
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
+    if (wantBins) {
+      // the slice's cells go to the caller before the next slice overwrites them, cut by cut (no second buffer, no
+      // overlap: 8 bytes a cell at most against the 4 K bytes a pair-site of the dump)
+      FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      for (int o = 0; o < 2; ++o) {
+        for (size_t j = 0; hOut[o] && j < nT; ++j) {
+          FSMC_HIP(ctx, hipMemcpy(hOut[o] + (j * ctx->nPairs + firstPair) * B, dOut[o] + j * slicePairsMax * B,
+                                  n * B * sizeof(float), hipMemcpyDeviceToHost));
+        }
+      }
+    }
+  }
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (tail_sum) {
+    FSMC_HIP(ctx, hipMemcpy(tail_sum, dSum, sumBytes, hipMemcpyDeviceToHost));
+  }
+  ctx->lastPtSlices = (int)nSlices;
   return FSMC_OK;
 }
 

@@ -35,7 +35,8 @@ DecodingReturnValues ASMC::decodeAllInJob()
 void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
                        bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
-                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles)
+                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
+                       const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights)
 {
   if (hapIndicesA.empty() || hapIndicesA.size() != hapIndicesB.size()) {
     throw std::runtime_error("Vector of A indices (" + std::to_string(hapIndicesA.size()) +
@@ -44,12 +45,18 @@ void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std:
   }
   // (first: arguments these refuse leave the last call's results as they are)
   const std::vector<int> tailStates = tailStatesOf(tailTimes);
+  const std::vector<int> tailSummaryStates = tailStatesOf(tailSummaryTimes);
+  if (!siteWeights.empty() && siteBins.empty()) {
+    throw std::runtime_error("site weights need site bins");
+  }
   mHmm.setPosteriorCdf(tailStates, quantiles);
+  mHmm.setTailSummaries(tailSummaryStates, siteWeights);
   mHmm.setSiteBins(siteBins);
   mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA, hapIndicesB, mHmm.getData().sites,
                                                mHmm.getDecodingQuantities().states, perPairPosteriors, sumOfPosteriors,
                                                perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-                                               siteBins, tailTimes, tailStates, quantiles);
+                                               siteBins, tailTimes, tailStates, quantiles, tailSummaryTimes,
+                                               tailSummaryStates, siteWeights);
   mHmm.setStorePerPairPosteriorMean(perPairPosteriorMeans);
   mHmm.setStorePerPairMap(perPairMAPs);
   mHmm.setStorePerPairPosterior(perPairPosteriors);
@@ -64,7 +71,8 @@ void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std:
 void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
                        bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
                        bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
-                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles)
+                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
+                       const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights)
 {
   if (hapIdsA.size() != hapIdsB.size()) {
     throw std::runtime_error("Vector of A IDs (" + std::to_string(hapIdsA.size()) +
@@ -79,7 +87,7 @@ void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vecto
     b[i] = dipToHapId(getIndIdxFromIdString(ids, strB), hapB);
   }
   decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-              siteBins, tailTimes, quantiles);
+              siteBins, tailTimes, quantiles, tailSummaryTimes, siteWeights);
 }
 
 std::vector<int> ASMC::tailStatesOf(const std::vector<float>& tailTimes)

@@ -22,15 +22,19 @@ public:
                    bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
                    bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
                    const std::vector<int>& siteBins = {}, const std::vector<float>& tailTimes = {},
-                   const std::vector<float>& quantiles = {});
+                   const std::vector<float>& quantiles = {}, const std::vector<float>& tailSummaryTimes = {},
+                   const std::vector<float>& siteWeights = {});
   // ASMC.cpp:80-100; minima: without the rows; siteBins: edges of the per-pair summaries over bins of sites, {} = none;
   // tailTimes (generations) / quantiles: per pair and site the posterior probability of a coalescence more recent than
-  // each time and the posterior quantile states, {} = none
+  // each time and the posterior quantile states, {} = none; tailSummaryTimes (generations): the same tail probabilities
+  // not stored but summed over the pairs per site and, with siteBins, reduced per pair over the bins -- the mean, and with
+  // siteWeights ([sites]) the weighted sum --, {} = none
   void decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
                    bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
                    bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
                    const std::vector<int>& siteBins = {}, const std::vector<float>& tailTimes = {},
-                   const std::vector<float>& quantiles = {}); // ASMC.cpp:102-128
+                   const std::vector<float>& quantiles = {}, const std::vector<float>& tailSummaryTimes = {},
+                   const std::vector<float>& siteWeights = {}); // ASMC.cpp:102-128
   // the state cut of a tail time T (generations): #{k : discretization[k] < (float)T}, the loop of
   // HMM::getStateThreshold (HMM.cpp:504-513); throws for a time no interval starts below
   std::vector<int> tailStatesOf(const std::vector<float>& tailTimes);

@@ -113,7 +113,10 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
                                          long sites, long states, bool fullPosteriors, bool sumOfPost,
                                          bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps,
                                          const std::vector<int>& siteBins, const std::vector<float>& tailTimesIn,
-                                         const std::vector<int>& tailStatesIn, const std::vector<float>& quantilesIn)
+                                         const std::vector<int>& tailStatesIn, const std::vector<float>& quantilesIn,
+                                         const std::vector<float>& tailSummaryTimesIn,
+                                         const std::vector<int>& tailSummaryStatesIn,
+                                         const std::vector<float>& siteWeightsIn)
 {
   numWritten = 0;
   numPairs = static_cast<long>(hapsA.size());
@@ -174,6 +177,13 @@ void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA
   const size_t rowCells = static_cast<size_t>(numPairs) * static_cast<size_t>(sites);
   perPairTailProbabilities.assign(tailStates.size() * rowCells, 0.f);
   perPairQuantileStates.assign(quantiles.size() * rowCells, 0);
+  // the tail probabilities reduced over pairs, [tails][sites], and over bins, [tails][pairs][bins]
+  tailSummaryTimes = tailSummaryTimesIn;
+  tailSummaryStates = tailSummaryStatesIn;
+  siteWeights = siteWeightsIn;
+  sumOfTailProbabilities.assign(tailSummaryStates.size() * static_cast<size_t>(sites), 0.0);
+  binTailMeans.assign(tailSummaryStates.size() * cells, 0.f);
+  binTailLengths.assign(siteWeights.empty() ? 0 : tailSummaryStates.size() * cells, 0.f);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()
@@ -701,6 +711,37 @@ void HMM::setPosteriorCdf(const std::vector<int>& tailStates, const std::vector<
   updateOutputStructures();
 }
 
+void HMM::setTailSummaries(const std::vector<int>& tailStates, const std::vector<float>& siteWeights)
+{
+  // (the messages of fsmc_decode_pair_tail_summaries)
+  if (tailStates.size() > 8) {
+    throw std::runtime_error("at most 8 tail states a call");
+  }
+  for (const int c : tailStates) {
+    if (c < 1 || c > static_cast<int>(mDq.states)) {
+      throw std::runtime_error("tail state " + std::to_string(c) + " outside [1, K]");
+    }
+  }
+  if (!siteWeights.empty()) {
+    if (tailStates.empty()) {
+      throw std::runtime_error("site weights need tail summary times");
+    }
+    if (siteWeights.size() != static_cast<size_t>(mData.sites)) {
+      throw std::runtime_error("site weights: " + std::to_string(siteWeights.size()) + " values for " +
+                               std::to_string(mData.sites) + " sites");
+    }
+    for (size_t t = 0; t < siteWeights.size(); ++t) {
+      if (!std::isfinite(siteWeights[t])) {
+        throw std::runtime_error("site weight " + std::to_string(t) + " is not finite");
+      }
+    }
+  }
+  flush(); // (what is queued was decoded under the old setting)
+  mTailSummaryStates = tailStates;
+  mSiteWeights = siteWeights;
+  updateOutputStructures();
+}
+
 void HMM::setWritePerPairPosteriorMean(bool v)
 {
   flush(); // (what is queued was decoded under the old setting in the reference)
@@ -1035,8 +1076,9 @@ void HMM::flush()
   const bool minMeanOnDevice = mStoreMinMean && !mStoreMean, minMapOnDevice = mStoreMinMap && !mStoreMap;
   const bool binsOnDevice = !mSiteBins.empty();
   const bool cdfOnDevice = !mTailStates.empty() || !mQuantiles.empty();
+  const bool tailSummariesOnDevice = !mTailSummaryStates.empty();
   const bool storeAny = mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice ||
-                        minMapOnDevice || binsOnDevice || cdfOnDevice;
+                        minMapOnDevice || binsOnDevice || cdfOnDevice || tailSummariesOnDevice;
   if (!mParams.FastSMC && (storeAny || writeFiles)) {
     // writePerPairOutput (HMM.cpp:1360-1458)
     const size_t S = static_cast<size_t>(mData.sites);
@@ -1108,6 +1150,39 @@ void HMM::flush()
             fsmc_decode_pair_cdf(mCtx, mModel, mTailStates.data(), mTailStates.size(), tailRows.data(), mQuantiles.data(),
                                  mQuantiles.size(), quantileRows.data()),
             "fsmc_decode_pair_cdf");
+    }
+    if (tailSummariesOnDevice) {
+      // the tail probabilities summed over the pairs -- the fp64 chain of the whole call, flush after flush -- and, with
+      // site bins, reduced per pair over the bins at the pairs written so far: 8 * S bytes a cut cross the bus each way
+      // and 4 bytes a pair, cut, bin and output come back, the tail rows stay on the device
+      const size_t nT = mTailSummaryStates.size();
+      const size_t nBins = mSiteBins.empty() ? 0 : mSiteBins.size() - 1;
+      const bool lengths = nBins > 0 && !mSiteWeights.empty();
+      const size_t cells = static_cast<size_t>(R.numPairs) * nBins;
+      if (R.tailSummaryStates != mTailSummaryStates || R.sumOfTailProbabilities.size() != nT * S ||
+          R.binTailMeans.size() != nT * cells || (lengths && R.binTailLengths.size() != nT * cells) ||
+          (nBins > 0 && R.binEdges != mSiteBins)) {
+        throw std::runtime_error("the return structure was not initialised for the tail summaries asked for");
+      }
+      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
+      // the ABI's bin outputs are [cut][pairs of the work list][bins]: a flush's cells pass through a buffer of that
+      // shape into the call's [cut][numPairs][bins] at the pairs written so far
+      std::vector<float> means(nT * nPairs * nBins), lens(lengths ? nT * nPairs * nBins : 0);
+      check(mCtx,
+            fsmc_decode_pair_tail_summaries(mCtx, mModel, mTailSummaryStates.data(), nT, R.sumOfTailProbabilities.data(),
+                                            nBins ? mSiteBins.data() : nullptr, nBins, nBins ? means.data() : nullptr,
+                                            lengths ? mSiteWeights.data() : nullptr, lengths ? lens.data() : nullptr),
+            "fsmc_decode_pair_tail_summaries");
+      for (size_t j = 0; nBins > 0 && j < nT; ++j) {
+        std::copy(means.begin() + static_cast<std::ptrdiff_t>(j * nPairs * nBins),
+                  means.begin() + static_cast<std::ptrdiff_t>((j + 1) * nPairs * nBins),
+                  R.binTailMeans.begin() + static_cast<std::ptrdiff_t>(j * cells + base * nBins));
+        if (lengths) {
+          std::copy(lens.begin() + static_cast<std::ptrdiff_t>(j * nPairs * nBins),
+                    lens.begin() + static_cast<std::ptrdiff_t>((j + 1) * nPairs * nBins),
+                    R.binTailLengths.begin() + static_cast<std::ptrdiff_t>(j * cells + base * nBins));
+        }
+      }
     }
     if (mStorePosterior || mStoreSumOfPosterior) {
       // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]

@@ -66,13 +66,22 @@ struct DecodePairsReturnStruct {
   std::vector<float> quantiles;
   std::vector<float> perPairTailProbabilities;
   std::vector<int> perPairQuantileStates;
+  // the tail probabilities reduced on the device, their rows not stored (fsmc_decode_pair_tail_summaries): per site the
+  // fp64 sum over the pairs in pair order, [tails][sites]; per pair the mean over each bin of binEdges and, with site
+  // weights, the weighted sum over it, [tails][pairs][bins] (empty without bins / without weights)
+  std::vector<float> tailSummaryTimes;
+  std::vector<int> tailSummaryStates;
+  std::vector<float> siteWeights;
+  std::vector<double> sumOfTailProbabilities;
+  std::vector<float> binTailMeans, binTailLengths;
   size_t numWritten = 0;
 
   void initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>& hapsB, long sites,
                   long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps,
                   bool minMeans = false, bool minMaps = false, const std::vector<int>& siteBins = {},
                   const std::vector<float>& tailTimesIn = {}, const std::vector<int>& tailStatesIn = {},
-                  const std::vector<float>& quantilesIn = {});
+                  const std::vector<float>& quantilesIn = {}, const std::vector<float>& tailSummaryTimesIn = {},
+                  const std::vector<int>& tailSummaryStatesIn = {}, const std::vector<float>& siteWeightsIn = {});
   void finaliseCalculations();
 };
 
@@ -163,6 +172,12 @@ public:
   // per_pair_tail_probabilities / per_pair_quantile_states (fsmc_decode_pair_cdf); both empty turns this off.  Throws
   // what the ABI would refuse: more than 8 of either kind, a cut outside [1, states], a quantile outside (0, 1].
   void setPosteriorCdf(const std::vector<int>& tailStates, const std::vector<float>& quantiles);
+  // the same tail probabilities, not stored but reduced on the device (fsmc_decode_pair_tail_summaries): per site their
+  // fp64 sum over the decoded pairs into sum_of_tail_probabilities, and with site bins (setSiteBins) per pair their mean
+  // over each bin into per_pair_bin_tail_means and, with siteWeights ([sites], finite), their weighted sum over it into
+  // per_pair_bin_tail_lengths.  Empty tailStates turns this off.  Throws what the ABI would refuse: more than 8 cuts, a
+  // cut outside [1, states], weights that are not one a site or not finite; and weights without cuts.
+  void setTailSummaries(const std::vector<int>& tailStates, const std::vector<float>& siteWeights = {});
   // HMM.hpp:287,293: per-pair posterior means / MAP states of every decoded pair as text, one row per pair, to
   // <outFileRoot>.perPairPosteriorMeans.gz / .perPairMAP.gz (ASMC mode; opened by resetDecoding, HMM.cpp:259-271,
   // written batch by batch, HMM.cpp:1412-1420, closed by finishDecoding, HMM.cpp:515-524)
@@ -262,6 +277,8 @@ private:
   std::vector<int> mSiteBins; // bin edges of the per-pair summaries, empty = none
   std::vector<int> mTailStates;  // state cuts of the per-pair tail probabilities, empty = none
   std::vector<float> mQuantiles; // quantiles of the per-pair quantile states, empty = none
+  std::vector<int> mTailSummaryStates; // state cuts of the tail probabilities reduced over pairs and bins, empty = none
+  std::vector<float> mSiteWeights;     // weights of per_pair_bin_tail_lengths, empty = none
   bool mWriteMean = false, mWriteMap = false;
   gzFile mMeanFile = nullptr, mMapFile = nullptr;
   int mMeanFd = -1, mMapFd = -1; // their descriptors (blocks of rows go out as gzip members of their own)

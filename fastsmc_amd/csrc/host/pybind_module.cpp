@@ -105,6 +105,16 @@ py::array_t<T> cdfRows(const std::vector<T>& v, size_t nOut, const DecodePairsRe
                         static_cast<py::ssize_t>(r.numSites)});
 }
 
+// a [tails][pairs][bins] stack of the return structure's tail summaries over site bins ([0][0][0] without them)
+py::array_t<float> tailBinStack(const std::vector<float>& v, const DecodePairsReturnStruct& r)
+{
+  if (v.empty()) {
+    return py::array_t<float>(std::vector<py::ssize_t>{0, 0, 0});
+  }
+  return toArray<float>(v, {static_cast<py::ssize_t>(r.tailSummaryStates.size()), static_cast<py::ssize_t>(r.numPairs),
+                            static_cast<py::ssize_t>(r.binEdges.size() - 1)});
+}
+
 PYBIND11_MODULE(_pyasmc, m)
 {
   m.doc() = "MI355X-native drop-in for the decode path of PalamaraLab/FastSMC (pyASMC-compatible names)";
@@ -128,6 +138,7 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_readwrite("siteWasFlippedDuringFolding", &DecodingReturnValues::siteWasFlippedDuringFolding);
 
   py::class_<DecodePairsReturnStruct>(m, "DecodePairsReturnStruct")
+      .def(py::init<>(), "an empty structure: what every field holds before a decode and whenever it was not asked for")
       .def_readwrite("per_pair_indices", &DecodePairsReturnStruct::perPairIndices)
       .def_property_readonly("per_pair_posteriors",
                              [](const DecodePairsReturnStruct& r) {
@@ -163,7 +174,24 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("tail_states", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.tailStates, {static_cast<py::ssize_t>(r.tailStates.size())}); })
       .def_property_readonly("quantiles", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.quantiles, {static_cast<py::ssize_t>(r.quantiles.size())}); })
       .def_property_readonly("per_pair_tail_probabilities", [](const DecodePairsReturnStruct& r) { return cdfRows<float>(r.perPairTailProbabilities, r.tailStates.size(), r); })
-      .def_property_readonly("per_pair_quantile_states", [](const DecodePairsReturnStruct& r) { return cdfRows<int>(r.perPairQuantileStates, r.quantiles.size(), r); });
+      .def_property_readonly("per_pair_quantile_states", [](const DecodePairsReturnStruct& r) { return cdfRows<int>(r.perPairQuantileStates, r.quantiles.size(), r); })
+      // the tail probabilities of tail_summary_states[j] (tail_summary_times[j]: the generations asked for), their rows
+      // not stored: summed over the pairs in pair order in fp64, [tails][sites]; per pair the mean over each site bin and,
+      // with site_weights, the weighted sum over it, [tails][pairs][bins]; empty where not asked for
+      .def_property_readonly("tail_summary_times", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.tailSummaryTimes, {static_cast<py::ssize_t>(r.tailSummaryTimes.size())}); })
+      .def_property_readonly("tail_summary_states", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.tailSummaryStates, {static_cast<py::ssize_t>(r.tailSummaryStates.size())}); })
+      .def_property_readonly("site_weights", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.siteWeights, {static_cast<py::ssize_t>(r.siteWeights.size())}); })
+      .def_property_readonly("sum_of_tail_probabilities",
+                             [](const DecodePairsReturnStruct& r) {
+                               if (r.sumOfTailProbabilities.empty()) {
+                                 return py::array_t<double>(std::vector<py::ssize_t>{0, 0});
+                               }
+                               return toArray<double>(r.sumOfTailProbabilities,
+                                                      {static_cast<py::ssize_t>(r.tailSummaryStates.size()),
+                                                       static_cast<py::ssize_t>(r.numSites)});
+                             })
+      .def_property_readonly("per_pair_bin_tail_means", [](const DecodePairsReturnStruct& r) { return tailBinStack(r.binTailMeans, r); })
+      .def_property_readonly("per_pair_bin_tail_lengths", [](const DecodePairsReturnStruct& r) { return tailBinStack(r.binTailLengths, r); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -428,6 +456,10 @@ PYBIND11_MODULE(_pyasmc, m)
            "per pair and site the posterior mass of the first tail_states[j] states (1 <= cut <= states) and the smallest "
            "state at which the running sum over the states reaches quantiles[j] (0 < q <= 1), computed on the device; up "
            "to 8 of each, two empty lists turn this off")
+      .def("setTailSummaries", &HMM::setTailSummaries, "tail_states"_a, "site_weights"_a = std::vector<float>{},
+           "the tail probabilities of tail_states[j] (1 <= cut <= states, up to 8) reduced on the device, their rows not "
+           "stored: summed over the decoded pairs per site (fp64, pair order) and, with site bins, per pair the mean over "
+           "each bin and, with site_weights ([sites], finite), the weighted sum over it; an empty list turns this off")
       .def("getExpectedCoalTimes", &HMM::getExpectedCoalTimes,
            "expected coalescence times the per-pair posterior means use: the intervals file's second column when "
            "DecodingParams.expectedCoalTimesFile names one, else the decoding quantities' (HMM.cpp:1736-1748)")
@@ -568,11 +600,13 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("decodePairs",
            py::overload_cast<const std::vector<unsigned long>&, const std::vector<unsigned long>&, bool, bool, bool,
                              bool, bool, bool, const std::vector<int>&, const std::vector<float>&,
+                             const std::vector<float>&, const std::vector<float>&,
                              const std::vector<float>&>(&ASMC::decodePairs),
            "hap_indices_a"_a, "hap_indices_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
            "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
-           "quantiles"_a = std::vector<float>{},
+           "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
+           "site_weights"_a = std::vector<float>{},
            "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
            "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
            "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
@@ -586,15 +620,23 @@ PYBIND11_MODULE(_pyasmc, m)
            "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
            "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
            "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
-           "each flush.")
+           "each flush.  tail_summary_times (generations, up to 8, cut like tail_times and reported in "
+           "tail_summary_states): the same tail probabilities, their rows NOT stored but reduced on the device: "
+           "sum_of_tail_probabilities ([tails][sites] float64: the sum over the pairs in pair order, one fp64 add a pair) "
+           "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
+           "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
+           "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
+           "in that order).")
       .def("decodePairs",
            py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool,
                              bool, bool, const std::vector<int>&, const std::vector<float>&,
+                             const std::vector<float>&, const std::vector<float>&,
                              const std::vector<float>&>(&ASMC::decodePairs),
            "hap_ids_a"_a, "hap_ids_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
            "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
            "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
-           "quantiles"_a = std::vector<float>{},
+           "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
+           "site_weights"_a = std::vector<float>{},
            "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
            "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
            "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
@@ -608,7 +650,13 @@ PYBIND11_MODULE(_pyasmc, m)
            "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
            "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
            "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
-           "each flush.")
+           "each flush.  tail_summary_times (generations, up to 8, cut like tail_times and reported in "
+           "tail_summary_states): the same tail probabilities, their rows NOT stored but reduced on the device: "
+           "sum_of_tail_probabilities ([tails][sites] float64: the sum over the pairs in pair order, one fp64 add a pair) "
+           "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
+           "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
+           "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
+           "in that order).")
       .def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

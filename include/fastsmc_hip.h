@@ -27,6 +27,8 @@
  *   fsmc_decode_pair_cdf    <- decodeBatch, then per pair and site the running sum of the posterior over the states: tail
  *                             probabilities and quantile states (none: the reference's callers do this in numpy on
  *                             perPairPosteriors; the sum's order is the IBD scan's, HMM.cpp:1207-1224)
+ *   fsmc_decode_pair_tail_summaries <- the tail probabilities of fsmc_decode_pair_cdf, summed over the pairs per site and
+ *                             reduced over bins of sites per pair (none: the reference's callers do this in numpy)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -213,6 +215,11 @@ int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices);
  * 64 * S * 4 bytes a group and output).  Results do not depend on it. */
 int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_tail_summaries.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of staging, tail rows and binned outputs (64 * K * S * 4 bytes a group
+ * of staging plus 64 * 4 bytes * (S + n_bins a bin output) a group and cut).  Results do not depend on it. */
+int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -387,6 +394,36 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
 int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
                          float* const* tail_rows, const float* quantiles, size_t n_quantiles,
                          int32_t* const* quantile_rows);
+
+/* The tail probabilities of fsmc_decode_pair_cdf reduced over the pairs of the resident work list and over bins of sites,
+ * without the [n_pairs][S] tail rows leaving the device.  tail[j][i][t] is exactly tail_rows[j][i * S + t] of
+ * fsmc_decode_pair_cdf: the fp32 running sum cdf[c - 1] of pair i's posterior at site t, ascending k, one fp32 add a
+ * state, for the cut c = tail_states[j], 1 <= c <= K.  Up to 8 cuts a call, one at least, duplicates allowed.  Outputs
+ * (any may be NULL, one at least):
+ *   tail_sum: [n_tail][S] float64, read AND written: tail_sum[j * S + t] = ((tail_sum[j * S + t] + (double)tail[j][0][t])
+ *     + (double)tail[j][1][t]) + ..., one fp64 add a pair, in work-list order, onto what the caller passes in (pass
+ *     zeros to start a sum).  Several calls over consecutive parts of a pair list, each continuing the array of the one
+ *     before, give the bits of one call over the whole list; so do the slices of one call.
+ *   bin_tail_mean: [n_tail][n_pairs][n_bins] float32: the mean of tail[j][i][t] over bin b, sites [bin_edges[b],
+ *     bin_edges[b + 1]), n of them, in the defined fp64 order of fsmc_decode_pair_bins' bin_mean: slot s (0 <= s < 64)
+ *     starts at +0.0 and adds (double)tail[j][i][t] for t = bin_edges[b] + s, + 64, ... in ascending order; then for
+ *     stride = 32, 16, 8, 4, 2, 1: a[s] = a[s] + a[s + stride] for s < stride; the result is (float)(a[0] / (double)n).
+ *   bin_tail_length: the same shape: the same slots and the same tree over (double)tail[j][i][t] *
+ *     (double)site_weights[t] (the fp64 product of two floats is exact, so a fused multiply-add gives the same bits);
+ *     the result is (float)a[0], no divide.  With site_weights[t] the centimorgans site t stands for this is the pair's
+ *     expected length below the cut in the bin.
+ * bin_edges: n_bins + 1 int32 values under the rules of fsmc_decode_pair_bins (strictly ascending, within [0, S]; sites
+ * outside [bin_edges[0], bin_edges[n_bins]) belong to no bin); read only with a bin output.  site_weights: [S] finite
+ * floats; read only with bin_tail_length.  The work list goes through the device in slices of groups
+ * (fsmc_ctx_set_pair_tail_slice); 8 * S bytes a cut cross the bus each way for tail_sum and 4 * n_bins bytes a pair, cut
+ * and bin output come back.  fsmc_last_kernel_ms spans every decode and every reduction of the call (with bin outputs
+ * and several slices also the copies of their cells in between).  FSMC_EINVAL: no output; no cut or more than 8; a cut
+ * outside [1, K]; a bin output without edges, n_bins == 0, edges not strictly ascending or outside [0, S];
+ * bin_tail_length without site_weights; a weight that is not finite; a group that is not the whole sequence (from = 0,
+ * to = S). */
+int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
+                                    double* tail_sum, const int32_t* bin_edges, size_t n_bins, float* bin_tail_mean,
+                                    const float* site_weights, float* bin_tail_length);
 
 /* augmentSumOverPairs: sums[S][K] += sum over the pairs of the work list of the posterior
  * (and the 00/01/11 split when the pointers are non-NULL).  Whole-sequence groups only. */

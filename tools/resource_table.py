@@ -2,8 +2,8 @@
 """Per-kernel resource table of the HIP library as the compiler reports it (-Rpass-analysis=kernel-resource-usage): VGPRs,
 AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, LDS bytes per workgroup, waves per SIMD -- one row per
 instantiation of every family member and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
-transposition, the per-pair minima and their combine step, the per-pair site bins, the per-pair tails and quantile states), stamped with the hash of the sources they were compiled from.
-Usage: tools/resource_table.py [out.json]   (default profiles/r09_kernel_resources.json; no GPU needed)"""
+transposition, the per-pair minima and their combine step, the per-pair site bins, the per-pair tails and quantile states, the tail summaries), stamped with the hash of the sources they were compiled from.
+Usage: tools/resource_table.py [out.json]   (default profiles/r10_kernel_resources.json; no GPU needed)"""
 import json
 import os
 import re
@@ -46,14 +46,14 @@ def member(define, src="fsmc_inst.hip"):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r09_kernel_resources.json")
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r10_kernel_resources.json")
     # every member the build compiles (fastsmc_amd/build.py): padded and exact lane-per-pair members, wave-group members
     defs = ([f"-DFSMC_INSTANCE_KT={k}" for k in KT_MEMBERS + EXACT_MEMBERS]
             + [f"-DFSMC_INSTANCE_W2={kh} -DFSMC_INSTANCE_NW={nw}" for kh, nw in W2_MEMBERS])
     with ThreadPoolExecutor(max_workers=min(len(defs), os.cpu_count() or 1)) as ex:
         rows = [r for rs in ex.map(member, defs) for r in rs]
     # the kernels that live beside the host code (the identification kernels of the same unit are not decode kernels)
-    rows += [r for r in member("", "fsmc_capi.hip") if any(k in r["mangled"] for k in ("add_planes", "pair_posteriors", "pair_minima", "pair_bins", "pair_cdf"))]
+    rows += [r for r in member("", "fsmc_capi.hip") if any(k in r["mangled"] for k in ("add_planes", "pair_posteriors", "pair_minima", "pair_bins", "pair_cdf", "pair_tail"))]
     for r, name in zip(rows, demangle([r["mangled"] for r in rows])):
         r["kernel"] = re.sub(r"^fsmc::", "", re.sub(r"\([^()]*\)$", "", name).replace("void fsmc::", ""))
         del r["mangled"]
