@@ -62,6 +62,10 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+
+// The entry points that send the work list through the device in slices of groups (planSlices): each has its own
+// slice setting and its own count of the last call's slices.
+enum PairSlicing { kSlicePosteriors, kSliceMinima, kSliceBins, kSliceCdf, kSliceTail, kPairSlicings };
 } // namespace
 
 struct fsmc_ctx {
@@ -130,36 +134,22 @@ struct fsmc_ctx {
   hipEvent_t evFork = nullptr, evJoin = nullptr;
   DevBuf wsSide;
 
-  // fsmc_decode_pair_posteriors: the work list goes through the device in slices of groups
-  uint32_t ppSlice = 0;     // groups a slice, 0 = automatic
-  int lastPpSlices = 0;     // slices of the last call
-  DevBuf ppStage;           // the dump of one slice, [group][site][k][lane]
-  DevBuf ppRows;            // the rows of one slice, [pair][K][S]
-  DevBuf ppAcc;             // [expCoal K floats][sum K * S floats]
-  hipStream_t copyStream = nullptr; // the rows leave on this one, through the two pinned buffers
+  // The fsmc_decode_pair_* entry points: the work list goes through the device in slices of groups (planSlices)
+  struct {
+    uint32_t groups = 0; // groups a slice, 0 = automatic
+    int last = 0;        // slices of the last call
+  } pairSlices[kPairSlicings];
+  DevBuf ppStage;           // a slice's decode: the dump, [group][site][k][lane], or its mean / MAP rows, [pair][S]
+  DevBuf ppRows;            // the rows a slice's reduction leaves: [pair][K][S] (posteriors), [output][pair][S] (cdf, tail)
+  DevBuf ppAcc;             // posteriors: [expCoal K floats][sum K * S floats]
+  hipStream_t copyStream = nullptr; // the rows leave on this one, through the two pinned buffers (drainRows)
   void* ppPinned[2] = {nullptr, nullptr};
   size_t ppPinnedBytes = 0; // size of each
   hipEvent_t evRows = nullptr, evCopied[2] = {nullptr, nullptr};
-
-  // fsmc_decode_pair_minima: slices of groups as above; the slice's mean / MAP rows share ppStage
-  uint32_t pmSlice = 0;     // groups a slice, 0 = automatic
-  int lastPmSlices = 0;     // slices of the last call
-  DevBuf pmAcc;             // [expCoal KP floats][the carried state, 4 x S][the ranges' partials, 4 x nRanges x S]
-
-  // fsmc_decode_pair_bins: slices of groups as above, the rows in ppStage
-  uint32_t pbSlice = 0;     // groups a slice, 0 = automatic
-  int lastPbSlices = 0;     // slices of the last call
-  DevBuf pbAcc;             // [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
-
-  // fsmc_decode_pair_cdf: slices of groups as for the posterior tables -- the dump in ppStage, the rows in ppRows
-  uint32_t pcSlice = 0;     // groups a slice, 0 = automatic
-  int lastPcSlices = 0;     // slices of the last call
-  DevBuf pcSpec;            // the call's outputs, PairCdfSpec each
-
-  // fsmc_decode_pair_tail_summaries: slices of groups as for fsmc_decode_pair_cdf, whose rows stay in ppRows
-  uint32_t ptSlice = 0;     // groups a slice, 0 = automatic
-  int lastPtSlices = 0;     // slices of the last call
-  DevBuf ptAcc;             // [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
+  DevBuf pmAcc;             // minima: [expCoal KP floats][the carried state, 4 x S][the ranges' partials, 4 x nRanges x S]
+  DevBuf pbAcc;             // bins: [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
+  DevBuf pcSpec;            // cdf, tail summaries: the call's outputs, PairCdfSpec each
+  DevBuf ptAcc;             // tail summaries: [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
@@ -230,6 +220,15 @@ int fail(fsmc_ctx* ctx, int code, const std::string& msg)
     hipError_t e_ = (call);                                                                                            \
     if (e_ != hipSuccess) {                                                                                            \
       return fail((ctx), FSMC_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));                                \
+    }                                                                                                                  \
+  } while (0)
+
+// `call` gives FSMC_OK or the caller returns what it gave (the error text is set where it failed).
+#define FSMC_TRY(call)                                                                                                 \
+  do {                                                                                                                 \
+    const int rc_ = (call);                                                                                            \
+    if (rc_ != FSMC_OK) {                                                                                              \
+      return rc_;                                                                                                      \
     }                                                                                                                  \
   } while (0)
 
@@ -1068,6 +1067,232 @@ int prepareDecode(fsmc_ctx* ctx, const fsmc_model* m, int mode, uint32_t wantStr
   return FSMC_OK;
 }
 
+int setPairSlice(fsmc_ctx* ctx, PairSlicing kind, uint32_t groups)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  ctx->pairSlices[kind].groups = groups;
+  return FSMC_OK;
+}
+
+int lastPairSlices(const fsmc_ctx* ctx, PairSlicing kind, int32_t* slices)
+{
+  if (!ctx || !slices) {
+    return FSMC_EINVAL;
+  }
+  *slices = ctx->pairSlices[kind].last;
+  return FSMC_OK;
+}
+
+// The work list in slices of groups, as the fsmc_decode_pair_* entry points send it through the device: the launch of a
+// slice sees the slice as its whole group list (p.groups points at the slice's first group of the resident list).
+struct WorkSlices {
+  const fsmc_ctx* ctx = nullptr;
+  size_t slice = 0;         // groups a slice (the last one may have fewer)
+  size_t nSlices = 0;
+  size_t slicePairsMax = 0; // pairs of the largest slice
+  LaunchPlan plan;
+  // per-pair mode (perPairSetup): the slice's mean / MAP rows in ppStage
+  float* stageMean = nullptr;
+  int* stageMap = nullptr;
+  // what the setups upload from: alive until the entry point synchronises the stream
+  std::vector<size_t> hOffsets;
+  std::vector<float> hCoal;
+
+  size_t firstGroup(size_t sl) const { return sl * slice; }
+  size_t groups(size_t sl) const { return std::min(slice, ctx->nGroups - sl * slice); }
+  size_t firstPair(size_t sl) const { return ctx->hGroups[firstGroup(sl)].first_pair; }
+  size_t pairs(size_t sl) const
+  {
+    const fsmc_group& last = ctx->hGroups[firstGroup(sl) + groups(sl) - 1];
+    return (size_t)last.first_pair + last.n_pairs - firstPair(sl);
+  }
+};
+
+// The sliced entry points decode whole sequences only.  (A check of its own: each entry point keeps it where it
+// always fired among its argument checks.)
+int checkWholeSequence(fsmc_ctx* ctx, const fsmc_model* m, const char* what)
+{
+  for (const fsmc_group& g : ctx->hGroups) {
+    if (g.from != 0 || g.to != (uint32_t)m->S) {
+      return fail(ctx, FSMC_EINVAL, std::string(what) + " need whole-sequence groups (HMM.cpp:1378)");
+    }
+  }
+  return FSMC_OK;
+}
+
+// The slices of a call and its decode plan, `mode` kModeDump or kModePerPair.  The slice is the caller's setting, or
+// what stagingLimit holds of `groupBytes` a group, of half the room the card has free with the `held` bytes this entry
+// point's buffers hold already counted as free -- the decode's workspace is allocated after this -- and `sliceMost`
+// groups at the most.  One wave per window: planned from the first slice's groups; two waves: a workgroup for each group
+// of a slice.
+int planSlices(fsmc_ctx* ctx, const fsmc_model* m, int mode, PairSlicing kind, uint64_t held, size_t groupBytes,
+               WorkSlices& ws, size_t sliceMost = SIZE_MAX)
+{
+  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  size_t slice = ctx->pairSlices[kind].groups;
+  if (slice == 0) {
+    slice = (size_t)(stagingLimit(ctx, held, 2) / groupBytes);
+  }
+  ws.ctx = ctx;
+  ws.slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, sliceMost}));
+  ws.nSlices = (ctx->nGroups + ws.slice - 1) / ws.slice;
+  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)ws.slice);
+  FSMC_TRY(prepareDecode(ctx, m, mode, ctx->betaStride, first, ws.slice, 0, ws.plan));
+  ws.slicePairsMax = 0;
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    ws.slicePairsMax = std::max(ws.slicePairsMax, ws.pairs(sl));
+  }
+  return FSMC_OK;
+}
+
+// Dump mode: a slice's groups land in ppStage one after the other, [group][site][k][lane]; the offsets (which count
+// from the slice's start) go to aux.  Both buffers are the entry point's to `ensure` before this.
+int dumpSetup(fsmc_ctx* ctx, const fsmc_model* m, WorkSlices& ws, KParams& p)
+{
+  ws.hOffsets.resize(ws.slice);
+  for (size_t i = 0; i < ws.slice; ++i) {
+    ws.hOffsets[i] = i * (size_t)kWave * (size_t)m->K * (size_t)m->S;
+  }
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, ws.hOffsets.data(), ws.slice * sizeof(size_t), hipMemcpyHostToDevice,
+                               ctx->stream));
+  fillParams(ctx, m, ws.plan, 0, p);
+  p.dumpOut = (float*)ctx->ppStage.p;
+  p.dumpOffsets = (const size_t*)ctx->aux.p;
+  return FSMC_OK;
+}
+
+// The expected coalescence times as the per-pair consumers read them: a row padded to KP floats, to `dst` on the device.
+// `keep` holds the padded row until the caller synchronises the stream.
+int uploadExpCoal(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, void* dst, std::vector<float>& keep)
+{
+  keep.assign((size_t)m->KP, 0.f);
+  std::memcpy(keep.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
+  FSMC_HIP(ctx, hipMemcpyAsync(dst, keep.data(), keep.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  return FSMC_OK;
+}
+
+// Per-pair mode: the expected coalescence times go to `dCoal`, and a slice's mean rows, then its MAP rows, [pair][S]
+// each, take ppStage from its start (the entry point's to `ensure` before this).
+int perPairSetup(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, void* dCoal, bool wantMean,
+                 bool wantMap, WorkSlices& ws, KParams& p)
+{
+  FSMC_TRY(uploadExpCoal(ctx, m, exp_coal_times, dCoal, ws.hCoal));
+  ws.stageMean = wantMean ? (float*)ctx->ppStage.p : nullptr;
+  ws.stageMap = wantMap ? (int*)ctx->ppStage.p + (wantMean ? ws.slicePairsMax * (size_t)m->S : 0) : nullptr;
+  fillParams(ctx, m, ws.plan, 0, p);
+  p.expCoal = (const float*)dCoal;
+  return FSMC_OK;
+}
+
+// The decode of slice `sl`.  The per-pair consumers index rows by pair of the work list, so the launch gets the staging
+// pointers moved back by the slice's first pair: row `pair` of the work list is row `pair - firstPair` of the buffer.
+int launchSlice(fsmc_ctx* ctx, const WorkSlices& ws, size_t sl, KParams& p)
+{
+  const size_t nG = ws.groups(sl), back = ws.firstPair(sl) * (size_t)p.S;
+  p.groups = ctx->dGroups + ws.firstGroup(sl);
+  p.nGroups = (int)nG;
+  p.ppMean = ws.stageMean ? ws.stageMean - back : nullptr;
+  p.ppMap = ws.stageMap ? ws.stageMap - back : nullptr;
+  return launch(ctx, ws.plan.k, p, (int)std::min<size_t>((size_t)ws.plan.slots, nG), 0, sl != 0);
+}
+
+// The pinned buffers' size, each: 128 MiB, FSMC_DIAG_ROW_COPY_BYTES=<bytes> for less -- tests: several copies a slice
+// on a small problem.
+size_t rowCopyBytes()
+{
+  return loweredByEnv("FSMC_DIAG_ROW_COPY_BYTES", (size_t)128 << 20);
+}
+
+// Spans of device memory leave through the two pinned buffers on the copy stream (ensureRowCopies), once the work
+// stream has passed evRows: `chunk(c)` names span c of `nChunks`, none larger than a pinned buffer, and `sink(c, host)`
+// receives it -- the next copy in flight while the host empties the one before.
+struct RowChunk {
+  const void* src;
+  size_t bytes;
+};
+template <typename Chunk, typename Sink> int drainRows(fsmc_ctx* ctx, size_t nChunks, Chunk chunk, Sink sink)
+{
+  FSMC_HIP(ctx, hipStreamWaitEvent(ctx->copyStream, ctx->evRows, 0));
+  auto issue = [&](size_t c, int b) -> int {
+    const RowChunk ch = chunk(c);
+    FSMC_HIP(ctx, hipMemcpyAsync(ctx->ppPinned[b], ch.src, ch.bytes, hipMemcpyDeviceToHost, ctx->copyStream));
+    FSMC_HIP(ctx, hipEventRecord(ctx->evCopied[b], ctx->copyStream));
+    return FSMC_OK;
+  };
+  FSMC_TRY(issue(0, 0));
+  for (size_t c = 0, b = 0; c < nChunks; ++c, b ^= 1) {
+    if (c + 1 < nChunks) {
+      FSMC_TRY(issue(c + 1, (int)b ^ 1));
+    }
+    FSMC_HIP(ctx, hipEventSynchronize(ctx->evCopied[b]));
+    sink(c, (const char*)ctx->ppPinned[b]);
+  }
+  return FSMC_OK;
+}
+
+// The slice loop of the entry points whose rows leave through drainRows: slice by slice the decode, `reduce(sl)` -- the
+// launches that turn the slice's dump into rows -- and the end of the call's timed span (every decode and every
+// reduction).  `wantRows`: `drain(sl)` takes the rows of a slice to the caller while the next slice decodes, and
+// returns before that one's reduction overwrites them; the last slice's rows leave after the loop.
+template <typename Reduce, typename Drain>
+int decodeSlicesDrained(fsmc_ctx* ctx, const WorkSlices& ws, KParams& p, bool wantRows, Reduce reduce, Drain drain)
+{
+  bool pending = false; // the rows of slice sl - 1 are still on the device
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    FSMC_TRY(launchSlice(ctx, ws, sl, p));
+    if (pending) { // (while this slice decodes; ppRows is free again when it returns)
+      FSMC_TRY(drain(sl - 1));
+    }
+    FSMC_TRY(reduce(sl));
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    if (wantRows) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+    }
+    pending = wantRows && ws.pairs(sl) > 0;
+  }
+  return pending ? drain(ws.nSlices - 1) : FSMC_OK;
+}
+
+int checkBinEdges(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* edges, size_t n_bins)
+{
+  if (n_bins == 0) {
+    return fail(ctx, FSMC_EINVAL, "need one bin at least (n_bins + 1 edges)");
+  }
+  if (n_bins > (size_t)m->S) {
+    return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending: more bins than sites");
+  }
+  if (edges[0] < 0 || edges[n_bins] > m->S) {
+    return fail(ctx, FSMC_EINVAL, "bin edges must lie in [0, sites]");
+  }
+  for (size_t b = 0; b < n_bins; ++b) {
+    if (edges[b] >= edges[b + 1]) {
+      return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending");
+    }
+  }
+  return FSMC_OK;
+}
+
+// The tail states of a call, each in [1, K], as outputs of pair_cdf_kernel appended to `spec`.  `rows` (may be null):
+// the caller's matrix of each, checked first.
+constexpr size_t kMaxOfAKind = 8; // tail states, quantiles a call
+constexpr const char* kTooManyTailStates = "at most 8 tail states a call";
+int tailSpecs(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail, float* const* rows,
+              std::vector<PairCdfSpec>& spec)
+{
+  for (size_t j = 0; j < n_tail; ++j) {
+    if (rows && !rows[j]) {
+      return fail(ctx, FSMC_EINVAL, "tail_rows[" + std::to_string(j) + "] is null");
+    }
+    if (tail_states[j] < 1 || tail_states[j] > m->K) {
+      return fail(ctx, FSMC_EINVAL, "tail state " + std::to_string(tail_states[j]) + " outside [1, K]");
+    }
+    spec.push_back(PairCdfSpec{tail_states[j], 0.f});
+  }
+  return FSMC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1312,95 +1537,16 @@ int fsmc_ctx_last_resident_chunks(const fsmc_ctx* ctx, int32_t* chunks)
   return FSMC_OK;
 }
 
-int fsmc_ctx_set_pair_posterior_slice(fsmc_ctx* ctx, uint32_t groups)
-{
-  if (!ctx) {
-    return FSMC_EINVAL;
-  }
-  ctx->ppSlice = groups;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices)
-{
-  if (!ctx || !slices) {
-    return FSMC_EINVAL;
-  }
-  *slices = ctx->lastPpSlices;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_set_pair_minima_slice(fsmc_ctx* ctx, uint32_t groups)
-{
-  if (!ctx) {
-    return FSMC_EINVAL;
-  }
-  ctx->pmSlice = groups;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices)
-{
-  if (!ctx || !slices) {
-    return FSMC_EINVAL;
-  }
-  *slices = ctx->lastPmSlices;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_set_pair_bins_slice(fsmc_ctx* ctx, uint32_t groups)
-{
-  if (!ctx) {
-    return FSMC_EINVAL;
-  }
-  ctx->pbSlice = groups;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices)
-{
-  if (!ctx || !slices) {
-    return FSMC_EINVAL;
-  }
-  *slices = ctx->lastPbSlices;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups)
-{
-  if (!ctx) {
-    return FSMC_EINVAL;
-  }
-  ctx->pcSlice = groups;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices)
-{
-  if (!ctx || !slices) {
-    return FSMC_EINVAL;
-  }
-  *slices = ctx->lastPcSlices;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups)
-{
-  if (!ctx) {
-    return FSMC_EINVAL;
-  }
-  ctx->ptSlice = groups;
-  return FSMC_OK;
-}
-
-int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices)
-{
-  if (!ctx || !slices) {
-    return FSMC_EINVAL;
-  }
-  *slices = ctx->lastPtSlices;
-  return FSMC_OK;
-}
+int fsmc_ctx_set_pair_posterior_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSlicePosteriors, groups); }
+int fsmc_ctx_last_pair_posterior_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSlicePosteriors, slices); }
+int fsmc_ctx_set_pair_minima_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceMinima, groups); }
+int fsmc_ctx_last_pair_minima_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceMinima, slices); }
+int fsmc_ctx_set_pair_bins_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceBins, groups); }
+int fsmc_ctx_last_pair_bins_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceBins, slices); }
+int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceCdf, groups); }
+int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceCdf, slices); }
+int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceTail, groups); }
+int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceTail, slices); }
 
 int fsmc_ctx_last_kernel(const fsmc_ctx* ctx, int32_t* member)
 {
@@ -2273,40 +2419,27 @@ int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_
 
 int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, float* mean, int32_t* map)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   if (!exp_coal_times || (!mean && !map)) {
     return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output");
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(prepareDecode(ctx, m, kModePerPair, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan));
   const size_t n = ctx->nPairs * (size_t)m->S;
   const size_t coalBytes = (size_t)m->KP * sizeof(float);
   // layout of the staging buffer: [expCoal KP floats][mean n floats][map n ints]
-  rc = ensure(ctx, ctx->out, coalBytes + n * (sizeof(float) + sizeof(int32_t)));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  std::vector<float> coal((size_t)m->KP, 0.f);
-  std::memcpy(coal.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
+  FSMC_TRY(ensure(ctx, ctx->out, coalBytes + n * (sizeof(float) + sizeof(int32_t))));
   char* base = (char*)ctx->out.p;
-  FSMC_HIP(ctx, hipMemcpyAsync(base, coal.data(), coalBytes, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<float> coal;
+  FSMC_TRY(uploadExpCoal(ctx, m, exp_coal_times, base, coal));
   FSMC_HIP(ctx, hipMemsetAsync(base + coalBytes, 0, n * (sizeof(float) + sizeof(int32_t)), ctx->stream));
   KParams p;
   fillParams(ctx, m, plan, 0, p);
   p.expCoal = (const float*)base;
   p.ppMean = mean ? (float*)(base + coalBytes) : nullptr;
   p.ppMap = map ? (int*)(base + coalBytes + n * sizeof(float)) : nullptr;
-  rc = launch(ctx, plan.k, p, plan.slots);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(launch(ctx, plan.k, p, plan.slots));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (mean) {
     FSMC_HIP(ctx, hipMemcpy(mean, p.ppMean, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -2317,26 +2450,23 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
   return FSMC_OK;
 }
 
-// writePerPairOutput's posterior tables (HMM.cpp:1378-1392).  The work list goes through the device in slices of groups:
-// the dump consumers decode a slice into ppStage (the launch sees the slice as its whole group list: p.groups points at
-// the slice's first group of the resident list, dumpOffsets count from the slice's start), pair_posteriors_kernel turns
-// it into rows and continues the sum, and the rows of slice i leave through two pinned buffers on the copy stream
-// while slice i + 1 decodes.
+// The fsmc_decode_pair_* entry points below share one flow.  The work list goes through the device in slices of groups
+// (planSlices): the consumers of the decode kernel write a slice into ppStage -- the dump (dumpSetup) or the mean / MAP
+// rows (perPairSetup) -- the entry point's own kernels reduce it, and what is left of the slice goes to the caller before
+// the next slice overwrites it.  Rows leave through drainRows while the next slice decodes (decodeSlicesDrained); small
+// outputs by a blocking copy.  The stream is synchronised after the small uploads, whose sources are locals or the
+// caller's arrays, and at the end; the slice count of the call is recorded only then, on success.
+
+// writePerPairOutput's posterior tables (HMM.cpp:1378-1392): pair_posteriors_kernel turns a slice's dump into rows,
+// [pair][K][S], and continues the sum over pairs.
 int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times,
                                 float* const* post_rows, float* sum)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   if (!exp_coal_times || (!post_rows && !sum)) {
     return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output (rows or sum)");
   }
-  for (const fsmc_group& g : ctx->hGroups) {
-    if (g.from != 0 || g.to != (uint32_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "per-pair posteriors need whole-sequence groups (HMM.cpp:1378)");
-    }
-  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair posteriors"));
   if (post_rows) {
     for (size_t i = 0; i < ctx->nPairs; ++i) {
       if (!post_rows[i]) {
@@ -2344,70 +2474,36 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
       }
     }
   }
-  FSMC_HIP(ctx, hipSetDevice(ctx->device));
   const size_t K = (size_t)m->K, S = (size_t)m->S;
   const size_t plane = K * S;                      // floats of one pair's table, and of the sum
   const size_t groupBytes = (size_t)kWave * plane * sizeof(float); // a group in the staging buffer; its rows at most
   const bool wantRows = post_rows != nullptr;
-
-  // The slice: what stagingLimit holds of staging and rows, of half the room the card has free -- the decode's
-  // workspace is allocated after this.
-  size_t slice = ctx->ppSlice;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes, 2) / (groupBytes * (wantRows ? 2 : 1)));
-  }
-  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
-  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
-
-  // (one wave per window: planned from the first slice's groups; two waves: a workgroup for each group of a slice)
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
-  LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  size_t slicePairsMax = 0;
-  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
-    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
-    slicePairsMax = std::max<size_t>(slicePairsMax, ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs -
-                                                      ctx->hGroups[g0].first_pair);
-  }
-  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * groupBytes);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppAcc, (K + plane) * sizeof(float));
-  if (rc == FSMC_OK && wantRows) rc = ensure(ctx, ctx->ppRows, slicePairsMax * plane * sizeof(float));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  // The way out for the rows: two pinned buffers of whole pairs each -- 128 MiB, or one pair's table if that is larger.
-  const size_t rowBytes = plane * sizeof(float);
-  size_t pairsPerCopy = 1;
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kModeDump, kSlicePosteriors, ctx->ppStage.bytes + ctx->ppRows.bytes,
+                      groupBytes * (wantRows ? 2 : 1), ws));
+  FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * groupBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppAcc, (K + plane) * sizeof(float)));
   if (wantRows) {
-    constexpr size_t kPinnedBytes = 128u << 20;
-    pairsPerCopy = std::max<size_t>(1, std::min<size_t>(kPinnedBytes / rowBytes, slicePairsMax));
-    rc = ensureRowCopies(ctx, pairsPerCopy * rowBytes);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(ensure(ctx, ctx->ppRows, ws.slicePairsMax * plane * sizeof(float)));
+  }
+  // The way out for the rows: whole pairs a copy -- what a pinned buffer holds, one pair's table at least.
+  const size_t rowBytes = plane * sizeof(float);
+  const size_t pairsPerCopy = std::max<size_t>(1, std::min<size_t>(rowCopyBytes() / rowBytes, ws.slicePairsMax));
+  if (wantRows) {
+    FSMC_TRY(ensureRowCopies(ctx, pairsPerCopy * rowBytes));
   }
 
-  std::vector<size_t> offsets(slice);
-  for (size_t i = 0; i < slice; ++i) {
-    offsets[i] = i * (size_t)kWave * plane;
-  }
   float* const dCoal = (float*)ctx->ppAcc.p;
   float* const dSum = dCoal + K;
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+  KParams p;
+  FSMC_TRY(dumpSetup(ctx, m, ws, p));
   FSMC_HIP(ctx, hipMemcpyAsync(dCoal, exp_coal_times, K * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (sum) {
     FSMC_HIP(ctx, hipMemcpyAsync(dSum, sum, plane * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   }
-  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets is a local, sum and exp_coal_times the caller's)
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  KParams p;
-  fillParams(ctx, m, plan, 0, p);
-  p.dumpOut = (float*)ctx->ppStage.p;
-  p.dumpOffsets = (const size_t*)ctx->aux.p;
   PairPostParams q;
   q.stage = (const float*)ctx->ppStage.p;
   q.K = m->K;
@@ -2416,89 +2512,43 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
   q.rows = wantRows ? (float*)ctx->ppRows.p : nullptr;
   q.sum = sum ? dSum : nullptr;
   const dim3 grid((unsigned)((S + kWave - 1) / kWave), (unsigned)K);
-
-  // the rows of pairs [lo, hi) of the work list, which the device holds from row `lo - base` of ppRows on: copy by copy
-  // through the pinned buffers, the next copy in flight while the host moves the one before into the caller's rows
-  auto drain = [&](size_t base, size_t lo, size_t hi) -> int {
-    FSMC_HIP(ctx, hipStreamWaitEvent(ctx->copyStream, ctx->evRows, 0));
-    auto issue = [&](size_t c0, int b) -> int {
-      const size_t n = std::min(pairsPerCopy, hi - c0);
-      FSMC_HIP(ctx, hipMemcpyAsync(ctx->ppPinned[b], (const float*)ctx->ppRows.p + (c0 - base) * plane, n * rowBytes,
-                                   hipMemcpyDeviceToHost, ctx->copyStream));
-      FSMC_HIP(ctx, hipEventRecord(ctx->evCopied[b], ctx->copyStream));
-      return FSMC_OK;
-    };
-    int b = 0;
-    int r = issue(lo, b);
-    for (size_t c0 = lo; r == FSMC_OK && c0 < hi; c0 += pairsPerCopy, b ^= 1) {
-      const size_t n = std::min(pairsPerCopy, hi - c0);
-      if (c0 + pairsPerCopy < hi) {
-        r = issue(c0 + pairsPerCopy, b ^ 1);
-        if (r != FSMC_OK) {
-          break;
-        }
-      }
-      FSMC_HIP(ctx, hipEventSynchronize(ctx->evCopied[b]));
-      for (size_t i = 0; i < n; ++i) {
-        std::memcpy(post_rows[c0 + i], (const float*)ctx->ppPinned[b] + i * plane, rowBytes);
-      }
-    }
-    return r;
-  };
-
-  size_t prevLo = 0, prevHi = 0; // pairs of the slice whose rows are still on the device
-  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
-    const size_t nG = std::min(slice, ctx->nGroups - g0);
-    p.groups = ctx->dGroups + g0;
-    p.nGroups = (int)nG;
-    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
-    if (prevHi > prevLo) { // (while this slice decodes; ppRows is free again when it returns)
-      rc = drain(prevLo, prevLo, prevHi);
-      if (rc != FSMC_OK) {
-        return rc;
-      }
-    }
-    q.groups = ctx->dGroups + g0;
-    q.nGroups = (int)nG;
-    q.firstPair = ctx->hGroups[g0].first_pair;
+  auto reduce = [&](size_t sl) -> int {
+    q.groups = ctx->dGroups + ws.firstGroup(sl);
+    q.nGroups = (int)ws.groups(sl);
+    q.firstPair = (unsigned)ws.firstPair(sl);
     hipLaunchKernelGGL(pair_posteriors_kernel, grid, dim3(kWave), 0, ctx->stream, q);
     FSMC_HIP(ctx, hipGetLastError());
-    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every transposition)
-    if (wantRows) {
-      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
-      prevLo = ctx->hGroups[g0].first_pair;
-      prevHi = ctx->hGroups[g0 + nG - 1].first_pair + ctx->hGroups[g0 + nG - 1].n_pairs;
-    }
-  }
-  if (prevHi > prevLo) {
-    rc = drain(prevLo, prevLo, prevHi);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
-  }
+    return FSMC_OK;
+  };
+  // the slice's pairs are the rows of ppRows from its start on: runs of whole pairs, scattered to the caller's rows
+  auto drain = [&](size_t sl) -> int {
+    const size_t lo = ws.firstPair(sl), n = ws.pairs(sl);
+    auto run = [&](size_t c) { return std::min(pairsPerCopy, n - c * pairsPerCopy); };
+    return drainRows(
+        ctx, (n + pairsPerCopy - 1) / pairsPerCopy,
+        [&](size_t c) { return RowChunk{(const float*)ctx->ppRows.p + c * pairsPerCopy * plane, run(c) * rowBytes}; },
+        [&](size_t c, const char* host) {
+          for (size_t i = 0; i < run(c); ++i) {
+            std::memcpy(post_rows[lo + c * pairsPerCopy + i], host + i * rowBytes, rowBytes);
+          }
+        });
+  };
+  FSMC_TRY(decodeSlicesDrained(ctx, ws, p, wantRows, reduce, drain));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (sum) {
     FSMC_HIP(ctx, hipMemcpy(sum, dSum, plane * sizeof(float), hipMemcpyDeviceToHost));
   }
-  ctx->lastPpSlices = (int)nSlices;
+  ctx->pairSlices[kSlicePosteriors].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 
 // finaliseCalculations' column-wise min / first argmin of the per-pair means and MAPs (hmm.cpp:151-184) without the
-// rows: the per-pair consumers decode a slice of groups into ppStage (p.groups points at the slice's first group of the
-// resident list; the consumers index rows by pair of the work list, so the launch gets the staging pointers moved back
-// by the slice's first pair), pair_minima_kernel reduces the slice's rows range by range, pair_minima_combine_kernel
-// continues the chain in the device copy of the state (fsmc_pair_minima.h).
+// rows: pair_minima_kernel reduces a slice's rows range by range, pair_minima_combine_kernel continues the chain in the
+// device copy of the state (fsmc_pair_minima.h).
 int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, uint64_t pair_base,
                             float* min_mean, int32_t* argmin_mean, int32_t* min_map, int32_t* argmin_map)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   const bool wantMean = min_mean || argmin_mean, wantMap = min_map || argmin_map;
   if (!exp_coal_times || (!wantMean && !wantMap)) {
     return fail(ctx, FSMC_EINVAL, "need expected coalescence times and at least one output (mean or MAP minima)");
@@ -2506,66 +2556,35 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
   if ((wantMean && !(min_mean && argmin_mean)) || (wantMap && !(min_map && argmin_map))) {
     return fail(ctx, FSMC_EINVAL, "a minimum and its argmin come together");
   }
-  for (const fsmc_group& g : ctx->hGroups) {
-    if (g.from != 0 || g.to != (uint32_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "per-pair minima need whole-sequence groups (HMM.cpp:1378)");
-    }
-  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair minima"));
   if (pair_base > (uint64_t)INT32_MAX || pair_base + (uint64_t)ctx->nPairs > (uint64_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "pair_base + pairs of the work list exceeds the range of the int32 argmin");
   }
-  FSMC_HIP(ctx, hipSetDevice(ctx->device));
   const size_t S = (size_t)m->S;
   const int nOut = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
   const size_t groupBytes = (size_t)kWave * S * sizeof(float) * (size_t)nOut; // a full group's rows in the staging buffer
-
-  // The slice: what stagingLimit holds of rows, of half the room the card has free -- the decode's workspace is
-  // allocated after this.
-  size_t slice = ctx->pmSlice;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes, 2) / groupBytes);
-  }
-  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
-  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
-
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
-  LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, first, slice, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  auto pairsOfSlice = [&](size_t g0) {
-    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
-    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
-  };
-  size_t slicePairsMax = 0;
-  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
-    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
-  }
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceMinima, ctx->ppStage.bytes, groupBytes, ws));
   // The ranges: a wave owns 64 sites of one range.  A large slice is cut so that every SIMD of the chip gets a few waves
   // (4 x 4 x CUs of them over the site blocks), a range no shorter than 16 pairs: the partials stay a small fraction of
   // the rows.  FSMC_DIAG_MINIMA_RANGE=<pairs> -- tests: several ranges on a small problem.
   const size_t siteBlocks = (S + kWave - 1) / kWave;
   const size_t wavesWanted = (size_t)16 * (size_t)ctx->nCU;
   const size_t rangesWanted = std::max<size_t>(1, (wavesWanted + siteBlocks - 1) / siteBlocks);
-  size_t rangeLen = std::max<size_t>(16, (slicePairsMax + rangesWanted - 1) / rangesWanted);
+  size_t rangeLen = std::max<size_t>(16, (ws.slicePairsMax + rangesWanted - 1) / rangesWanted);
   rangeLen = loweredByEnv("FSMC_DIAG_MINIMA_RANGE", rangeLen);
-  const size_t rangesMax = (slicePairsMax + rangeLen - 1) / rangeLen;
+  const size_t rangesMax = (ws.slicePairsMax + rangeLen - 1) / rangeLen;
   if (rangesMax * siteBlocks > (size_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "too many ranges for one launch (FSMC_DIAG_MINIMA_RANGE)");
   }
 
   const size_t coalBytes = (size_t)m->KP * sizeof(float);
   const size_t vec = S * sizeof(float); // one [S] vector of floats or int32s
-  rc = ensure(ctx, ctx->ppStage, slicePairsMax * S * sizeof(float) * (size_t)nOut);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pmAcc, coalBytes + 4 * vec + 4 * rangesMax * vec);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slicePairsMax * S * sizeof(float) * (size_t)nOut));
+  FSMC_TRY(ensure(ctx, ctx->pmAcc, coalBytes + 4 * vec + 4 * rangesMax * vec));
   char* const acc = (char*)ctx->pmAcc.p;
-  std::vector<float> coal((size_t)m->KP, 0.f);
-  std::memcpy(coal.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
-  FSMC_HIP(ctx, hipMemcpyAsync(acc, coal.data(), coalBytes, hipMemcpyHostToDevice, ctx->stream));
+  KParams p;
+  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc, wantMean, wantMap, ws, p));
   void* const dState[4] = {acc + coalBytes, acc + coalBytes + vec, acc + coalBytes + 2 * vec, acc + coalBytes + 3 * vec};
   void* const hState[4] = {min_mean, argmin_mean, min_map, argmin_map};
   if (pair_base > 0) { // the chain continues: the caller's arrays are its state
@@ -2575,17 +2594,12 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
       }
     }
   }
-  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (coal is a local, the state the caller's)
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  float* const stageMean = wantMean ? (float*)ctx->ppStage.p : nullptr;
-  int* const stageMap = wantMap ? (int*)ctx->ppStage.p + (wantMean ? slicePairsMax * S : 0) : nullptr;
   char* const parts = acc + coalBytes + 4 * vec;
-  KParams p;
-  fillParams(ctx, m, plan, 0, p);
-  p.expCoal = (const float*)acc;
   PairMinimaParams q;
-  q.mean = stageMean;
-  q.map = stageMap;
+  q.mean = ws.stageMean;
+  q.map = ws.stageMap;
   q.S = m->S;
   q.rangeLen = (int)rangeLen;
   q.partMinMean = (float*)parts;
@@ -2597,23 +2611,13 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
   q.minMap = (int*)dState[2];
   q.argMap = (int*)dState[3];
 
-  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
-    const size_t nG = std::min(slice, ctx->nGroups - g0);
-    const size_t firstPair = ctx->hGroups[g0].first_pair;
-    const size_t n = pairsOfSlice(g0);
-    p.groups = ctx->dGroups + g0;
-    p.nGroups = (int)nG;
-    // (row `pair` of the work list is row `pair - firstPair` of the staging buffer)
-    p.ppMean = stageMean ? stageMean - firstPair * S : nullptr;
-    p.ppMap = stageMap ? stageMap - firstPair * S : nullptr;
-    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    FSMC_TRY(launchSlice(ctx, ws, sl, p));
+    const size_t n = ws.pairs(sl);
     q.n = (int)n;
     q.nRanges = (int)((n + rangeLen - 1) / rangeLen);
     q.seeded = (pair_base == 0 && sl == 0) ? 1 : 0;
-    q.firstIndex = (int)(pair_base + firstPair);
+    q.firstIndex = (int)(pair_base + ws.firstPair(sl));
     hipLaunchKernelGGL(pair_minima_kernel, dim3((unsigned)((size_t)q.nRanges * siteBlocks)), dim3(kWave), 0, ctx->stream,
                        q);
     FSMC_HIP(ctx, hipGetLastError());
@@ -2627,23 +2631,19 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
       FSMC_HIP(ctx, hipMemcpy(hState[i], dState[i], vec, hipMemcpyDeviceToHost));
     }
   }
-  ctx->lastPmSlices = (int)nSlices;
+  ctx->pairSlices[kSliceMinima].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 
 // Per pair, the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over bins of sites,
-// without the rows leaving the device: the per-pair consumers decode a slice of groups into ppStage exactly as for
-// fsmc_decode_pair_minima (the staging pointers moved back by the slice's first pair), pair_bins_kernel reduces the
-// slice's rows cell by cell (fsmc_pair_bins.h), and the slice's [pairs][B] outputs are copied to the caller's arrays at
-// the slice's first pair.  Slices are independent: nothing is carried.
+// without the rows leaving the device: pair_bins_kernel reduces a slice's rows cell by cell (fsmc_pair_bins.h), and the
+// slice's [pairs][B] outputs are copied to the caller's arrays at the slice's first pair.  Slices are independent:
+// nothing is carried.
 int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, const int32_t* bin_edges,
                           size_t n_bins, float* bin_mean, float* bin_min_mean, int32_t* bin_argmin_mean,
                           int32_t* bin_min_map, int32_t* bin_argmin_map)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   const bool wantMean = bin_mean || bin_min_mean || bin_argmin_mean, wantMap = bin_min_map || bin_argmin_map;
   if (!exp_coal_times || !bin_edges || (!wantMean && !wantMap)) {
     return fail(ctx, FSMC_EINVAL, "need expected coalescence times, bin edges and at least one output");
@@ -2651,26 +2651,8 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   if ((bin_min_mean != nullptr) != (bin_argmin_mean != nullptr) || (bin_min_map != nullptr) != (bin_argmin_map != nullptr)) {
     return fail(ctx, FSMC_EINVAL, "a minimum and its argmin come together");
   }
-  if (n_bins == 0) {
-    return fail(ctx, FSMC_EINVAL, "need one bin at least (n_bins + 1 edges)");
-  }
-  if (n_bins > (size_t)m->S) {
-    return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending: more bins than sites");
-  }
-  if (bin_edges[0] < 0 || bin_edges[n_bins] > m->S) {
-    return fail(ctx, FSMC_EINVAL, "bin edges must lie in [0, sites]");
-  }
-  for (size_t b = 0; b < n_bins; ++b) {
-    if (bin_edges[b] >= bin_edges[b + 1]) {
-      return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending");
-    }
-  }
-  for (const fsmc_group& g : ctx->hGroups) {
-    if (g.from != 0 || g.to != (uint32_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "per-pair bins need whole-sequence groups (HMM.cpp:1378)");
-    }
-  }
-  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  FSMC_TRY(checkBinEdges(ctx, m, bin_edges, n_bins));
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair bins"));
   const size_t S = (size_t)m->S, B = n_bins;
   const int nRows = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
   void* const hOut[5] = {bin_mean, bin_min_mean, bin_argmin_mean, bin_min_map, bin_argmin_map};
@@ -2680,51 +2662,23 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   }
   // a full group's rows in the staging buffer and its cells in the output buffer
   const size_t groupBytes = (size_t)kWave * sizeof(float) * (S * (size_t)nRows + B * nOut);
-
-  // The slice: what stagingLimit holds of rows and outputs, of half the room the card has free -- the decode's
-  // workspace is allocated after this.
-  size_t slice = ctx->pbSlice;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->pbAcc.bytes, 2) / groupBytes);
-  }
-  slice = std::max<size_t>(1, std::min(slice, ctx->nGroups));
-  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
-
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
-  LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModePerPair, ctx->betaStride, first, slice, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  auto pairsOfSlice = [&](size_t g0) {
-    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
-    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
-  };
-  size_t slicePairsMax = 0;
-  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
-    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
-  }
-  if (slicePairsMax > (size_t)INT32_MAX) {
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceBins, ctx->ppStage.bytes + ctx->pbAcc.bytes, groupBytes, ws));
+  if (ws.slicePairsMax > (size_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_bins_slice)");
   }
 
   const size_t coalBytes = (size_t)m->KP * sizeof(float);
   const size_t edgeBytes = (B + 1) * sizeof(int32_t);
-  const size_t outBytes = slicePairsMax * B * sizeof(float); // one output of the largest slice
-  rc = ensure(ctx, ctx->ppStage, slicePairsMax * S * sizeof(float) * (size_t)nRows);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pbAcc, coalBytes + edgeBytes + nOut * outBytes);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  const size_t outBytes = ws.slicePairsMax * B * sizeof(float); // one output of the largest slice
+  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slicePairsMax * S * sizeof(float) * (size_t)nRows));
+  FSMC_TRY(ensure(ctx, ctx->pbAcc, coalBytes + edgeBytes + nOut * outBytes));
   char* const acc = (char*)ctx->pbAcc.p;
-  std::vector<float> coal((size_t)m->KP, 0.f);
-  std::memcpy(coal.data(), exp_coal_times, sizeof(float) * (size_t)m->K);
-  FSMC_HIP(ctx, hipMemcpyAsync(acc, coal.data(), coalBytes, hipMemcpyHostToDevice, ctx->stream));
+  KParams p;
+  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc, wantMean, wantMap, ws, p));
   FSMC_HIP(ctx, hipMemcpyAsync(acc + coalBytes, bin_edges, edgeBytes, hipMemcpyHostToDevice, ctx->stream));
-  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (coal is a local, the edges the caller's)
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  float* const stageMean = wantMean ? (float*)ctx->ppStage.p : nullptr;
-  int* const stageMap = wantMap ? (int*)ctx->ppStage.p + (wantMean ? slicePairsMax * S : 0) : nullptr;
   void* dOut[5];
   {
     char* next = acc + coalBytes + edgeBytes;
@@ -2733,12 +2687,9 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
       next += hOut[i] ? outBytes : 0;
     }
   }
-  KParams p;
-  fillParams(ctx, m, plan, 0, p);
-  p.expCoal = (const float*)acc;
   PairBinsParams q;
-  q.mean = stageMean;
-  q.map = stageMap;
+  q.mean = ws.stageMean;
+  q.map = ws.stageMap;
   q.edges = (const int*)(acc + coalBytes);
   q.S = m->S;
   q.B = (int)B;
@@ -2751,19 +2702,9 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   const size_t wavesPerBlock = kPairBinsThreads / kWave;
   const size_t blocksMax = (size_t)8 * (size_t)std::max(ctx->nCU, 1);
 
-  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
-    const size_t nG = std::min(slice, ctx->nGroups - g0);
-    const size_t firstPair = ctx->hGroups[g0].first_pair;
-    const size_t n = pairsOfSlice(g0);
-    p.groups = ctx->dGroups + g0;
-    p.nGroups = (int)nG;
-    // (row `pair` of the work list is row `pair - firstPair` of the staging buffer)
-    p.ppMean = stageMean ? stageMean - firstPair * S : nullptr;
-    p.ppMap = stageMap ? stageMap - firstPair * S : nullptr;
-    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    FSMC_TRY(launchSlice(ctx, ws, sl, p));
+    const size_t n = ws.pairs(sl);
     q.n = (int)n;
     const size_t blocks = std::min(blocksMax, (n * B + wavesPerBlock - 1) / wavesPerBlock);
     hipLaunchKernelGGL(pair_bins_kernel, dim3((unsigned)blocks), dim3(kPairBinsThreads), 0, ctx->stream, q);
@@ -2774,33 +2715,28 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 5; ++i) {
       if (hOut[i]) {
-        FSMC_HIP(ctx, hipMemcpy((char*)hOut[i] + firstPair * B * sizeof(float), dOut[i], n * B * sizeof(float),
+        FSMC_HIP(ctx, hipMemcpy((char*)hOut[i] + ws.firstPair(sl) * B * sizeof(float), dOut[i], n * B * sizeof(float),
                                 hipMemcpyDeviceToHost));
       }
     }
   }
-  ctx->lastPbSlices = (int)nSlices;
+  ctx->pairSlices[kSliceBins].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 
 // Per pair and site, tail probabilities at state cuts and quantile states of the posterior (fsmc_pair_cdf.h), without the
-// [K][S] tables leaving the device.  The flow is that of fsmc_decode_pair_posteriors: the dump consumers decode a slice
-// of groups into ppStage, pair_cdf_kernel reduces it into ppRows, [output][pair of slice][S], and the rows of slice i
-// leave through the two pinned buffers on the copy stream while slice i + 1 decodes.  Slices are independent.
+// [K][S] tables leaving the device: pair_cdf_kernel reduces a slice's dump into ppRows, [output][pair of slice][S], one
+// launch of a workgroup per group and site block.  Slices are independent.
 int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
                          float* const* tail_rows, const float* quantiles, size_t n_quantiles,
                          int32_t* const* quantile_rows)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  constexpr size_t kMaxOfAKind = 8;
+  FSMC_TRY(checkReady(ctx, m));
   if (n_tail == 0 && n_quantiles == 0) {
     return fail(ctx, FSMC_EINVAL, "need at least one output (a tail state or a quantile)");
   }
   if (n_tail > kMaxOfAKind) {
-    return fail(ctx, FSMC_EINVAL, "at most 8 tail states a call");
+    return fail(ctx, FSMC_EINVAL, kTooManyTailStates);
   }
   if (n_quantiles > kMaxOfAKind) {
     return fail(ctx, FSMC_EINVAL, "at most 8 quantiles a call");
@@ -2812,15 +2748,9 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
     return fail(ctx, FSMC_EINVAL, "quantiles or quantile_rows is null");
   }
   std::vector<PairCdfSpec> spec;
+  FSMC_TRY(tailSpecs(ctx, m, tail_states, n_tail, tail_rows, spec));
   std::vector<char*> hRows; // the caller's matrices, in the order of spec
   for (size_t j = 0; j < n_tail; ++j) {
-    if (!tail_rows[j]) {
-      return fail(ctx, FSMC_EINVAL, "tail_rows[" + std::to_string(j) + "] is null");
-    }
-    if (tail_states[j] < 1 || tail_states[j] > m->K) {
-      return fail(ctx, FSMC_EINVAL, "tail state " + std::to_string(tail_states[j]) + " outside [1, K]");
-    }
-    spec.push_back(PairCdfSpec{tail_states[j], 0.f});
     hRows.push_back((char*)tail_rows[j]);
   }
   for (size_t j = 0; j < n_quantiles; ++j) {
@@ -2833,64 +2763,29 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
     spec.push_back(PairCdfSpec{0, quantiles[j]});
     hRows.push_back((char*)quantile_rows[j]);
   }
-  for (const fsmc_group& g : ctx->hGroups) {
-    if (g.from != 0 || g.to != (uint32_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "per-pair tails and quantiles need whole-sequence groups (HMM.cpp:1378)");
-    }
-  }
-  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair tails and quantiles"));
   const size_t K = (size_t)m->K, S = (size_t)m->S, nOut = spec.size();
   const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
   const size_t groupBytes = stageBytes + (size_t)kWave * S * sizeof(float) * nOut; // ... and its rows, at most
   const size_t siteBlocks = (S + kWave - 1) / kWave;
-
-  // The slice: what stagingLimit holds of staging and rows, of half the room the card has free -- the decode's
-  // workspace is allocated after this.  (A slice's reduction is one launch of a workgroup per group and site block.)
-  size_t slice = ctx->pcSlice;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes, 2) / groupBytes);
-  }
-  slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, (size_t)INT32_MAX / siteBlocks}));
-  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
-
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
-  LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  size_t slicePairsMax = 0;
-  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
-    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
-    slicePairsMax = std::max<size_t>(slicePairsMax, ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs -
-                                                      ctx->hGroups[g0].first_pair);
-  }
-  const size_t outCells = slicePairsMax * S; // cells of one output of the largest slice
-  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * stageBytes);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppRows, nOut * outCells * sizeof(float));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pcSpec, nOut * sizeof(PairCdfSpec));
-  // the way out: two pinned buffers of 128 MiB, or one output of the largest slice if that is smaller
-  constexpr size_t kPinnedBytes = 128u << 20;
-  const size_t cellsPerCopy = std::min<size_t>(kPinnedBytes / sizeof(float), outCells);
-  if (rc == FSMC_OK) rc = ensureRowCopies(ctx, cellsPerCopy * sizeof(float));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-
-  std::vector<size_t> offsets(slice);
-  for (size_t i = 0; i < slice; ++i) {
-    offsets[i] = i * (size_t)kWave * K * S;
-  }
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nOut * sizeof(PairCdfSpec), hipMemcpyHostToDevice,
-                               ctx->stream));
-  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets and spec are locals)
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceCdf, ctx->ppStage.bytes + ctx->ppRows.bytes, groupBytes, ws,
+                      (size_t)INT32_MAX / siteBlocks));
+  const size_t outCells = ws.slicePairsMax * S; // cells of one output of the largest slice
+  FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppRows, nOut * outCells * sizeof(float)));
+  FSMC_TRY(ensure(ctx, ctx->pcSpec, nOut * sizeof(PairCdfSpec)));
+  // the way out: cells a copy -- what a pinned buffer holds, or one output of the largest slice if that is smaller
+  const size_t cellsPerCopy = std::min(std::max<size_t>(1, rowCopyBytes() / sizeof(float)), outCells);
+  FSMC_TRY(ensureRowCopies(ctx, cellsPerCopy * sizeof(float)));
 
   KParams p;
-  fillParams(ctx, m, plan, 0, p);
-  p.dumpOut = (float*)ctx->ppStage.p;
-  p.dumpOffsets = (const size_t*)ctx->aux.p;
+  FSMC_TRY(dumpSetup(ctx, m, ws, p));
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nOut * sizeof(PairCdfSpec), hipMemcpyHostToDevice,
+                               ctx->stream));
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
   PairCdfParams q;
   q.stage = (const float*)ctx->ppStage.p;
   q.K = m->K;
@@ -2898,91 +2793,46 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
   q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
   q.nOut = (int)nOut;
   q.rows = (int*)ctx->ppRows.p;
-  q.rowsPerOut = slicePairsMax;
-
-  // the rows of pairs [lo, hi) of the work list, rows 0 ... hi - lo of every output on the device: output by output,
-  // copy by copy through the pinned buffers, the next copy in flight while the host moves the one before into the
-  // caller's matrix
-  auto drain = [&](size_t lo, size_t hi) -> int {
-    FSMC_HIP(ctx, hipStreamWaitEvent(ctx->copyStream, ctx->evRows, 0));
-    const size_t cells = (hi - lo) * S;
-    const size_t copiesPerOut = (cells + cellsPerCopy - 1) / cellsPerCopy, nCopies = copiesPerOut * nOut;
-    auto issue = [&](size_t c, int b) -> int {
-      const size_t o = c / copiesPerOut, c0 = (c % copiesPerOut) * cellsPerCopy;
-      FSMC_HIP(ctx, hipMemcpyAsync(ctx->ppPinned[b], (const float*)ctx->ppRows.p + o * outCells + c0,
-                                   std::min(cellsPerCopy, cells - c0) * sizeof(float), hipMemcpyDeviceToHost,
-                                   ctx->copyStream));
-      FSMC_HIP(ctx, hipEventRecord(ctx->evCopied[b], ctx->copyStream));
-      return FSMC_OK;
-    };
-    int b = 0;
-    int r = issue(0, b);
-    for (size_t c = 0; r == FSMC_OK && c < nCopies; ++c, b ^= 1) {
-      if (c + 1 < nCopies) {
-        r = issue(c + 1, b ^ 1);
-        if (r != FSMC_OK) {
-          break;
-        }
-      }
-      FSMC_HIP(ctx, hipEventSynchronize(ctx->evCopied[b]));
-      const size_t o = c / copiesPerOut, c0 = (c % copiesPerOut) * cellsPerCopy;
-      std::memcpy(hRows[o] + (lo * S + c0) * sizeof(float), ctx->ppPinned[b],
-                  std::min(cellsPerCopy, cells - c0) * sizeof(float));
-    }
-    return r;
-  };
-
-  size_t prevLo = 0, prevHi = 0; // pairs of the slice whose rows are still on the device
-  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
-    const size_t nG = std::min(slice, ctx->nGroups - g0);
-    p.groups = ctx->dGroups + g0;
-    p.nGroups = (int)nG;
-    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
-    if (prevHi > prevLo) { // (while this slice decodes; ppRows is free again when it returns)
-      rc = drain(prevLo, prevHi);
-      if (rc != FSMC_OK) {
-        return rc;
-      }
-    }
-    q.groups = ctx->dGroups + g0;
-    q.nGroups = (int)nG;
-    q.firstPair = ctx->hGroups[g0].first_pair;
-    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(nG * siteBlocks)), dim3(kPairCdfThreads), 0, ctx->stream, q);
+  q.rowsPerOut = ws.slicePairsMax;
+  auto reduce = [&](size_t sl) -> int {
+    q.groups = ctx->dGroups + ws.firstGroup(sl);
+    q.nGroups = (int)ws.groups(sl);
+    q.firstPair = (unsigned)ws.firstPair(sl);
+    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(ws.groups(sl) * siteBlocks)), dim3(kPairCdfThreads), 0,
+                       ctx->stream, q);
     FSMC_HIP(ctx, hipGetLastError());
-    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
-    FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
-    prevLo = ctx->hGroups[g0].first_pair;
-    prevHi = ctx->hGroups[g0 + nG - 1].first_pair + ctx->hGroups[g0 + nG - 1].n_pairs;
-  }
-  if (prevHi > prevLo) {
-    rc = drain(prevLo, prevHi);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
-  }
+    return FSMC_OK;
+  };
+  // the slice's pairs are rows 0 ... of every output on the device, `outCells` apart: output by output, runs of cells
+  // into the caller's matrix
+  auto drain = [&](size_t sl) -> int {
+    const size_t cells = ws.pairs(sl) * S, copiesPerOut = (cells + cellsPerCopy - 1) / cellsPerCopy;
+    const float* const dRows = (const float*)ctx->ppRows.p;
+    auto first = [&](size_t c) { return (c % copiesPerOut) * cellsPerCopy; };
+    auto bytes = [&](size_t c) { return std::min(cellsPerCopy, cells - first(c)) * sizeof(float); };
+    return drainRows(
+        ctx, copiesPerOut * nOut,
+        [&](size_t c) { return RowChunk{dRows + c / copiesPerOut * outCells + first(c), bytes(c)}; },
+        [&](size_t c, const char* host) {
+          std::memcpy(hRows[c / copiesPerOut] + (ws.firstPair(sl) * S + first(c)) * sizeof(float), host, bytes(c));
+        });
+  };
+  FSMC_TRY(decodeSlicesDrained(ctx, ws, p, true, reduce, drain));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->lastPcSlices = (int)nSlices;
+  ctx->pairSlices[kSliceCdf].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 
 // The tail probabilities of fsmc_decode_pair_cdf reduced over pairs per site and over bins of sites per pair
-// (fsmc_pair_tail.h), without the tail rows leaving the device.  The flow is that of fsmc_decode_pair_cdf up to the rows:
-// the dump consumers decode a slice of groups into ppStage, pair_cdf_kernel -- as it is -- reduces it into ppRows,
-// [cut][pair of slice][S]; then pair_tail_sum_kernel continues the fp64 chain of every site in the device copy of the
-// accumulator and pair_tail_bins_kernel reduces the rows cell by cell, and the slice's [cut][pairs][B] outputs are copied
-// to the caller's arrays at the slice's first pair.  Only the sum is carried from slice to slice.
+// (fsmc_pair_tail.h), without the tail rows leaving the device: pair_cdf_kernel -- as it is -- reduces a slice's dump into
+// ppRows, [cut][pair of slice][S]; then pair_tail_sum_kernel continues the fp64 chain of every site in the device copy of
+// the accumulator and pair_tail_bins_kernel reduces the rows cell by cell, and the slice's [cut][pairs][B] outputs are
+// copied to the caller's arrays at the slice's first pair.  Only the sum is carried from slice to slice.
 int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
                                     double* tail_sum, const int32_t* bin_edges, size_t n_bins, float* bin_tail_mean,
                                     const float* site_weights, float* bin_tail_length)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  constexpr size_t kMaxCuts = 8;
+  FSMC_TRY(checkReady(ctx, m));
   const bool wantBins = bin_tail_mean || bin_tail_length;
   if (!tail_sum && !wantBins) {
     return fail(ctx, FSMC_EINVAL, "need at least one output (tail_sum, bin_tail_mean or bin_tail_length)");
@@ -2990,34 +2840,16 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   if (n_tail == 0 || !tail_states) {
     return fail(ctx, FSMC_EINVAL, "need one tail state at least");
   }
-  if (n_tail > kMaxCuts) {
-    return fail(ctx, FSMC_EINVAL, "at most 8 tail states a call");
+  if (n_tail > kMaxOfAKind) {
+    return fail(ctx, FSMC_EINVAL, kTooManyTailStates);
   }
   std::vector<PairCdfSpec> spec;
-  for (size_t j = 0; j < n_tail; ++j) {
-    if (tail_states[j] < 1 || tail_states[j] > m->K) {
-      return fail(ctx, FSMC_EINVAL, "tail state " + std::to_string(tail_states[j]) + " outside [1, K]");
-    }
-    spec.push_back(PairCdfSpec{tail_states[j], 0.f});
-  }
+  FSMC_TRY(tailSpecs(ctx, m, tail_states, n_tail, nullptr, spec));
   if (wantBins) {
     if (!bin_edges) {
       return fail(ctx, FSMC_EINVAL, "bin outputs need bin edges");
     }
-    if (n_bins == 0) {
-      return fail(ctx, FSMC_EINVAL, "need one bin at least (n_bins + 1 edges)");
-    }
-    if (n_bins > (size_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending: more bins than sites");
-    }
-    if (bin_edges[0] < 0 || bin_edges[n_bins] > m->S) {
-      return fail(ctx, FSMC_EINVAL, "bin edges must lie in [0, sites]");
-    }
-    for (size_t b = 0; b < n_bins; ++b) {
-      if (bin_edges[b] >= bin_edges[b + 1]) {
-        return fail(ctx, FSMC_EINVAL, "bin edges must be strictly ascending");
-      }
-    }
+    FSMC_TRY(checkBinEdges(ctx, m, bin_edges, n_bins));
   }
   if (bin_tail_length) {
     if (!site_weights) {
@@ -3029,57 +2861,28 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
       }
     }
   }
-  for (const fsmc_group& g : ctx->hGroups) {
-    if (g.from != 0 || g.to != (uint32_t)m->S) {
-      return fail(ctx, FSMC_EINVAL, "tail summaries need whole-sequence groups (HMM.cpp:1378)");
-    }
-  }
-  FSMC_HIP(ctx, hipSetDevice(ctx->device));
+  FSMC_TRY(checkWholeSequence(ctx, m, "tail summaries"));
   const size_t K = (size_t)m->K, S = (size_t)m->S, nT = n_tail, B = wantBins ? n_bins : 0;
   const size_t nBinOut = (bin_tail_mean ? 1 : 0) + (bin_tail_length ? 1 : 0);
   const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
   // ... and its rows and its cells in the output buffer
   const size_t groupBytes = stageBytes + (size_t)kWave * sizeof(float) * nT * (S + B * nBinOut);
   const size_t siteBlocks = (S + kWave - 1) / kWave;
-
-  // The slice: what stagingLimit holds of staging, rows and outputs, of half the room the card has free -- the decode's
-  // workspace is allocated after this.
-  size_t slice = ctx->ptSlice;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, ctx->ppStage.bytes + ctx->ppRows.bytes + ctx->ptAcc.bytes, 2) / groupBytes);
-  }
-  slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, (size_t)INT32_MAX / siteBlocks}));
-  const size_t nSlices = (ctx->nGroups + slice - 1) / slice;
-
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)slice);
-  LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, first, slice, 0, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
-  auto pairsOfSlice = [&](size_t g0) {
-    const size_t g1 = std::min(ctx->nGroups, g0 + slice);
-    return (size_t)(ctx->hGroups[g1 - 1].first_pair + ctx->hGroups[g1 - 1].n_pairs - ctx->hGroups[g0].first_pair);
-  };
-  size_t slicePairsMax = 0;
-  for (size_t g0 = 0; g0 < ctx->nGroups; g0 += slice) {
-    slicePairsMax = std::max(slicePairsMax, pairsOfSlice(g0));
-  }
-  if (slicePairsMax > (size_t)INT32_MAX) {
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceTail, ctx->ppStage.bytes + ctx->ppRows.bytes + ctx->ptAcc.bytes,
+                      groupBytes, ws, (size_t)INT32_MAX / siteBlocks));
+  if (ws.slicePairsMax > (size_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_tail_slice)");
   }
   const size_t sumBytes = nT * S * sizeof(double);
   const size_t edgeBytes = wantBins ? ((B + 1) * sizeof(int32_t) + 7) / 8 * 8 : 0;
   const size_t weightBytes = bin_tail_length ? (S * sizeof(float) + 7) / 8 * 8 : 0;
-  const size_t outBytes = nT * slicePairsMax * B * sizeof(float); // one output of the largest slice, every cut
-  rc = ensure(ctx, ctx->aux, slice * sizeof(size_t));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppStage, slice * stageBytes);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ppRows, nT * slicePairsMax * S * sizeof(float));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->pcSpec, nT * sizeof(PairCdfSpec));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->ptAcc, sumBytes + edgeBytes + weightBytes + nBinOut * outBytes);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  const size_t outBytes = nT * ws.slicePairsMax * B * sizeof(float); // one output of the largest slice, every cut
+  FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppRows, nT * ws.slicePairsMax * S * sizeof(float)));
+  FSMC_TRY(ensure(ctx, ctx->pcSpec, nT * sizeof(PairCdfSpec)));
+  FSMC_TRY(ensure(ctx, ctx->ptAcc, sumBytes + edgeBytes + weightBytes + nBinOut * outBytes));
 
   char* const acc = (char*)ctx->ptAcc.p;
   double* const dSum = (double*)acc;
@@ -3087,11 +2890,8 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   char* const dWeights = dEdges + edgeBytes;
   float* const dMean = bin_tail_mean ? (float*)(dWeights + weightBytes) : nullptr;
   float* const dLength = bin_tail_length ? (float*)(dWeights + weightBytes + (bin_tail_mean ? outBytes : 0)) : nullptr;
-  std::vector<size_t> offsets(slice);
-  for (size_t i = 0; i < slice; ++i) {
-    offsets[i] = i * (size_t)kWave * K * S;
-  }
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), slice * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+  KParams p;
+  FSMC_TRY(dumpSetup(ctx, m, ws, p));
   FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nT * sizeof(PairCdfSpec), hipMemcpyHostToDevice, ctx->stream));
   if (tail_sum) { // the chain continues what the caller passes in
     FSMC_HIP(ctx, hipMemcpyAsync(dSum, tail_sum, sumBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -3102,12 +2902,8 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   if (bin_tail_length) {
     FSMC_HIP(ctx, hipMemcpyAsync(dWeights, site_weights, S * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   }
-  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (offsets and spec are locals, the rest the caller's)
+  FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  KParams p;
-  fillParams(ctx, m, plan, 0, p);
-  p.dumpOut = (float*)ctx->ppStage.p;
-  p.dumpOffsets = (const size_t*)ctx->aux.p;
   PairCdfParams q;
   q.stage = (const float*)ctx->ppStage.p;
   q.K = m->K;
@@ -3115,10 +2911,10 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
   q.nOut = (int)nT;
   q.rows = (int*)ctx->ppRows.p;
-  q.rowsPerOut = slicePairsMax;
+  q.rowsPerOut = ws.slicePairsMax;
   PairTailParams r;
   r.rows = (const float*)ctx->ppRows.p;
-  r.rowsPerOut = slicePairsMax;
+  r.rowsPerOut = ws.slicePairsMax;
   r.S = m->S;
   r.nTail = (int)nT;
   r.sum = tail_sum ? dSum : nullptr;
@@ -3133,17 +2929,10 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   float* const hOut[2] = {bin_tail_mean, bin_tail_length};
   const float* const dOut[2] = {dMean, dLength};
 
-  for (size_t g0 = 0, sl = 0; g0 < ctx->nGroups; g0 += slice, ++sl) {
-    const size_t nG = std::min(slice, ctx->nGroups - g0);
-    const size_t firstPair = ctx->hGroups[g0].first_pair;
-    const size_t n = pairsOfSlice(g0);
-    p.groups = ctx->dGroups + g0;
-    p.nGroups = (int)nG;
-    rc = launch(ctx, plan.k, p, (int)std::min<size_t>((size_t)plan.slots, nG), 0, sl != 0);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
-    q.groups = ctx->dGroups + g0;
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    FSMC_TRY(launchSlice(ctx, ws, sl, p));
+    const size_t nG = ws.groups(sl), firstPair = ws.firstPair(sl), n = ws.pairs(sl);
+    q.groups = ctx->dGroups + ws.firstGroup(sl);
     q.nGroups = (int)nG;
     q.firstPair = (unsigned)firstPair;
     hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(nG * siteBlocks)), dim3(kPairCdfThreads), 0, ctx->stream, q);
@@ -3166,7 +2955,7 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
       FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
       for (int o = 0; o < 2; ++o) {
         for (size_t j = 0; hOut[o] && j < nT; ++j) {
-          FSMC_HIP(ctx, hipMemcpy(hOut[o] + (j * ctx->nPairs + firstPair) * B, dOut[o] + j * slicePairsMax * B,
+          FSMC_HIP(ctx, hipMemcpy(hOut[o] + (j * ctx->nPairs + firstPair) * B, dOut[o] + j * ws.slicePairsMax * B,
                                   n * B * sizeof(float), hipMemcpyDeviceToHost));
         }
       }
@@ -3176,7 +2965,7 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   if (tail_sum) {
     FSMC_HIP(ctx, hipMemcpy(tail_sum, dSum, sumBytes, hipMemcpyDeviceToHost));
   }
-  ctx->lastPtSlices = (int)nSlices;
+  ctx->pairSlices[kSliceTail].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 

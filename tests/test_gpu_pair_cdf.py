@@ -120,6 +120,28 @@ def test_ragged_list_and_rows_beyond_it(gpu, small_problem, slice_groups):
         assert _untouched(g[:, 150:]), name
 
 
+@pytest.mark.parametrize("slice_groups", [0, 1])
+def test_short_row_copies_do_not_show(small_problem, monkeypatch, slice_groups):
+    """The ragged list of 150 pairs through pinned buffers of 4000 bytes: 1000 cells a copy, no multiple of the 640
+    sites, so copies straddle rows.  A slice of 64 pairs leaves in 41 copies per output, the last of 960 cells, the
+    slice of 22 pairs in 15, the last of 80 cells -- and on the device an output's rows lie 64 x 640 cells apart, more
+    than that slice holds; the automatic slice, all 150 pairs, in 96 full copies per output."""
+    monkeypatch.setenv("FSMC_DIAG_ROW_COPY_BYTES", "4000")
+    ctx, model = _open(small_problem)
+    pm = small_problem["model"]
+    want = CL.expected_192(small_problem)
+    _upload(ctx, pm, CL.PAIRS_192[:150])
+    ctx.set_pair_cdf_slice(slice_groups)
+    bufs = _sentinels(4, 4, 170, pm.S)
+    got = ctx.decode_pair_cdf(model, CL.cuts(pm), CL.QS, out=bufs)
+    slices = ctx.last_pair_cdf_slices()
+    ctx.close()
+    assert slices == (3 if slice_groups else 1)
+    for name, g, w in zip(("tail", "qstate"), got, want):
+        assert np.array_equal(g[:, :150], w[:, :150]), name
+        assert _untouched(g[:, 150:]), name
+
+
 def _problem(K, n_hap=64, S=200, seed=11):
     tables = synth.make_model_tables(K)
     haps = synth.make_haps(n_hap, S, seed=seed, cm_per_mb=25.0, switch_per_cm=0.6)

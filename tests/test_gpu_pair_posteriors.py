@@ -132,6 +132,27 @@ def test_slices_do_not_show(gpu, small_problem, want_150):
         np.testing.assert_array_equal(s, wsum, err_msg=f"slice {slice_groups}")
 
 
+@pytest.mark.parametrize("copy_bytes,slice_groups", [(529920, 1), (529920, 0), (1000, 1)])
+def test_short_row_copies_do_not_show(small_problem, want_150, monkeypatch, copy_bytes, slice_groups):
+    """Pinned buffers of 529920 bytes, three tables of 69 x 640 floats: a slice of 64 pairs leaves in 22 copies, the
+    last of one pair, the slice of 22 pairs in 8, the last of one pair; the automatic slice, all 150 pairs, in 50 full
+    copies.  1000 bytes are less than one table: one pair a copy."""
+    monkeypatch.setenv("FSMC_DIAG_ROW_COPY_BYTES", str(copy_bytes))
+    ctx = capi.Context(0)
+    pm = small_problem["model"]
+    model = ctx.create_model(pm)
+    ctx.upload_haps(small_problem["bits"], pm.S)
+    _upload(ctx, pm, PAIRS_150)
+    ctx.set_pair_posterior_slice(slice_groups)
+    rows, s = ctx.decode_pair_posteriors(model, pm.exp_times, sum_into=np.zeros((pm.K, pm.S), np.float32))
+    slices = ctx.last_pair_posterior_slices()
+    ctx.close()
+    assert slices == (3 if slice_groups else 1)
+    wrows, wsum = want_150
+    np.testing.assert_array_equal(rows, wrows)
+    np.testing.assert_array_equal(s, wsum)
+
+
 @pytest.mark.parametrize("K,S,n_pairs", [(40, 200, 96), (200, 200, 96), (1030, 120, 70)])
 def test_other_kernels(K, S, n_pairs):
     """A padded member with ghost states (40 -> 48), the wave-group kernel (200 states), the any-K kernel (1030)."""

@@ -3,7 +3,7 @@
 AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, LDS bytes per workgroup, waves per SIMD -- one row per
 instantiation of every family member and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
 transposition, the per-pair minima and their combine step, the per-pair site bins, the per-pair tails and quantile states, the tail summaries), stamped with the hash of the sources they were compiled from.
-Usage: tools/resource_table.py [out.json]   (default profiles/r10_kernel_resources.json; no GPU needed)"""
+Usage: tools/resource_table.py [out.json]   (default profiles/r11_kernel_resources.json; no GPU needed)"""
 import json
 import os
 import re
@@ -46,7 +46,7 @@ def member(define, src="fsmc_inst.hip"):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r10_kernel_resources.json")
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r11_kernel_resources.json")
     # every member the build compiles (fastsmc_amd/build.py): padded and exact lane-per-pair members, wave-group members
     defs = ([f"-DFSMC_INSTANCE_KT={k}" for k in KT_MEMBERS + EXACT_MEMBERS]
             + [f"-DFSMC_INSTANCE_W2={kh} -DFSMC_INSTANCE_NW={nw}" for kh, nw in W2_MEMBERS])
