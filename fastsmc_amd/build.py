@@ -133,8 +133,8 @@ def build_hip(force: bool = False, verbose: bool = False, jobs: int | None = Non
 
 
 HOST_DIR = os.path.join(CSRC, "host")
-HOST_SOURCES = ["decoding_quantities.cpp", "decoding_params.cpp", "data.cpp", "hmm.cpp", "hashing.cpp", "drivers.cpp",
-                "pybind_module.cpp", "pybind_containers.cpp"]
+HOST_SOURCES = ["decoding_quantities.cpp", "decoding_params.cpp", "data.cpp", "pair_outputs.cpp", "hmm.cpp", "hashing.cpp",
+                "drivers.cpp", "pybind_module.cpp", "pybind_containers.cpp"]
 
 
 def host_module_path() -> str:

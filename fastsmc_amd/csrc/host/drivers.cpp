@@ -33,46 +33,33 @@ DecodingReturnValues ASMC::decodeAllInJob()
 }
 
 void ASMC::decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
-                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
-                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
-                       const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights)
+                       const PairOutputs& outputs)
 {
   if (hapIndicesA.empty() || hapIndicesA.size() != hapIndicesB.size()) {
     throw std::runtime_error("Vector of A indices (" + std::to_string(hapIndicesA.size()) +
                              ") must be the same size as vector of B indices (" +
                              std::to_string(hapIndicesB.size()) + ").\n");
   }
+  if (!outputs.tailStates.empty() || !outputs.tailSummaryStates.empty()) {
+    throw std::runtime_error("tail states are derived from the tail times: leave them empty");
+  }
   // (first: arguments these refuse leave the last call's results as they are)
-  const std::vector<int> tailStates = tailStatesOf(tailTimes);
-  const std::vector<int> tailSummaryStates = tailStatesOf(tailSummaryTimes);
-  if (!siteWeights.empty() && siteBins.empty()) {
+  PairOutputs o = outputs;
+  o.tailStates = tailStatesOf(o.tailTimes);
+  o.tailSummaryStates = tailStatesOf(o.tailSummaryTimes);
+  if (!o.siteWeights.empty() && o.siteBins.empty()) {
     throw std::runtime_error("site weights need site bins");
   }
-  mHmm.setPosteriorCdf(tailStates, quantiles);
-  mHmm.setTailSummaries(tailSummaryStates, siteWeights);
-  mHmm.setSiteBins(siteBins);
-  mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA, hapIndicesB, mHmm.getData().sites,
-                                               mHmm.getDecodingQuantities().states, perPairPosteriors, sumOfPosteriors,
-                                               perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-                                               siteBins, tailTimes, tailStates, quantiles, tailSummaryTimes,
-                                               tailSummaryStates, siteWeights);
-  mHmm.setStorePerPairPosteriorMean(perPairPosteriorMeans);
-  mHmm.setStorePerPairMap(perPairMAPs);
-  mHmm.setStorePerPairPosterior(perPairPosteriors);
-  mHmm.setStoreSumOfPosterior(sumOfPosteriors);
-  mHmm.setStoreMinPosteriorMean(minPosteriorMeans);
-  mHmm.setStoreMinMap(minMAPs);
+  mHmm.setPairOutputs(o);
+  mHmm.getDecodePairsReturnStruct().initialise(hapIndicesA.size(), mHmm.getData().sites,
+                                               mHmm.getDecodingQuantities().states, o);
   mHmm.decodeHapPairs(hapIndicesA, hapIndicesB);
   mHmm.finishDecoding();
   mHmm.getDecodePairsReturnStruct().finaliseCalculations();
 }
 
 void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
-                       bool perPairPosteriors, bool sumOfPosteriors, bool perPairPosteriorMeans, bool perPairMAPs,
-                       bool minPosteriorMeans, bool minMAPs, const std::vector<int>& siteBins,
-                       const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
-                       const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights)
+                       const PairOutputs& outputs)
 {
   if (hapIdsA.size() != hapIdsB.size()) {
     throw std::runtime_error("Vector of A IDs (" + std::to_string(hapIdsA.size()) +
@@ -86,8 +73,7 @@ void ASMC::decodePairs(const std::vector<std::string>& hapIdsA, const std::vecto
     a[i] = dipToHapId(getIndIdxFromIdString(ids, strA), hapA);
     b[i] = dipToHapId(getIndIdxFromIdString(ids, strB), hapB);
   }
-  decodePairs(a, b, perPairPosteriors, sumOfPosteriors, perPairPosteriorMeans, perPairMAPs, minPosteriorMeans, minMAPs,
-              siteBins, tailTimes, quantiles, tailSummaryTimes, siteWeights);
+  decodePairs(a, b, outputs);
 }
 
 std::vector<int> ASMC::tailStatesOf(const std::vector<float>& tailTimes)

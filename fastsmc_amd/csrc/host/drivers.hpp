@@ -18,23 +18,15 @@ public:
   ASMC(const std::string& inFileRoot, const std::string& decodingQuantFile, const std::string& outFileRoot = "");
 
   DecodingReturnValues decodeAllInJob(); // ASMC.cpp:51-78
+  // ASMC.cpp:80-100: decode the listed pairs into the return structure.  `outputs` says what is stored (PairOutputs,
+  // pair_outputs.hpp); its tailStates / tailSummaryStates are made here from tailTimes / tailSummaryTimes (generations,
+  // tailStatesOf) and must come empty.  A request that is refused throws before the last call's results or any queued
+  // work are touched.
   void decodePairs(const std::vector<unsigned long>& hapIndicesA, const std::vector<unsigned long>& hapIndicesB,
-                   bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
-                   bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
-                   const std::vector<int>& siteBins = {}, const std::vector<float>& tailTimes = {},
-                   const std::vector<float>& quantiles = {}, const std::vector<float>& tailSummaryTimes = {},
-                   const std::vector<float>& siteWeights = {});
-  // ASMC.cpp:80-100; minima: without the rows; siteBins: edges of the per-pair summaries over bins of sites, {} = none;
-  // tailTimes (generations) / quantiles: per pair and site the posterior probability of a coalescence more recent than
-  // each time and the posterior quantile states, {} = none; tailSummaryTimes (generations): the same tail probabilities
-  // not stored but summed over the pairs per site and, with siteBins, reduced per pair over the bins -- the mean, and with
-  // siteWeights ([sites]) the weighted sum --, {} = none
+                   const PairOutputs& outputs = {});
+  // ASMC.cpp:102-128: the same for "<individual ID>#<1|2>" strings
   void decodePairs(const std::vector<std::string>& hapIdsA, const std::vector<std::string>& hapIdsB,
-                   bool perPairPosteriors = false, bool sumOfPosteriors = false, bool perPairPosteriorMeans = false,
-                   bool perPairMAPs = false, bool minPosteriorMeans = false, bool minMAPs = false,
-                   const std::vector<int>& siteBins = {}, const std::vector<float>& tailTimes = {},
-                   const std::vector<float>& quantiles = {}, const std::vector<float>& tailSummaryTimes = {},
-                   const std::vector<float>& siteWeights = {}); // ASMC.cpp:102-128
+                   const PairOutputs& outputs = {});
   // the state cut of a tail time T (generations): #{k : discretization[k] < (float)T}, the loop of
   // HMM::getStateThreshold (HMM.cpp:504-513); throws for a time no interval starts below
   std::vector<int> tailStatesOf(const std::vector<float>& tailTimes);

@@ -107,124 +107,12 @@ unsigned long getIndIdxFromIdString(const std::vector<std::string>& ids, const s
   return static_cast<unsigned long>(std::distance(ids.begin(), it));
 }
 
-// ------------------------------------------------------------------ return structs
-
-void DecodePairsReturnStruct::initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>&,
-                                         long sites, long states, bool fullPosteriors, bool sumOfPost,
-                                         bool perPairMeans, bool perPairMaps, bool minMeans, bool minMaps,
-                                         const std::vector<int>& siteBins, const std::vector<float>& tailTimesIn,
-                                         const std::vector<int>& tailStatesIn, const std::vector<float>& quantilesIn,
-                                         const std::vector<float>& tailSummaryTimesIn,
-                                         const std::vector<int>& tailSummaryStatesIn,
-                                         const std::vector<float>& siteWeightsIn)
-{
-  numWritten = 0;
-  numPairs = static_cast<long>(hapsA.size());
-  numSites = sites;
-  numStates = states;
-  storeFullPosteriors = fullPosteriors;
-  storeSumOfPosteriors = sumOfPost;
-  storePerPairPosteriorMeans = perPairMeans;
-  storePerPairMAPs = perPairMaps;
-  storeMinPosteriorMeans = minMeans;
-  storeMinMAPs = minMaps;
-  perPairIndices.assign(static_cast<size_t>(numPairs), {});
-  perPairPosteriors.clear();
-  sumOfPosteriors.clear();
-  perPairPosteriorMeans.clear();
-  perPairMAPs.clear();
-  minPosteriorMeans.clear();
-  argminPosteriorMeans.clear();
-  minMAPs.clear();
-  argminMAPs.clear();
-  if (fullPosteriors) {
-    perPairPosteriors.assign(static_cast<size_t>(numPairs), std::vector<float>(static_cast<size_t>(states * sites)));
-  }
-  if (sumOfPost) {
-    sumOfPosteriors.assign(static_cast<size_t>(states * sites), 0.f);
-  }
-  if (perPairMeans) {
-    perPairPosteriorMeans.assign(static_cast<size_t>(numPairs * sites), 0.f);
-    minPosteriorMeans.assign(static_cast<size_t>(sites), 0.f);
-    argminPosteriorMeans.assign(static_cast<size_t>(sites), 0);
-  }
-  if (perPairMaps) {
-    perPairMAPs.assign(static_cast<size_t>(numPairs * sites), 0);
-    minMAPs.assign(static_cast<size_t>(sites), 0);
-    argminMAPs.assign(static_cast<size_t>(sites), 0);
-  }
-  // the minima alone: the four [sites] vectors without the [pairs][sites] matrices
-  if (minMeans && !perPairMeans) {
-    minPosteriorMeans.assign(static_cast<size_t>(sites), 0.f);
-    argminPosteriorMeans.assign(static_cast<size_t>(sites), 0);
-  }
-  if (minMaps && !perPairMaps) {
-    minMAPs.assign(static_cast<size_t>(sites), 0);
-    argminMAPs.assign(static_cast<size_t>(sites), 0);
-  }
-  // the per-pair summaries over bins of sites: [pairs][bins]
-  binEdges = siteBins;
-  const size_t cells = siteBins.size() < 2 ? 0 : static_cast<size_t>(numPairs) * (siteBins.size() - 1);
-  binMeanPosteriorMeans.assign(cells, 0.f);
-  binMinPosteriorMeans.assign(cells, 0.f);
-  binArgminPosteriorMeans.assign(cells, 0);
-  binMinMAPs.assign(cells, 0);
-  binArgminMAPs.assign(cells, 0);
-  // the per-pair tail probabilities and quantile states: [outputs][pairs][sites]
-  tailTimes = tailTimesIn;
-  tailStates = tailStatesIn;
-  quantiles = quantilesIn;
-  const size_t rowCells = static_cast<size_t>(numPairs) * static_cast<size_t>(sites);
-  perPairTailProbabilities.assign(tailStates.size() * rowCells, 0.f);
-  perPairQuantileStates.assign(quantiles.size() * rowCells, 0);
-  // the tail probabilities reduced over pairs, [tails][sites], and over bins, [tails][pairs][bins]
-  tailSummaryTimes = tailSummaryTimesIn;
-  tailSummaryStates = tailSummaryStatesIn;
-  siteWeights = siteWeightsIn;
-  sumOfTailProbabilities.assign(tailSummaryStates.size() * static_cast<size_t>(sites), 0.0);
-  binTailMeans.assign(tailSummaryStates.size() * cells, 0.f);
-  binTailLengths.assign(siteWeights.empty() ? 0 : tailSummaryStates.size() * cells, 0.f);
-}
-
-void DecodePairsReturnStruct::finaliseCalculations()
-{
-  // column-wise min / first argmin (DecodePairsReturnStruct.hpp:105-118)
-  if (!perPairPosteriorMeans.empty()) {
-    for (long s = 0; s < numSites; ++s) {
-      long arg = 0;
-      float best = perPairPosteriorMeans[static_cast<size_t>(s)];
-      for (long p = 1; p < numPairs; ++p) {
-        const float v = perPairPosteriorMeans[static_cast<size_t>(p * numSites + s)];
-        if (v < best) {
-          best = v;
-          arg = p;
-        }
-      }
-      minPosteriorMeans[static_cast<size_t>(s)] = best;
-      argminPosteriorMeans[static_cast<size_t>(s)] = static_cast<int>(arg);
-    }
-  }
-  if (!perPairMAPs.empty()) {
-    for (long s = 0; s < numSites; ++s) {
-      long arg = 0;
-      int best = perPairMAPs[static_cast<size_t>(s)];
-      for (long p = 1; p < numPairs; ++p) {
-        const int v = perPairMAPs[static_cast<size_t>(p * numSites + s)];
-        if (v < best) {
-          best = v;
-          arg = p;
-        }
-      }
-      minMAPs[static_cast<size_t>(s)] = best;
-      argminMAPs[static_cast<size_t>(s)] = static_cast<int>(arg);
-    }
-  }
-}
-
 // ------------------------------------------------------------------ construction
 
 namespace
 {
+static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
+
 void check(fsmc_ctx* ctx, int rc, const char* what)
 {
   if (rc != FSMC_OK) {
@@ -602,6 +490,71 @@ void putIbdText(gzFile file, int fd, const std::string& text)
     writeAll(fd, m.get());
   }
 }
+// The per-pair files.  HMM.cpp:1412-1420: `fout << matrix.topRows(actualBatchSize).format(m_eigenOutputFormat)` once per
+// BATCH, with IOFormat(FullPrecision, DontAlignCols, " ", "\n") (HMM.hpp:154): coefficients separated by a blank, rows by
+// a newline -- a separator BETWEEN rows: nothing follows a batch's last row, so the next batch's first row continues that
+// line.  Reproduced as it is (the files are the reference's, quirk included): a newline goes in front of every row that
+// is not the first of its batch.  FullPrecision for float is the stream at NumTraits<float>::digits10() = 6 significant
+// digits (Eigen 3.4, the version the reference's unpinned vcpkg dependency resolves to; general notation = "%.6g"); the
+// MAP matrix is integer.  Eigen master / 5.x print max_digits10 = 9 there: FSMC_EIGEN_FULL_PRECISION_DIGITS=9 in the
+// environment writes the file such a build of the reference writes.
+struct RowLayout {
+  size_t rows, sites;   // a flush's [rows][sites] matrix
+  uint64_t rowsBefore;  // rows the file holds already (the newline rule counts rows over the whole file)
+  uint64_t batch;       // rows of a batch
+};
+
+// the rows [lo, hi) of the matrix as text; cell(buffer, size, index) prints one coefficient
+template <typename Cell> std::string rowsText(const RowLayout& m, size_t lo, size_t hi, const Cell& cell)
+{
+  std::string text;
+  text.reserve((hi - lo) * m.sites * 8);
+  char buf[48];
+  for (size_t i = lo; i < hi; ++i) {
+    if ((m.rowsBefore + i) % m.batch != 0) {
+      text.push_back('\n');
+    }
+    for (size_t pos = 0; pos < m.sites; ++pos) {
+      if (pos) {
+        text.push_back(' ');
+      }
+      text.append(buf, static_cast<size_t>(cell(buf, sizeof(buf), i * m.sites + pos)));
+    }
+  }
+  return text;
+}
+
+// A few rows: one thread, gzwrite.  Many (a number per pair and site: 300 million for the reference's example cohort):
+// several threads format AND compress blocks of rows into gzip members of their own, written in order behind whatever
+// gzwrite had under way (putIbdText, above: one stream to every reader of gzip files).
+template <typename Cell> void writeRows(gzFile f, int fd, const RowLayout& m, const Cell& cell)
+{
+  const size_t rowsPerThread = std::max<size_t>(1, ((size_t)1 << 20) / (m.sites * 8 + 1)); // (about a MiB of text a piece)
+  const size_t nThreads = std::min<size_t>(outputThreads(), (m.rows + rowsPerThread - 1) / rowsPerThread);
+  if (fd < 0 || nThreads < 2) {
+    for (size_t lo = 0; lo < m.rows; lo += rowsPerThread) {
+      const std::string text = rowsText(m, lo, std::min(m.rows, lo + rowsPerThread), cell);
+      gzwrite(f, text.data(), static_cast<unsigned>(text.size()));
+    }
+    return;
+  }
+  gzflush(f, Z_FINISH);
+  for (size_t blockLo = 0; blockLo < m.rows; blockLo += nThreads * rowsPerThread) {
+    std::vector<std::future<std::string>> members;
+    for (size_t t = 0; t < nThreads; ++t) {
+      const size_t lo = std::min(m.rows, blockLo + t * rowsPerThread), hi = std::min(m.rows, lo + rowsPerThread);
+      if (lo < hi) {
+        members.push_back(std::async(std::launch::async, [&, lo, hi] {
+          const std::string text = rowsText(m, lo, hi, cell);
+          return gzipMember(text.data(), text.size());
+        }));
+      }
+    }
+    for (auto& mem : members) {
+      writeAll(fd, mem.get());
+    }
+  }
+}
 } // namespace
 
 void HMM::closePerPairFiles()
@@ -624,137 +577,52 @@ void HMM::updateOutputStructures()
   resetDecoding(); // HMM.cpp:1757
 }
 
-void HMM::setStorePerPairPosteriorMean(bool v)
+template <typename Assign> void HMM::changeOutputs(Assign&& assign)
 {
   flush(); // (what is queued was decoded under the old setting in the reference)
-  mStoreMean = v;
+  assign();
   updateOutputStructures();
 }
 
-void HMM::setStorePerPairMap(bool v)
+void HMM::setPairOutputs(const PairOutputs& outputs)
 {
-  flush(); // (what is queued was decoded under the old setting in the reference)
-  mStoreMap = v;
-  updateOutputStructures();
+  outputs.check(mData.sites, static_cast<long>(mDq.states));
+  changeOutputs([&] { mOutputs = outputs; });
 }
 
-void HMM::setStorePerPairPosterior(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting in the reference)
-  mStorePosterior = v;
-  updateOutputStructures();
-}
+void HMM::setStorePerPairPosteriorMean(bool v) { changeOutputs([&] { mOutputs.means = v; }); }
+void HMM::setStorePerPairMap(bool v) { changeOutputs([&] { mOutputs.maps = v; }); }
+void HMM::setStorePerPairPosterior(bool v) { changeOutputs([&] { mOutputs.posteriors = v; }); }
+void HMM::setStoreSumOfPosterior(bool v) { changeOutputs([&] { mOutputs.sumOfPosteriors = v; }); }
+void HMM::setStoreMinPosteriorMean(bool v) { changeOutputs([&] { mOutputs.minMeans = v; }); }
+void HMM::setStoreMinMap(bool v) { changeOutputs([&] { mOutputs.minMaps = v; }); }
 
-void HMM::setStoreSumOfPosterior(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting in the reference)
-  mStoreSumOfPosterior = v;
-  updateOutputStructures();
-}
-
-void HMM::setStoreMinPosteriorMean(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting)
-  mStoreMinMean = v;
-  updateOutputStructures();
-}
-
-void HMM::setStoreMinMap(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting)
-  mStoreMinMap = v;
-  updateOutputStructures();
-}
-
+// (the rest of the request passed its check when it was set: only the part that changes can be refused)
 void HMM::setSiteBins(const std::vector<int>& edges)
 {
-  if (!edges.empty()) { // (the messages of fsmc_decode_pair_bins)
-    if (edges.size() < 2) {
-      throw std::runtime_error("need one bin at least (n_bins + 1 edges)");
-    }
-    if (edges.front() < 0 || static_cast<long>(edges.back()) > static_cast<long>(mData.sites)) {
-      throw std::runtime_error("bin edges must lie in [0, sites]");
-    }
-    for (size_t b = 0; b + 1 < edges.size(); ++b) {
-      if (edges[b] >= edges[b + 1]) {
-        throw std::runtime_error("bin edges must be strictly ascending");
-      }
-    }
-  }
-  flush(); // (what is queued was decoded under the old setting)
-  mSiteBins = edges;
-  updateOutputStructures();
+  PairOutputs next = mOutputs;
+  next.siteBins = edges;
+  setPairOutputs(next);
 }
 
 void HMM::setPosteriorCdf(const std::vector<int>& tailStates, const std::vector<float>& quantiles)
 {
-  // (the messages of fsmc_decode_pair_cdf)
-  if (tailStates.size() > 8) {
-    throw std::runtime_error("at most 8 tail states a call");
-  }
-  if (quantiles.size() > 8) {
-    throw std::runtime_error("at most 8 quantiles a call");
-  }
-  for (const int c : tailStates) {
-    if (c < 1 || c > static_cast<int>(mDq.states)) {
-      throw std::runtime_error("tail state " + std::to_string(c) + " outside [1, K]");
-    }
-  }
-  for (const float q : quantiles) {
-    if (!std::isfinite(q) || !(q > 0.f) || q > 1.f) {
-      throw std::runtime_error("quantile " + std::to_string(q) + " not finite or outside (0, 1]");
-    }
-  }
-  flush(); // (what is queued was decoded under the old setting)
-  mTailStates = tailStates;
-  mQuantiles = quantiles;
-  updateOutputStructures();
+  PairOutputs next = mOutputs;
+  next.tailStates = tailStates;
+  next.quantiles = quantiles;
+  setPairOutputs(next);
 }
 
 void HMM::setTailSummaries(const std::vector<int>& tailStates, const std::vector<float>& siteWeights)
 {
-  // (the messages of fsmc_decode_pair_tail_summaries)
-  if (tailStates.size() > 8) {
-    throw std::runtime_error("at most 8 tail states a call");
-  }
-  for (const int c : tailStates) {
-    if (c < 1 || c > static_cast<int>(mDq.states)) {
-      throw std::runtime_error("tail state " + std::to_string(c) + " outside [1, K]");
-    }
-  }
-  if (!siteWeights.empty()) {
-    if (tailStates.empty()) {
-      throw std::runtime_error("site weights need tail summary times");
-    }
-    if (siteWeights.size() != static_cast<size_t>(mData.sites)) {
-      throw std::runtime_error("site weights: " + std::to_string(siteWeights.size()) + " values for " +
-                               std::to_string(mData.sites) + " sites");
-    }
-    for (size_t t = 0; t < siteWeights.size(); ++t) {
-      if (!std::isfinite(siteWeights[t])) {
-        throw std::runtime_error("site weight " + std::to_string(t) + " is not finite");
-      }
-    }
-  }
-  flush(); // (what is queued was decoded under the old setting)
-  mTailSummaryStates = tailStates;
-  mSiteWeights = siteWeights;
-  updateOutputStructures();
+  PairOutputs next = mOutputs;
+  next.tailSummaryStates = tailStates;
+  next.siteWeights = siteWeights;
+  setPairOutputs(next);
 }
 
-void HMM::setWritePerPairPosteriorMean(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting in the reference)
-  mWriteMean = v;
-  updateOutputStructures();
-}
-
-void HMM::setWritePerPairMap(bool v)
-{
-  flush(); // (what is queued was decoded under the old setting in the reference)
-  mWriteMap = v;
-  updateOutputStructures();
-}
+void HMM::setWritePerPairPosteriorMean(bool v) { changeOutputs([&] { mWriteMean = v; }); }
+void HMM::setWritePerPairMap(bool v) { changeOutputs([&] { mWriteMap = v; }); }
 
 void HMM::resetDecoding()
 {
@@ -832,7 +700,12 @@ fsmc_ctx* HMM::engine()
 
 namespace
 {
-void putIbdText(gzFile file, int fd, const std::string& text); // (below, beside openIbdFile)
+using Clock = std::chrono::steady_clock;
+double secondsSince(const Clock::time_point t0)
+{
+  return std::chrono::duration<double>(Clock::now() - t0).count();
+}
+
 // FSMC_HOST_TIMING: wall-clock marks of a job's phases on stderr (seconds since the first mark of the process)
 void hostMark(const char* what)
 {
@@ -840,9 +713,8 @@ void hostMark(const char* what)
   if (!on) {
     return;
   }
-  using Clock = std::chrono::steady_clock;
   static const Clock::time_point t0 = Clock::now();
-  std::fprintf(stderr, "[fsmc host] %8.3f s  %s\n", std::chrono::duration<double>(Clock::now() - t0).count(), what);
+  std::fprintf(stderr, "[fsmc host] %8.3f s  %s\n", secondsSince(t0), what);
 }
 } // namespace
 
@@ -1007,292 +879,20 @@ void HMM::flush()
   }
   ensureEngine();
   const size_t nPairs = mBatchBegin; // pairs covered by closed batches
-  using Clock = std::chrono::steady_clock;
-  auto since = [](const Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); };
-  Clock::time_point t0 = Clock::now();
+  const Clock::time_point t0 = Clock::now();
   check(mCtx, fsmc_worklist_upload(mCtx, mPairs.data(), nPairs, mGroups.data(), mGroups.size()),
         "fsmc_worklist_upload");
-  mTimeUpload += since(t0);
+  mTimeUpload += secondsSince(t0);
   hostMark("flush: work list uploaded");
 
   if (mParams.FastSMC) {
-    uint32_t flags = 0;
-    if (mParams.doPerPairPosteriorMean) flags |= FSMC_WANT_MEAN;
-    if (mParams.doPerPairMAP) flags |= FSMC_WANT_MAP;
-    t0 = Clock::now();
-    check(mCtx, fsmc_decode_ibd_launch(mCtx, mModel, flags), "fsmc_decode_ibd_launch");
-    hostMark("flush: kernel launched");
-    std::vector<fsmc_ibd_record> recs(std::max<size_t>(1024, 4 * nPairs));
-    size_t n = 0;
-    int rc = fsmc_decode_ibd_fetch(mCtx, recs.data(), recs.size(), &n);
-    if (rc == FSMC_EOVERFLOW) {
-      recs.resize(n);
-      rc = fsmc_decode_ibd_fetch(mCtx, recs.data(), recs.size(), &n);
-    }
-    check(mCtx, rc, "fsmc_decode_ibd_fetch");
-    mTimeDecode += since(t0);
-    hostMark("flush: records fetched");
-    t0 = Clock::now();
-    if (mIbdFile && !mParams.BIN_OUT && n >= 512) {
-      // a flush's text in one piece (formatted by several threads), then what writeIbd does beside the text
-      std::vector<uint32_t> pairOf(n);
-      for (size_t i = 0; i < n; ++i) {
-        pairOf[i] = recs[i].pair;
-      }
-      putIbdText(mIbdFile, mIbdFd, formatIbdRecords(mPairs.data(), recs.data(), n, pairOf.data()));
-      mSegmentsDetected += n;
-      if (mKeepRecords) {
-        for (size_t i = 0; i < n; ++i) {
-          mKeptOrdinals.push_back(mPairsFlushed + recs[i].pair);
-          mKeptRecords.push_back(recs[i]);
-          mKeptPairs.push_back(mPairs[recs[i].pair]);
-        }
-      }
-    } else {
-      for (size_t i = 0; i < n; ++i) {
-        if (mKeepRecords) {
-          mKeptOrdinals.push_back(mPairsFlushed + recs[i].pair);
-        }
-        writeIbd(mPairs[recs[i].pair], recs[i]);
-      }
-    }
-    mTimeWrite += since(t0);
+    emitIbdRecords(fetchIbdRecords(nPairs));
   }
   if (mParams.doPosteriorSums || mParams.doMajorMinorPosteriorSums) {
-    const bool mm = mParams.doMajorMinorPosteriorSums;
-    // the reference sums a WHOLE batch over its pairs and then adds it (HMM.cpp:1054-1073): the groups of a batch of more
-    // than 64 pairs share one running sum on the device
-    mBatchFirstGroup.push_back(static_cast<uint32_t>(mGroups.size()));
-    check(mCtx,
-          fsmc_decode_sums_batches(mCtx, mModel, mBatchFirstGroup.data(), mBatchFirstGroup.size() - 1,
-                                   mParams.doPosteriorSums ? mReturn.sumOverPairs.data() : nullptr,
-                                   mm ? mReturn.sumOverPairs00.data() : nullptr,
-                                   mm ? mReturn.sumOverPairs01.data() : nullptr,
-                                   mm ? mReturn.sumOverPairs11.data() : nullptr),
-          "fsmc_decode_sums_batches");
+    flushPosteriorSums();
   }
-  const bool writeFiles = mMeanFile || mMapFile;
-  // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
-  const bool minMeanOnDevice = mStoreMinMean && !mStoreMean, minMapOnDevice = mStoreMinMap && !mStoreMap;
-  const bool binsOnDevice = !mSiteBins.empty();
-  const bool cdfOnDevice = !mTailStates.empty() || !mQuantiles.empty();
-  const bool tailSummariesOnDevice = !mTailSummaryStates.empty();
-  const bool storeAny = mStoreMean || mStoreMap || mStorePosterior || mStoreSumOfPosterior || minMeanOnDevice ||
-                        minMapOnDevice || binsOnDevice || cdfOnDevice || tailSummariesOnDevice;
-  if (!mParams.FastSMC && (storeAny || writeFiles)) {
-    // writePerPairOutput (HMM.cpp:1360-1458)
-    const size_t S = static_cast<size_t>(mData.sites);
-    auto& R = mPairsReturn;
-    const size_t base = R.numWritten;
-    if (storeAny && base + nPairs > static_cast<size_t>(R.numPairs)) {
-      throw std::runtime_error("more pairs decoded than the return structure was initialised for");
-    }
-    const bool wantMean = mStoreMean || mStorePosterior || mStoreSumOfPosterior || mMeanFile;
-    std::vector<float> mean(wantMean ? nPairs * S : 0);
-    std::vector<int32_t> map(mStoreMap || mStoreMean || mMapFile ? nPairs * S : 0);
-    if (!mean.empty() || !map.empty()) {
-      check(mCtx,
-            fsmc_decode_per_pair(mCtx, mModel, mExpectedCoalTimes.data(), mean.empty() ? nullptr : mean.data(),
-                                 map.empty() ? nullptr : map.data()),
-            "fsmc_decode_per_pair");
-    }
-    if (minMeanOnDevice || minMapOnDevice) {
-      // the chain of finaliseCalculations over all pairs of the call, flush after flush: 4 * S bytes per output cross
-      // the bus, the rows stay on the device
-      if ((minMeanOnDevice && R.minPosteriorMeans.size() != S) || (minMapOnDevice && R.minMAPs.size() != S)) {
-        throw std::runtime_error("the return structure was not initialised for the minima asked for");
-      }
-      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
-      check(mCtx,
-            fsmc_decode_pair_minima(mCtx, mModel, mExpectedCoalTimes.data(), static_cast<uint64_t>(base),
-                                    minMeanOnDevice ? R.minPosteriorMeans.data() : nullptr,
-                                    minMeanOnDevice ? R.argminPosteriorMeans.data() : nullptr,
-                                    minMapOnDevice ? R.minMAPs.data() : nullptr,
-                                    minMapOnDevice ? R.argminMAPs.data() : nullptr),
-            "fsmc_decode_pair_minima");
-    }
-    if (binsOnDevice) {
-      // per pair the summaries over the bins, flush after flush at the pairs written so far: 20 bytes a pair and bin
-      // cross the bus, the rows stay on the device (where the rows are stored as well, this decodes the flush again)
-      const size_t nBins = mSiteBins.size() - 1;
-      if (R.binEdges != mSiteBins || R.binMeanPosteriorMeans.size() != static_cast<size_t>(R.numPairs) * nBins) {
-        throw std::runtime_error("the return structure was not initialised for the site bins asked for");
-      }
-      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
-      const size_t at = base * nBins;
-      check(mCtx,
-            fsmc_decode_pair_bins(mCtx, mModel, mExpectedCoalTimes.data(), mSiteBins.data(), nBins,
-                                  R.binMeanPosteriorMeans.data() + at, R.binMinPosteriorMeans.data() + at,
-                                  R.binArgminPosteriorMeans.data() + at, R.binMinMAPs.data() + at,
-                                  R.binArgminMAPs.data() + at),
-            "fsmc_decode_pair_bins");
-    }
-    if (cdfOnDevice) {
-      // per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far:
-      // 4 bytes a pair-site and output cross the bus, the posterior tables stay on the device (where the tables are
-      // stored as well, this decodes the flush again)
-      const size_t rowCells = static_cast<size_t>(R.numPairs) * S;
-      if (R.tailStates != mTailStates || R.quantiles != mQuantiles ||
-          R.perPairTailProbabilities.size() != mTailStates.size() * rowCells ||
-          R.perPairQuantileStates.size() != mQuantiles.size() * rowCells) {
-        throw std::runtime_error("the return structure was not initialised for the tail states and quantiles asked for");
-      }
-      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
-      std::vector<float*> tailRows(mTailStates.size());
-      std::vector<int32_t*> quantileRows(mQuantiles.size());
-      for (size_t j = 0; j < tailRows.size(); ++j) {
-        tailRows[j] = R.perPairTailProbabilities.data() + j * rowCells + base * S;
-      }
-      for (size_t j = 0; j < quantileRows.size(); ++j) {
-        quantileRows[j] = R.perPairQuantileStates.data() + j * rowCells + base * S;
-      }
-      check(mCtx,
-            fsmc_decode_pair_cdf(mCtx, mModel, mTailStates.data(), mTailStates.size(), tailRows.data(), mQuantiles.data(),
-                                 mQuantiles.size(), quantileRows.data()),
-            "fsmc_decode_pair_cdf");
-    }
-    if (tailSummariesOnDevice) {
-      // the tail probabilities summed over the pairs -- the fp64 chain of the whole call, flush after flush -- and, with
-      // site bins, reduced per pair over the bins at the pairs written so far: 8 * S bytes a cut cross the bus each way
-      // and 4 bytes a pair, cut, bin and output come back, the tail rows stay on the device
-      const size_t nT = mTailSummaryStates.size();
-      const size_t nBins = mSiteBins.empty() ? 0 : mSiteBins.size() - 1;
-      const bool lengths = nBins > 0 && !mSiteWeights.empty();
-      const size_t cells = static_cast<size_t>(R.numPairs) * nBins;
-      if (R.tailSummaryStates != mTailSummaryStates || R.sumOfTailProbabilities.size() != nT * S ||
-          R.binTailMeans.size() != nT * cells || (lengths && R.binTailLengths.size() != nT * cells) ||
-          (nBins > 0 && R.binEdges != mSiteBins)) {
-        throw std::runtime_error("the return structure was not initialised for the tail summaries asked for");
-      }
-      static_assert(sizeof(int) == sizeof(int32_t), "the return structure's int vectors are the ABI's int32 arrays");
-      // the ABI's bin outputs are [cut][pairs of the work list][bins]: a flush's cells pass through a buffer of that
-      // shape into the call's [cut][numPairs][bins] at the pairs written so far
-      std::vector<float> means(nT * nPairs * nBins), lens(lengths ? nT * nPairs * nBins : 0);
-      check(mCtx,
-            fsmc_decode_pair_tail_summaries(mCtx, mModel, mTailSummaryStates.data(), nT, R.sumOfTailProbabilities.data(),
-                                            nBins ? mSiteBins.data() : nullptr, nBins, nBins ? means.data() : nullptr,
-                                            lengths ? mSiteWeights.data() : nullptr, lengths ? lens.data() : nullptr),
-            "fsmc_decode_pair_tail_summaries");
-      for (size_t j = 0; nBins > 0 && j < nT; ++j) {
-        std::copy(means.begin() + static_cast<std::ptrdiff_t>(j * nPairs * nBins),
-                  means.begin() + static_cast<std::ptrdiff_t>((j + 1) * nPairs * nBins),
-                  R.binTailMeans.begin() + static_cast<std::ptrdiff_t>(j * cells + base * nBins));
-        if (lengths) {
-          std::copy(lens.begin() + static_cast<std::ptrdiff_t>(j * nPairs * nBins),
-                    lens.begin() + static_cast<std::ptrdiff_t>((j + 1) * nPairs * nBins),
-                    R.binTailLengths.begin() + static_cast<std::ptrdiff_t>(j * cells + base * nBins));
-        }
-      }
-    }
-    if (mStorePosterior || mStoreSumOfPosterior) {
-      // full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S]
-      // table and continues the sum over pairs in pair order -- nothing but those tables crosses the bus
-      std::vector<float*> rows;
-      if (mStorePosterior) {
-        rows.resize(nPairs);
-        for (size_t i = 0; i < nPairs; ++i) {
-          rows[i] = R.perPairPosteriors[base + i].data();
-        }
-      }
-      check(mCtx,
-            fsmc_decode_pair_posteriors(mCtx, mModel, mExpectedCoalTimes.data(), mStorePosterior ? rows.data() : nullptr,
-                                        mStoreSumOfPosterior ? R.sumOfPosteriors.data() : nullptr),
-            "fsmc_decode_pair_posteriors");
-    }
-    if (writeFiles) {
-      // HMM.cpp:1412-1420: `fout << matrix.topRows(actualBatchSize).format(m_eigenOutputFormat)` once per BATCH, with
-      // IOFormat(FullPrecision, DontAlignCols, " ", "\n") (HMM.hpp:154): coefficients separated by a blank, rows by a
-      // newline -- a separator BETWEEN rows: nothing follows a batch's last row, so the next batch's first row
-      // continues that line.  Reproduced as it is (the files are the reference's, quirk included): a newline goes in
-      // front of every row that is not the first of its batch.  FullPrecision for float is the stream at
-      // NumTraits<float>::digits10() = 6 significant digits (Eigen 3.4, the version the reference's unpinned vcpkg
-      // dependency resolves to; general notation = "%.6g"); the MAP matrix is integer.  Eigen master / 5.x print
-      // max_digits10 = 9 there: FSMC_EIGEN_FULL_PRECISION_DIGITS=9 in the environment writes the file such a build of
-      // the reference writes.
-      const auto B = static_cast<uint64_t>(mBatchSize);
-      // the rows of pairs [lo, hi) as text (the newline rule above counts rows over the whole file)
-      auto rowsText = [&](size_t lo, size_t hi, auto&& cell) {
-        std::string text;
-        text.reserve((hi - lo) * S * 8);
-        char buf[48];
-        for (size_t i = lo; i < hi; ++i) {
-          if ((mPerPairRows + i) % B != 0) {
-            text.push_back('\n');
-          }
-          for (size_t pos = 0; pos < S; ++pos) {
-            if (pos) {
-              text.push_back(' ');
-            }
-            text.append(buf, static_cast<size_t>(cell(buf, sizeof(buf), i * S + pos)));
-          }
-        }
-        return text;
-      };
-      // A few rows: one thread, gzwrite.  Many (a number per pair and site: 300 million for the reference's example
-      // cohort): several threads format AND compress blocks of rows into gzip members of their own, written in order
-      // behind whatever gzwrite had under way (putIbdText, above: one stream to every reader of gzip files).
-      auto writeRows = [&](gzFile f, int fd, auto&& cell) {
-        const size_t rowsPerThread = std::max<size_t>(1, ((size_t)1 << 20) / (S * 8 + 1)); // (about a MiB of text a piece)
-        const size_t nThreads = std::min<size_t>(outputThreads(), (nPairs + rowsPerThread - 1) / rowsPerThread);
-        if (fd < 0 || nThreads < 2) {
-          for (size_t lo = 0; lo < nPairs; lo += rowsPerThread) {
-            const std::string text = rowsText(lo, std::min(nPairs, lo + rowsPerThread), cell);
-            gzwrite(f, text.data(), static_cast<unsigned>(text.size()));
-          }
-          return;
-        }
-        gzflush(f, Z_FINISH);
-        for (size_t blockLo = 0; blockLo < nPairs; blockLo += nThreads * rowsPerThread) {
-          std::vector<std::future<std::string>> members;
-          for (size_t t = 0; t < nThreads; ++t) {
-            const size_t lo = std::min(nPairs, blockLo + t * rowsPerThread), hi = std::min(nPairs, lo + rowsPerThread);
-            if (lo < hi) {
-              members.push_back(std::async(std::launch::async, [&, lo, hi] {
-                const std::string text = rowsText(lo, hi, cell);
-                return gzipMember(text.data(), text.size());
-              }));
-            }
-          }
-          for (auto& m : members) {
-            writeAll(fd, m.get());
-          }
-        }
-      };
-      if (mMeanFile) {
-        int digits = 6;
-        if (const char* v = std::getenv("FSMC_EIGEN_FULL_PRECISION_DIGITS")) {
-          const int d = std::atoi(v);
-          if (d != 6 && d != 9) {
-            throw std::runtime_error("FSMC_EIGEN_FULL_PRECISION_DIGITS is 6 (Eigen 3.4) or 9 (Eigen 5)");
-          }
-          digits = d;
-        }
-        writeRows(mMeanFile, mMeanFd, [&](char* b, size_t n, size_t idx) {
-          return std::snprintf(b, n, "%.*g", digits, static_cast<double>(mean[idx]));
-        });
-      }
-      if (mMapFile) {
-        writeRows(mMapFile, mMapFd, [&](char* b, size_t n, size_t idx) { return std::snprintf(b, n, "%d", map[idx]); });
-      }
-      mPerPairRows += nPairs;
-    }
-    for (size_t i = 0; storeAny && i < nPairs; ++i) {
-      const auto [indA, hapA] = hapToDipId(mPairs[i].hap_a);
-      const auto [indB, hapB] = hapToDipId(mPairs[i].hap_b);
-      R.perPairIndices.at(base + i) =
-          std::make_tuple(static_cast<unsigned long>(mPairs[i].hap_a), indPlusHapToCombinedId(mData.IIDList.at(indA), hapA),
-                          static_cast<unsigned long>(mPairs[i].hap_b), indPlusHapToCombinedId(mData.IIDList.at(indB), hapB));
-      if (mStoreMean) {
-        std::copy(mean.begin() + i * S, mean.begin() + (i + 1) * S, R.perPairPosteriorMeans.begin() + (base + i) * S);
-        // the reference stores the MAP rows under the posterior-mean flag (HMM.cpp:1447-1449)
-        if (!R.perPairMAPs.empty() && !map.empty()) {
-          std::copy(map.begin() + i * S, map.begin() + (i + 1) * S, R.perPairMAPs.begin() + (base + i) * S);
-        }
-      }
-    }
-    if (storeAny) {
-      R.numWritten += nPairs;
-    }
+  if (!mParams.FastSMC && (mOutputs.any() || mMeanFile || mMapFile)) {
+    flushPairOutputs(nPairs);
   }
 
   // keep any pairs of a still-open batch
@@ -1302,6 +902,280 @@ void HMM::flush()
   mGroups.clear();
   mBatchFirstGroup.clear();
   mBatchBegin = 0;
+}
+
+std::vector<fsmc_ibd_record> HMM::fetchIbdRecords(size_t nPairs)
+{
+  uint32_t flags = 0;
+  if (mParams.doPerPairPosteriorMean) flags |= FSMC_WANT_MEAN;
+  if (mParams.doPerPairMAP) flags |= FSMC_WANT_MAP;
+  const Clock::time_point t0 = Clock::now();
+  check(mCtx, fsmc_decode_ibd_launch(mCtx, mModel, flags), "fsmc_decode_ibd_launch");
+  hostMark("flush: kernel launched");
+  std::vector<fsmc_ibd_record> recs(std::max<size_t>(1024, 4 * nPairs));
+  size_t n = 0;
+  int rc = fsmc_decode_ibd_fetch(mCtx, recs.data(), recs.size(), &n);
+  if (rc == FSMC_EOVERFLOW) {
+    recs.resize(n);
+    rc = fsmc_decode_ibd_fetch(mCtx, recs.data(), recs.size(), &n);
+  }
+  check(mCtx, rc, "fsmc_decode_ibd_fetch");
+  recs.resize(n);
+  mTimeDecode += secondsSince(t0);
+  hostMark("flush: records fetched");
+  return recs;
+}
+
+void HMM::emitIbdRecords(const std::vector<fsmc_ibd_record>& recs)
+{
+  const Clock::time_point t0 = Clock::now();
+  const size_t n = recs.size();
+  if (mIbdFile && !mParams.BIN_OUT && n >= 512) {
+    // a flush's text in one piece (formatted by several threads), then what writeIbd does beside the text
+    std::vector<uint32_t> pairOf(n);
+    for (size_t i = 0; i < n; ++i) {
+      pairOf[i] = recs[i].pair;
+    }
+    putIbdText(mIbdFile, mIbdFd, formatIbdRecords(mPairs.data(), recs.data(), n, pairOf.data()));
+    mSegmentsDetected += n;
+    if (mKeepRecords) {
+      for (size_t i = 0; i < n; ++i) {
+        mKeptOrdinals.push_back(mPairsFlushed + recs[i].pair);
+        mKeptRecords.push_back(recs[i]);
+        mKeptPairs.push_back(mPairs[recs[i].pair]);
+      }
+    }
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      if (mKeepRecords) {
+        mKeptOrdinals.push_back(mPairsFlushed + recs[i].pair);
+      }
+      writeIbd(mPairs[recs[i].pair], recs[i]);
+    }
+  }
+  mTimeWrite += secondsSince(t0);
+}
+
+void HMM::flushPosteriorSums()
+{
+  const bool mm = mParams.doMajorMinorPosteriorSums;
+  // the reference sums a WHOLE batch over its pairs and then adds it (HMM.cpp:1054-1073): the groups of a batch of more
+  // than 64 pairs share one running sum on the device
+  mBatchFirstGroup.push_back(static_cast<uint32_t>(mGroups.size()));
+  check(mCtx,
+        fsmc_decode_sums_batches(mCtx, mModel, mBatchFirstGroup.data(), mBatchFirstGroup.size() - 1,
+                                 mParams.doPosteriorSums ? mReturn.sumOverPairs.data() : nullptr,
+                                 mm ? mReturn.sumOverPairs00.data() : nullptr,
+                                 mm ? mReturn.sumOverPairs01.data() : nullptr,
+                                 mm ? mReturn.sumOverPairs11.data() : nullptr),
+        "fsmc_decode_sums_batches");
+}
+
+// writePerPairOutput (HMM.cpp:1360-1458): what a flush of the pair-list decode leaves in the return structure, at the
+// pairs written so far, and in the per-pair files.  Every device consumer decodes the flush's work list again.
+void HMM::flushPairOutputs(size_t nPairs)
+{
+  const PairOutputs& o = mOutputs;
+  const size_t S = static_cast<size_t>(mData.sites);
+  if (o.any() && mPairsReturn.numWritten + nPairs > static_cast<size_t>(mPairsReturn.numPairs)) {
+    throw std::runtime_error("more pairs decoded than the return structure was initialised for");
+  }
+  const bool wantMean = o.means || o.posteriors || o.sumOfPosteriors || mMeanFile;
+  std::vector<float> mean(wantMean ? nPairs * S : 0);
+  std::vector<int32_t> map(o.maps || o.means || mMapFile ? nPairs * S : 0);
+  if (!mean.empty() || !map.empty()) {
+    check(mCtx,
+          fsmc_decode_per_pair(mCtx, mModel, mExpectedCoalTimes.data(), mean.empty() ? nullptr : mean.data(),
+                               map.empty() ? nullptr : map.data()),
+          "fsmc_decode_per_pair");
+  }
+  if (o.minMeansOnDevice() || o.minMapsOnDevice()) {
+    flushPairMinima();
+  }
+  if (!o.siteBins.empty()) {
+    flushPairBins();
+  }
+  if (o.cdf()) {
+    flushPairCdf();
+  }
+  if (!o.tailSummaryStates.empty()) {
+    flushPairTailSummaries(nPairs);
+  }
+  if (o.posteriors || o.sumOfPosteriors) {
+    flushPairPosteriors(nPairs);
+  }
+  if (mMeanFile || mMapFile) {
+    writePerPairFiles(nPairs, mean, map);
+  }
+  if (o.any()) {
+    copyPairRows(nPairs, mean, map);
+    mPairsReturn.numWritten += nPairs;
+  }
+}
+
+// the chain of finaliseCalculations over all pairs of the call, flush after flush: 4 * S bytes per output cross the bus,
+// the rows stay on the device
+void HMM::flushPairMinima()
+{
+  auto& R = mPairsReturn;
+  const size_t S = static_cast<size_t>(mData.sites);
+  const bool mean = mOutputs.minMeansOnDevice(), map = mOutputs.minMapsOnDevice();
+  if ((mean && R.minPosteriorMeans.size() != S) || (map && R.minMAPs.size() != S)) {
+    throw std::runtime_error("the return structure was not initialised for the minima asked for");
+  }
+  check(mCtx,
+        fsmc_decode_pair_minima(mCtx, mModel, mExpectedCoalTimes.data(), static_cast<uint64_t>(R.numWritten),
+                                mean ? R.minPosteriorMeans.data() : nullptr,
+                                mean ? R.argminPosteriorMeans.data() : nullptr, map ? R.minMAPs.data() : nullptr,
+                                map ? R.argminMAPs.data() : nullptr),
+        "fsmc_decode_pair_minima");
+}
+
+// per pair the summaries over the bins, flush after flush at the pairs written so far: 20 bytes a pair and bin cross the
+// bus, the rows stay on the device (where the rows are stored as well, this decodes the flush again)
+void HMM::flushPairBins()
+{
+  auto& R = mPairsReturn;
+  const std::vector<int>& edges = mOutputs.siteBins;
+  const size_t nBins = edges.size() - 1;
+  if (R.request.siteBins != edges || R.binMeanPosteriorMeans.size() != static_cast<size_t>(R.numPairs) * nBins) {
+    throw std::runtime_error("the return structure was not initialised for the site bins asked for");
+  }
+  const size_t at = R.numWritten * nBins;
+  check(mCtx,
+        fsmc_decode_pair_bins(mCtx, mModel, mExpectedCoalTimes.data(), edges.data(), nBins,
+                              R.binMeanPosteriorMeans.data() + at, R.binMinPosteriorMeans.data() + at,
+                              R.binArgminPosteriorMeans.data() + at, R.binMinMAPs.data() + at,
+                              R.binArgminMAPs.data() + at),
+        "fsmc_decode_pair_bins");
+}
+
+// per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far: 4 bytes a
+// pair-site and output cross the bus, the posterior tables stay on the device (where the tables are stored as well, this
+// decodes the flush again)
+void HMM::flushPairCdf()
+{
+  auto& R = mPairsReturn;
+  const std::vector<int>& cuts = mOutputs.tailStates;
+  const std::vector<float>& quantiles = mOutputs.quantiles;
+  const size_t S = static_cast<size_t>(mData.sites);
+  const size_t rowCells = static_cast<size_t>(R.numPairs) * S;
+  if (R.request.tailStates != cuts || R.request.quantiles != quantiles ||
+      R.perPairTailProbabilities.size() != cuts.size() * rowCells ||
+      R.perPairQuantileStates.size() != quantiles.size() * rowCells) {
+    throw std::runtime_error("the return structure was not initialised for the tail states and quantiles asked for");
+  }
+  std::vector<float*> tailRows(cuts.size());
+  std::vector<int32_t*> quantileRows(quantiles.size());
+  for (size_t j = 0; j < tailRows.size(); ++j) {
+    tailRows[j] = R.perPairTailProbabilities.data() + j * rowCells + R.numWritten * S;
+  }
+  for (size_t j = 0; j < quantileRows.size(); ++j) {
+    quantileRows[j] = R.perPairQuantileStates.data() + j * rowCells + R.numWritten * S;
+  }
+  check(mCtx,
+        fsmc_decode_pair_cdf(mCtx, mModel, cuts.data(), cuts.size(), tailRows.data(), quantiles.data(),
+                             quantiles.size(), quantileRows.data()),
+        "fsmc_decode_pair_cdf");
+}
+
+// the tail probabilities summed over the pairs -- the fp64 chain of the whole call, flush after flush -- and, with site
+// bins, reduced per pair over the bins at the pairs written so far: 8 * S bytes a cut cross the bus each way and 4 bytes a
+// pair, cut, bin and output come back, the tail rows stay on the device
+void HMM::flushPairTailSummaries(size_t nPairs)
+{
+  auto& R = mPairsReturn;
+  const PairOutputs& o = mOutputs;
+  const size_t S = static_cast<size_t>(mData.sites);
+  const size_t nT = o.tailSummaryStates.size();
+  const size_t nBins = o.siteBins.empty() ? 0 : o.siteBins.size() - 1;
+  const bool lengths = nBins > 0 && !o.siteWeights.empty();
+  const size_t cells = static_cast<size_t>(R.numPairs) * nBins;
+  if (R.request.tailSummaryStates != o.tailSummaryStates || R.sumOfTailProbabilities.size() != nT * S ||
+      R.binTailMeans.size() != nT * cells || (lengths && R.binTailLengths.size() != nT * cells) ||
+      (nBins > 0 && R.request.siteBins != o.siteBins)) {
+    throw std::runtime_error("the return structure was not initialised for the tail summaries asked for");
+  }
+  // the ABI's bin outputs are [cut][pairs of the work list][bins]: a flush's cells pass through a buffer of that shape
+  // into the call's [cut][numPairs][bins] at the pairs written so far
+  const size_t flushCells = nPairs * nBins;
+  std::vector<float> means(nT * flushCells), lens(lengths ? nT * flushCells : 0);
+  check(mCtx,
+        fsmc_decode_pair_tail_summaries(mCtx, mModel, o.tailSummaryStates.data(), nT, R.sumOfTailProbabilities.data(),
+                                        nBins ? o.siteBins.data() : nullptr, nBins, nBins ? means.data() : nullptr,
+                                        lengths ? o.siteWeights.data() : nullptr, lengths ? lens.data() : nullptr),
+        "fsmc_decode_pair_tail_summaries");
+  for (size_t j = 0; nBins > 0 && j < nT; ++j) {
+    const size_t at = j * cells + R.numWritten * nBins;
+    std::copy_n(means.begin() + static_cast<std::ptrdiff_t>(j * flushCells), flushCells,
+                R.binTailMeans.begin() + static_cast<std::ptrdiff_t>(at));
+    if (lengths) {
+      std::copy_n(lens.begin() + static_cast<std::ptrdiff_t>(j * flushCells), flushCells,
+                  R.binTailLengths.begin() + static_cast<std::ptrdiff_t>(at));
+    }
+  }
+}
+
+// full posteriors (times expected coalescence time, HMM.cpp:1382-1388): the device writes every pair's [K][S] table and
+// continues the sum over pairs in pair order -- nothing but those tables crosses the bus
+void HMM::flushPairPosteriors(size_t nPairs)
+{
+  auto& R = mPairsReturn;
+  std::vector<float*> rows;
+  if (mOutputs.posteriors) {
+    rows.resize(nPairs);
+    for (size_t i = 0; i < nPairs; ++i) {
+      rows[i] = R.perPairPosteriors[R.numWritten + i].data();
+    }
+  }
+  check(mCtx,
+        fsmc_decode_pair_posteriors(mCtx, mModel, mExpectedCoalTimes.data(), mOutputs.posteriors ? rows.data() : nullptr,
+                                    mOutputs.sumOfPosteriors ? R.sumOfPosteriors.data() : nullptr),
+        "fsmc_decode_pair_posteriors");
+}
+
+// HMM.cpp:1412-1420: the flush's rows into the per-pair files (rowsText: their format)
+void HMM::writePerPairFiles(size_t nPairs, const std::vector<float>& mean, const std::vector<int32_t>& map)
+{
+  const RowLayout rows{nPairs, static_cast<size_t>(mData.sites), mPerPairRows, static_cast<uint64_t>(mBatchSize)};
+  if (mMeanFile) {
+    int digits = 6;
+    if (const char* v = std::getenv("FSMC_EIGEN_FULL_PRECISION_DIGITS")) {
+      const int d = std::atoi(v);
+      if (d != 6 && d != 9) {
+        throw std::runtime_error("FSMC_EIGEN_FULL_PRECISION_DIGITS is 6 (Eigen 3.4) or 9 (Eigen 5)");
+      }
+      digits = d;
+    }
+    writeRows(mMeanFile, mMeanFd, rows, [&](char* b, size_t n, size_t idx) {
+      return std::snprintf(b, n, "%.*g", digits, static_cast<double>(mean[idx]));
+    });
+  }
+  if (mMapFile) {
+    writeRows(mMapFile, mMapFd, rows, [&](char* b, size_t n, size_t idx) { return std::snprintf(b, n, "%d", map[idx]); });
+  }
+  mPerPairRows += nPairs;
+}
+
+// the pairs' indices and IDs and, where they are stored, their mean / MAP rows into the return structure
+void HMM::copyPairRows(size_t nPairs, const std::vector<float>& mean, const std::vector<int32_t>& map)
+{
+  auto& R = mPairsReturn;
+  const size_t S = static_cast<size_t>(mData.sites), base = R.numWritten;
+  for (size_t i = 0; i < nPairs; ++i) {
+    const auto [indA, hapA] = hapToDipId(mPairs[i].hap_a);
+    const auto [indB, hapB] = hapToDipId(mPairs[i].hap_b);
+    R.perPairIndices.at(base + i) =
+        std::make_tuple(static_cast<unsigned long>(mPairs[i].hap_a), indPlusHapToCombinedId(mData.IIDList.at(indA), hapA),
+                        static_cast<unsigned long>(mPairs[i].hap_b), indPlusHapToCombinedId(mData.IIDList.at(indB), hapB));
+    if (mOutputs.means) {
+      std::copy(mean.begin() + i * S, mean.begin() + (i + 1) * S, R.perPairPosteriorMeans.begin() + (base + i) * S);
+      // the reference stores the MAP rows under the posterior-mean flag (HMM.cpp:1447-1449)
+      if (!R.perPairMAPs.empty() && !map.empty()) {
+        std::copy(map.begin() + i * S, map.begin() + (i + 1) * S, R.perPairMAPs.begin() + (base + i) * S);
+      }
+    }
+  }
 }
 
 void HMM::setShard(int rank, int world)

@@ -18,6 +18,7 @@
 #include "data.hpp"
 #include "decoding_params.hpp"
 #include "decoding_quantities.hpp"
+#include "pair_outputs.hpp"
 
 namespace fsmc_host
 {
@@ -36,53 +37,6 @@ struct DecodingReturnValues {
   int sites = 0;
   unsigned int states = 0;
   std::vector<bool> siteWasFlippedDuringFolding;
-};
-
-// DecodePairsReturnStruct.hpp:29-124; matrices row-major
-struct DecodePairsReturnStruct {
-  std::vector<std::tuple<unsigned long, std::string, unsigned long, std::string>> perPairIndices;
-  std::vector<std::vector<float>> perPairPosteriors; // per pair [states][sites]
-  std::vector<float> sumOfPosteriors;                // [states][sites]
-  std::vector<float> perPairPosteriorMeans;          // [pairs][sites]
-  std::vector<float> minPosteriorMeans;              // [sites]
-  std::vector<int> argminPosteriorMeans;             // [sites]
-  std::vector<int> perPairMAPs;                      // [pairs][sites]
-  std::vector<int> minMAPs, argminMAPs;              // [sites]
-  long numPairs = 0, numSites = 0, numStates = 0;
-  bool storeFullPosteriors = false, storeSumOfPosteriors = false, storePerPairPosteriorMeans = false,
-       storePerPairMAPs = false;
-  // the four [sites] minima without the [pairs][sites] matrices (computed on the device, fsmc_decode_pair_minima)
-  bool storeMinPosteriorMeans = false, storeMinMAPs = false;
-  // per pair, summaries of the mean / MAP rows over bins of sites (computed on the device, fsmc_decode_pair_bins): bin b
-  // is sites [binEdges[b], binEdges[b + 1]); the five matrices are [pairs][bins], empty without bins
-  std::vector<int> binEdges;
-  std::vector<float> binMeanPosteriorMeans, binMinPosteriorMeans;
-  std::vector<int> binArgminPosteriorMeans, binMinMAPs, binArgminMAPs;
-  // per pair and site, where the posterior mass lies (computed on the device, fsmc_decode_pair_cdf): the sum of the
-  // posterior over the first tailStates[j] states (tailTimes[j]: the time in generations the cut was made from), and the
-  // smallest state at which that running sum reaches quantiles[j]; [tails][pairs][sites] and [quantiles][pairs][sites]
-  std::vector<float> tailTimes;
-  std::vector<int> tailStates;
-  std::vector<float> quantiles;
-  std::vector<float> perPairTailProbabilities;
-  std::vector<int> perPairQuantileStates;
-  // the tail probabilities reduced on the device, their rows not stored (fsmc_decode_pair_tail_summaries): per site the
-  // fp64 sum over the pairs in pair order, [tails][sites]; per pair the mean over each bin of binEdges and, with site
-  // weights, the weighted sum over it, [tails][pairs][bins] (empty without bins / without weights)
-  std::vector<float> tailSummaryTimes;
-  std::vector<int> tailSummaryStates;
-  std::vector<float> siteWeights;
-  std::vector<double> sumOfTailProbabilities;
-  std::vector<float> binTailMeans, binTailLengths;
-  size_t numWritten = 0;
-
-  void initialise(const std::vector<unsigned long>& hapsA, const std::vector<unsigned long>& hapsB, long sites,
-                  long states, bool fullPosteriors, bool sumOfPost, bool perPairMeans, bool perPairMaps,
-                  bool minMeans = false, bool minMaps = false, const std::vector<int>& siteBins = {},
-                  const std::vector<float>& tailTimesIn = {}, const std::vector<int>& tailStatesIn = {},
-                  const std::vector<float>& quantilesIn = {}, const std::vector<float>& tailSummaryTimesIn = {},
-                  const std::vector<int>& tailSummaryStatesIn = {}, const std::vector<float>& siteWeightsIn = {});
-  void finaliseCalculations();
 };
 
 // The constant inputs of the path as the constructor leaves them (what fsmc_model_create receives).
@@ -152,9 +106,13 @@ public:
   // (TESTS/test_HMM.cpp:49-79)
   std::vector<PairObservations> getBatchBuffer() const;
 
-  // Every setStore* / setWrite* setter ends in updateOutputStructures() -> resetDecoding() as in the reference
-  // (HMM.cpp:1733-1757, 1759-1800): the posterior sums are zeroed and the per-pair files reopened (truncated).  Full
-  // batches the reference would have decoded by then are decoded first (flush).
+  // Every setter of an output ends in updateOutputStructures() -> resetDecoding() as in the reference (HMM.cpp:1733-1757,
+  // 1759-1800): the posterior sums are zeroed and the per-pair files reopened (truncated).  Full batches the reference
+  // would have decoded by then are decoded first (flush), under the old setting.
+  //
+  // everything a pair-list decode stores, at once (ASMC::decodePairs): checked (PairOutputs::check) before anything is
+  // touched, then one flush and one reset; the setStore* / setSiteBins / ... setters below change their part of it
+  void setPairOutputs(const PairOutputs& outputs);
   void setStorePerPairPosteriorMean(bool v);
   void setStorePerPairMap(bool v);
   void setStorePerPairPosterior(bool v);
@@ -236,7 +194,21 @@ private:
   std::pair<unsigned long long, unsigned long long> pairRangeOfJob(int jobs, int jobInd, bool shardOnly) const;
   void queuePair(unsigned hapRowA, unsigned hapRowB);
   void closeBatch(bool last);
+  // flush what is queued under the old setting, assign(), updateOutputStructures()
+  template <typename Assign> void changeOutputs(Assign&& assign);
   void flush();
+  // the parts of a flush, in its order (nPairs: the pairs of the closed batches, the flush's work list)
+  std::vector<fsmc_ibd_record> fetchIbdRecords(size_t nPairs);
+  void emitIbdRecords(const std::vector<fsmc_ibd_record>& recs);
+  void flushPosteriorSums();
+  void flushPairOutputs(size_t nPairs);
+  void flushPairMinima();
+  void flushPairBins();
+  void flushPairCdf();
+  void flushPairTailSummaries(size_t nPairs);
+  void flushPairPosteriors(size_t nPairs);
+  void writePerPairFiles(size_t nPairs, const std::vector<float>& mean, const std::vector<int32_t>& map);
+  void copyPairRows(size_t nPairs, const std::vector<float>& mean, const std::vector<int32_t>& map);
   void writeIbd(const fsmc_pair& pr, const fsmc_ibd_record& r);
   void emitIbd(gzFile file, const fsmc_pair& pr, const fsmc_ibd_record& r) const;
   void writeBinaryHeader(gzFile file) const; // HMM.cpp:383-401
@@ -272,13 +244,7 @@ private:
   unsigned long long mSegmentsDetected = 0;
   DecodingReturnValues mReturn;
   DecodePairsReturnStruct mPairsReturn;
-  bool mStoreMean = false, mStoreMap = false, mStorePosterior = false, mStoreSumOfPosterior = false;
-  bool mStoreMinMean = false, mStoreMinMap = false;
-  std::vector<int> mSiteBins; // bin edges of the per-pair summaries, empty = none
-  std::vector<int> mTailStates;  // state cuts of the per-pair tail probabilities, empty = none
-  std::vector<float> mQuantiles; // quantiles of the per-pair quantile states, empty = none
-  std::vector<int> mTailSummaryStates; // state cuts of the tail probabilities reduced over pairs and bins, empty = none
-  std::vector<float> mSiteWeights;     // weights of per_pair_bin_tail_lengths, empty = none
+  PairOutputs mOutputs; // what the pair-list decode stores into mPairsReturn
   bool mWriteMean = false, mWriteMap = false;
   gzFile mMeanFile = nullptr, mMapFile = nullptr;
   int mMeanFd = -1, mMapFd = -1; // their descriptors (blocks of rows go out as gzip members of their own)

@@ -27,12 +27,13 @@ template <typename T> py::array_t<T> toArray(const std::vector<T>& v, std::vecto
   return a;
 }
 
-py::array_t<float> mat2(const std::vector<float>& v, long rows, long cols)
+// v as an array of the given dimensions; an empty v as the array whose dimensions are all zero ([0][0], [0][0][0], length 0)
+template <typename T, typename... Dims> py::array_t<T> shaped(const std::vector<T>& v, Dims... dims)
 {
   if (v.empty()) {
-    return py::array_t<float>(std::vector<py::ssize_t>{0, 0});
+    return py::array_t<T>(std::vector<py::ssize_t>(sizeof...(dims), 0));
   }
-  return toArray<float>(v, {rows, cols});
+  return toArray<T>(v, {static_cast<py::ssize_t>(dims)...});
 }
 
 py::dict keyedTableToDict(const KeyedTable& t, unsigned states)
@@ -84,36 +85,66 @@ namespace fsmc_host
 void bindContainers(py::module_& m); // pybind_containers.cpp: VectorBool ... UMapIntToVectorFloat (pybind.cpp:63-70)
 }
 
-// a [pairs][bins] matrix of the return structure's site-bin summaries ([0][0] without bins)
-template <typename T>
-py::array_t<T> binMatrix(const std::vector<T>& v, const DecodePairsReturnStruct& r)
+namespace
 {
-  if (v.empty()) {
-    return py::array_t<T>(std::vector<py::ssize_t>{0, 0});
-  }
-  return toArray<T>(v, {static_cast<py::ssize_t>(r.numPairs), static_cast<py::ssize_t>(r.binEdges.size() - 1)});
+
+using Pairs = DecodePairsReturnStruct;
+size_t numBins(const Pairs& r)
+{
+  return r.request.siteBins.empty() ? 0 : r.request.siteBins.size() - 1;
 }
 
-// an [outputs][pairs][sites] stack of the return structure's tail / quantile rows ([0][0][0] without outputs)
-template <typename T>
-py::array_t<T> cdfRows(const std::vector<T>& v, size_t nOut, const DecodePairsReturnStruct& r)
+// ASMC.decodePairs for one kind of pair list (haplotype indices / "<ID>#<1|2>" strings): the keywords and the text once
+template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* listA, const char* listB)
 {
-  if (v.empty()) {
-    return py::array_t<T>(std::vector<py::ssize_t>{0, 0, 0});
-  }
-  return toArray<T>(v, {static_cast<py::ssize_t>(nOut), static_cast<py::ssize_t>(r.numPairs),
-                        static_cast<py::ssize_t>(r.numSites)});
+  c.def(
+      "decodePairs",
+      [](ASMC& self, const std::vector<Id>& a, const std::vector<Id>& b, bool perPairPosteriors, bool sumOfPosteriors,
+         bool perPairPosteriorMeans, bool perPairMAPs, bool minPosteriorMeans, bool minMAPs,
+         const std::vector<int>& siteBins, const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
+         const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights) {
+        PairOutputs o;
+        o.posteriors = perPairPosteriors;
+        o.sumOfPosteriors = sumOfPosteriors;
+        o.means = perPairPosteriorMeans;
+        o.maps = perPairMAPs;
+        o.minMeans = minPosteriorMeans;
+        o.minMaps = minMAPs;
+        o.siteBins = siteBins;
+        o.tailTimes = tailTimes;
+        o.quantiles = quantiles;
+        o.tailSummaryTimes = tailSummaryTimes;
+        o.siteWeights = siteWeights;
+        self.decodePairs(a, b, o);
+      },
+      py::arg(listA), py::arg(listB), "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
+      "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
+      "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
+      "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
+      "site_weights"_a = std::vector<float>{},
+      "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
+      "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
+      "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
+      "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
+      "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.  "
+      "tail_times (generations, up to 8) / quantiles (in (0, 1], up to 8): per pair and site, computed on the device "
+      "from the posterior over the states summed in ascending order in fp32, per_pair_tail_probabilities "
+      "([tails][pairs][sites] float32: the probability of a coalescence in one of the states whose interval starts "
+      "below the time -- the cut of HMM::getStateThreshold, reported in tail_states; tail_times=[params.time] is the "
+      "IBD scan's per-site sum) and per_pair_quantile_states ([quantiles][pairs][sites] int32: the smallest state at "
+      "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
+      "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
+      "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
+      "each flush.  tail_summary_times (generations, up to 8, cut like tail_times and reported in "
+      "tail_summary_states): the same tail probabilities, their rows NOT stored but reduced on the device: "
+      "sum_of_tail_probabilities ([tails][sites] float64: the sum over the pairs in pair order, one fp64 add a pair) "
+      "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
+      "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
+      "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
+      "in that order).");
 }
 
-// a [tails][pairs][bins] stack of the return structure's tail summaries over site bins ([0][0][0] without them)
-py::array_t<float> tailBinStack(const std::vector<float>& v, const DecodePairsReturnStruct& r)
-{
-  if (v.empty()) {
-    return py::array_t<float>(std::vector<py::ssize_t>{0, 0, 0});
-  }
-  return toArray<float>(v, {static_cast<py::ssize_t>(r.tailSummaryStates.size()), static_cast<py::ssize_t>(r.numPairs),
-                            static_cast<py::ssize_t>(r.binEdges.size() - 1)});
-}
+} // namespace
 
 PYBIND11_MODULE(_pyasmc, m)
 {
@@ -129,69 +160,55 @@ PYBIND11_MODULE(_pyasmc, m)
       .value("array", DecodingMode::array);
 
   py::class_<DecodingReturnValues>(m, "DecodingReturnValues")
-      .def_property_readonly("sumOverPairs", [](const DecodingReturnValues& r) { return mat2(r.sumOverPairs, r.sites, r.states); })
-      .def_property_readonly("sumOverPairs00", [](const DecodingReturnValues& r) { return mat2(r.sumOverPairs00, r.sites, r.states); })
-      .def_property_readonly("sumOverPairs01", [](const DecodingReturnValues& r) { return mat2(r.sumOverPairs01, r.sites, r.states); })
-      .def_property_readonly("sumOverPairs11", [](const DecodingReturnValues& r) { return mat2(r.sumOverPairs11, r.sites, r.states); })
+      .def_property_readonly("sumOverPairs", [](const DecodingReturnValues& r) { return shaped(r.sumOverPairs, r.sites, r.states); })
+      .def_property_readonly("sumOverPairs00", [](const DecodingReturnValues& r) { return shaped(r.sumOverPairs00, r.sites, r.states); })
+      .def_property_readonly("sumOverPairs01", [](const DecodingReturnValues& r) { return shaped(r.sumOverPairs01, r.sites, r.states); })
+      .def_property_readonly("sumOverPairs11", [](const DecodingReturnValues& r) { return shaped(r.sumOverPairs11, r.sites, r.states); })
       .def_readwrite("sites", &DecodingReturnValues::sites)
       .def_readwrite("states", &DecodingReturnValues::states)
       .def_readwrite("siteWasFlippedDuringFolding", &DecodingReturnValues::siteWasFlippedDuringFolding);
 
-  py::class_<DecodePairsReturnStruct>(m, "DecodePairsReturnStruct")
+  py::class_<Pairs>(m, "DecodePairsReturnStruct")
       .def(py::init<>(), "an empty structure: what every field holds before a decode and whenever it was not asked for")
-      .def_readwrite("per_pair_indices", &DecodePairsReturnStruct::perPairIndices)
+      .def_readwrite("per_pair_indices", &Pairs::perPairIndices)
       .def_property_readonly("per_pair_posteriors",
-                             [](const DecodePairsReturnStruct& r) {
+                             [](const Pairs& r) {
                                py::list out;
                                for (const auto& p : r.perPairPosteriors) {
-                                 out.append(mat2(p, r.numStates, r.numSites));
+                                 out.append(shaped(p, r.numStates, r.numSites));
                                }
                                return out;
                              })
-      .def_property_readonly("sum_of_posteriors", [](const DecodePairsReturnStruct& r) { return mat2(r.sumOfPosteriors, r.numStates, r.numSites); })
-      .def_property_readonly("per_pair_posterior_means", [](const DecodePairsReturnStruct& r) { return mat2(r.perPairPosteriorMeans, r.numPairs, r.numSites); })
-      .def_property_readonly("min_posterior_means", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.minPosteriorMeans, {static_cast<py::ssize_t>(r.minPosteriorMeans.size())}); })
-      .def_property_readonly("argmin_posterior_means", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.argminPosteriorMeans, {static_cast<py::ssize_t>(r.argminPosteriorMeans.size())}); })
-      .def_property_readonly("per_pair_MAPs",
-                             [](const DecodePairsReturnStruct& r) {
-                               if (r.perPairMAPs.empty()) {
-                                 return py::array_t<int>(std::vector<py::ssize_t>{0, 0});
-                               }
-                               return toArray<int>(r.perPairMAPs, {r.numPairs, r.numSites});
-                             })
-      .def_property_readonly("min_MAPs", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.minMAPs, {static_cast<py::ssize_t>(r.minMAPs.size())}); })
-      .def_property_readonly("argmin_MAPs", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.argminMAPs, {static_cast<py::ssize_t>(r.argminMAPs.size())}); })
+      .def_property_readonly("sum_of_posteriors", [](const Pairs& r) { return shaped(r.sumOfPosteriors, r.numStates, r.numSites); })
+      .def_property_readonly("per_pair_posterior_means", [](const Pairs& r) { return shaped(r.perPairPosteriorMeans, r.numPairs, r.numSites); })
+      .def_property_readonly("min_posterior_means", [](const Pairs& r) { return shaped(r.minPosteriorMeans, r.minPosteriorMeans.size()); })
+      .def_property_readonly("argmin_posterior_means", [](const Pairs& r) { return shaped(r.argminPosteriorMeans, r.argminPosteriorMeans.size()); })
+      .def_property_readonly("per_pair_MAPs", [](const Pairs& r) { return shaped(r.perPairMAPs, r.numPairs, r.numSites); })
+      .def_property_readonly("min_MAPs", [](const Pairs& r) { return shaped(r.minMAPs, r.minMAPs.size()); })
+      .def_property_readonly("argmin_MAPs", [](const Pairs& r) { return shaped(r.argminMAPs, r.argminMAPs.size()); })
       // per pair, summaries over the bins of sites [bin_edges[b], bin_edges[b + 1]): [pairs][bins], empty without bins
-      .def_property_readonly("bin_edges", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.binEdges, {static_cast<py::ssize_t>(r.binEdges.size())}); })
-      .def_property_readonly("bin_mean_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<float>(r.binMeanPosteriorMeans, r); })
-      .def_property_readonly("bin_min_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<float>(r.binMinPosteriorMeans, r); })
-      .def_property_readonly("bin_argmin_posterior_means", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminPosteriorMeans, r); })
-      .def_property_readonly("bin_min_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binMinMAPs, r); })
-      .def_property_readonly("bin_argmin_MAPs", [](const DecodePairsReturnStruct& r) { return binMatrix<int>(r.binArgminMAPs, r); })
+      .def_property_readonly("bin_edges", [](const Pairs& r) { return shaped(r.request.siteBins, r.request.siteBins.size()); })
+      .def_property_readonly("bin_mean_posterior_means", [](const Pairs& r) { return shaped(r.binMeanPosteriorMeans, r.numPairs, numBins(r)); })
+      .def_property_readonly("bin_min_posterior_means", [](const Pairs& r) { return shaped(r.binMinPosteriorMeans, r.numPairs, numBins(r)); })
+      .def_property_readonly("bin_argmin_posterior_means", [](const Pairs& r) { return shaped(r.binArgminPosteriorMeans, r.numPairs, numBins(r)); })
+      .def_property_readonly("bin_min_MAPs", [](const Pairs& r) { return shaped(r.binMinMAPs, r.numPairs, numBins(r)); })
+      .def_property_readonly("bin_argmin_MAPs", [](const Pairs& r) { return shaped(r.binArgminMAPs, r.numPairs, numBins(r)); })
       // per pair and site: the posterior mass of the first tail_states[j] states (tail_times[j]: the generations asked
       // for) and the smallest state whose running sum reaches quantiles[j]; [outputs][pairs][sites], empty without outputs
-      .def_property_readonly("tail_times", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.tailTimes, {static_cast<py::ssize_t>(r.tailTimes.size())}); })
-      .def_property_readonly("tail_states", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.tailStates, {static_cast<py::ssize_t>(r.tailStates.size())}); })
-      .def_property_readonly("quantiles", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.quantiles, {static_cast<py::ssize_t>(r.quantiles.size())}); })
-      .def_property_readonly("per_pair_tail_probabilities", [](const DecodePairsReturnStruct& r) { return cdfRows<float>(r.perPairTailProbabilities, r.tailStates.size(), r); })
-      .def_property_readonly("per_pair_quantile_states", [](const DecodePairsReturnStruct& r) { return cdfRows<int>(r.perPairQuantileStates, r.quantiles.size(), r); })
+      .def_property_readonly("tail_times", [](const Pairs& r) { return shaped(r.request.tailTimes, r.request.tailTimes.size()); })
+      .def_property_readonly("tail_states", [](const Pairs& r) { return shaped(r.request.tailStates, r.request.tailStates.size()); })
+      .def_property_readonly("quantiles", [](const Pairs& r) { return shaped(r.request.quantiles, r.request.quantiles.size()); })
+      .def_property_readonly("per_pair_tail_probabilities", [](const Pairs& r) { return shaped(r.perPairTailProbabilities, r.request.tailStates.size(), r.numPairs, r.numSites); })
+      .def_property_readonly("per_pair_quantile_states", [](const Pairs& r) { return shaped(r.perPairQuantileStates, r.request.quantiles.size(), r.numPairs, r.numSites); })
       // the tail probabilities of tail_summary_states[j] (tail_summary_times[j]: the generations asked for), their rows
       // not stored: summed over the pairs in pair order in fp64, [tails][sites]; per pair the mean over each site bin and,
       // with site_weights, the weighted sum over it, [tails][pairs][bins]; empty where not asked for
-      .def_property_readonly("tail_summary_times", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.tailSummaryTimes, {static_cast<py::ssize_t>(r.tailSummaryTimes.size())}); })
-      .def_property_readonly("tail_summary_states", [](const DecodePairsReturnStruct& r) { return toArray<int>(r.tailSummaryStates, {static_cast<py::ssize_t>(r.tailSummaryStates.size())}); })
-      .def_property_readonly("site_weights", [](const DecodePairsReturnStruct& r) { return toArray<float>(r.siteWeights, {static_cast<py::ssize_t>(r.siteWeights.size())}); })
-      .def_property_readonly("sum_of_tail_probabilities",
-                             [](const DecodePairsReturnStruct& r) {
-                               if (r.sumOfTailProbabilities.empty()) {
-                                 return py::array_t<double>(std::vector<py::ssize_t>{0, 0});
-                               }
-                               return toArray<double>(r.sumOfTailProbabilities,
-                                                      {static_cast<py::ssize_t>(r.tailSummaryStates.size()),
-                                                       static_cast<py::ssize_t>(r.numSites)});
-                             })
-      .def_property_readonly("per_pair_bin_tail_means", [](const DecodePairsReturnStruct& r) { return tailBinStack(r.binTailMeans, r); })
-      .def_property_readonly("per_pair_bin_tail_lengths", [](const DecodePairsReturnStruct& r) { return tailBinStack(r.binTailLengths, r); });
+      .def_property_readonly("tail_summary_times", [](const Pairs& r) { return shaped(r.request.tailSummaryTimes, r.request.tailSummaryTimes.size()); })
+      .def_property_readonly("tail_summary_states", [](const Pairs& r) { return shaped(r.request.tailSummaryStates, r.request.tailSummaryStates.size()); })
+      .def_property_readonly("site_weights", [](const Pairs& r) { return shaped(r.request.siteWeights, r.request.siteWeights.size()); })
+      .def_property_readonly("sum_of_tail_probabilities", [](const Pairs& r) { return shaped(r.sumOfTailProbabilities, r.request.tailSummaryStates.size(), r.numSites); })
+      .def_property_readonly("per_pair_bin_tail_means", [](const Pairs& r) { return shaped(r.binTailMeans, r.request.tailSummaryStates.size(), r.numPairs, numBins(r)); })
+      .def_property_readonly("per_pair_bin_tail_lengths", [](const Pairs& r) { return shaped(r.binTailLengths, r.request.tailSummaryStates.size(), r.numPairs, numBins(r)); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -592,72 +609,14 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("outputFileName", &FastSMC::outputFileName)
       .def("hmm", &FastSMC::hmm, py::return_value_policy::reference_internal);
 
-  py::class_<ASMC>(m, "ASMC")
-      .def(py::init<DecodingParams>(), "decodingParams"_a)
+  py::class_<ASMC> asmc(m, "ASMC");
+  asmc.def(py::init<DecodingParams>(), "decodingParams"_a)
       .def(py::init<const std::string&, const std::string&, const std::string&>(), "in_dir"_a, "dq_file"_a,
            "out_dir"_a = "")
-      .def("decodeAllInJob", &ASMC::decodeAllInJob)
-      .def("decodePairs",
-           py::overload_cast<const std::vector<unsigned long>&, const std::vector<unsigned long>&, bool, bool, bool,
-                             bool, bool, bool, const std::vector<int>&, const std::vector<float>&,
-                             const std::vector<float>&, const std::vector<float>&,
-                             const std::vector<float>&>(&ASMC::decodePairs),
-           "hap_indices_a"_a, "hap_indices_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
-           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
-           "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
-           "site_weights"_a = std::vector<float>{},
-           "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
-           "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
-           "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
-           "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
-           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.  "
-           "tail_times (generations, up to 8) / quantiles (in (0, 1], up to 8): per pair and site, computed on the device "
-           "from the posterior over the states summed in ascending order in fp32, per_pair_tail_probabilities "
-           "([tails][pairs][sites] float32: the probability of a coalescence in one of the states whose interval starts "
-           "below the time -- the cut of HMM::getStateThreshold, reported in tail_states; tail_times=[params.time] is the "
-           "IBD scan's per-site sum) and per_pair_quantile_states ([quantiles][pairs][sites] int32: the smallest state at "
-           "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
-           "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
-           "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
-           "each flush.  tail_summary_times (generations, up to 8, cut like tail_times and reported in "
-           "tail_summary_states): the same tail probabilities, their rows NOT stored but reduced on the device: "
-           "sum_of_tail_probabilities ([tails][sites] float64: the sum over the pairs in pair order, one fp64 add a pair) "
-           "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
-           "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
-           "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
-           "in that order).")
-      .def("decodePairs",
-           py::overload_cast<const std::vector<std::string>&, const std::vector<std::string>&, bool, bool, bool, bool,
-                             bool, bool, const std::vector<int>&, const std::vector<float>&,
-                             const std::vector<float>&, const std::vector<float>&,
-                             const std::vector<float>&>(&ASMC::decodePairs),
-           "hap_ids_a"_a, "hap_ids_b"_a, "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
-           "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-           "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
-           "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
-           "site_weights"_a = std::vector<float>{},
-           "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
-           "pair and bin [e[b], e[b+1]) the mean (a defined fp64 order), min and argmin (lowest site) of the posterior-mean "
-           "row and the min and argmin of the MAP row are computed on the device into bin_mean_posterior_means, "
-           "bin_min_posterior_means, bin_argmin_posterior_means, bin_min_MAPs, bin_argmin_MAPs ([pairs][B]); the rows "
-           "themselves do not reach the host unless asked for as well, which costs a second decode of each flush.  "
-           "tail_times (generations, up to 8) / quantiles (in (0, 1], up to 8): per pair and site, computed on the device "
-           "from the posterior over the states summed in ascending order in fp32, per_pair_tail_probabilities "
-           "([tails][pairs][sites] float32: the probability of a coalescence in one of the states whose interval starts "
-           "below the time -- the cut of HMM::getStateThreshold, reported in tail_states; tail_times=[params.time] is the "
-           "IBD scan's per-site sum) and per_pair_quantile_states ([quantiles][pairs][sites] int32: the smallest state at "
-           "which the running sum reaches the quantile, states - 1 if none does; expectedTimes[state] or "
-           "discretization[state + 1] turns it into a time).  A time no interval starts below is refused.  The posterior "
-           "tables do not reach the host unless per_pair_posteriors is asked for as well, which costs a second decode of "
-           "each flush.  tail_summary_times (generations, up to 8, cut like tail_times and reported in "
-           "tail_summary_states): the same tail probabilities, their rows NOT stored but reduced on the device: "
-           "sum_of_tail_probabilities ([tails][sites] float64: the sum over the pairs in pair order, one fp64 add a pair) "
-           "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
-           "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
-           "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
-           "in that order).")
-      .def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
+      .def("decodeAllInJob", &ASMC::decodeAllInJob);
+  defDecodePairs<unsigned long>(asmc, "hap_indices_a", "hap_indices_b");
+  defDecodePairs<std::string>(asmc, "hap_ids_a", "hap_ids_b");
+  asmc.def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);
 

@@ -3,32 +3,26 @@ row and the min and argmin (lowest site) of the MAP row over bins of sites, comp
 [pairs][sites] rows crossing the bus.  Everything is np.array_equal against the numpy statement of
 tests/pair_bins_lists.py on the oracle's rows (tests/test_pair_bins_lists.py shows what the edge sets reach).  No test
 here can put a NaN into the rows: the NaN rule of the kernel's comment is not tested."""
-import copy
-import gzip
-import os
-import shutil
 
 import numpy as np
 import pytest
 
 import pair_bins_lists as BL
 from conftest import expected_member
-from fastsmc_amd import api, capi, synth
+from fastsmc_amd import api, capi
 from oracle import oracle as O
+from pair_common import (pairs_array as _pairs_array, upload as _upload, open_context as _open, gpu_context,
+                         problem as _problem, example_files as _example_files, asmc as _asmc)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
+
+@pytest.fixture
+def gpu(small_problem):
+    yield from gpu_context(small_problem)
+
+
 INT_MIN = np.iinfo(np.int32).min
-
-
-def _pairs_array(pairs):
-    return np.array(pairs, dtype=np.uint32).view(capi.PAIR_DTYPE).reshape(-1)
-
-
-def _upload(ctx, pm, pairs):
-    ctx.upload_worklist(_pairs_array(pairs), capi.whole_sequence_groups(len(pairs), pm.S))
 
 
 def _assert_equal(got, want, msg=""):
@@ -36,20 +30,6 @@ def _assert_equal(got, want, msg=""):
     for name, g, w in zip(BL.NAMES, got, want):
         assert g.dtype == w.dtype and g.shape == w.shape, (name, g.dtype, w.dtype, g.shape, w.shape)
         assert np.array_equal(g, w), f"{name} {msg}: {int((g != w).sum())} of {g.size} cells differ"
-
-
-def _open(small_problem):
-    ctx = capi.Context(0)
-    model = ctx.create_model(small_problem["model"])
-    ctx.upload_haps(small_problem["bits"], small_problem["model"].S)
-    return ctx, model
-
-
-@pytest.fixture
-def gpu(small_problem):
-    ctx, model = _open(small_problem)
-    yield ctx, model
-    ctx.close()
 
 
 def _sentinels(n, B):
@@ -142,16 +122,6 @@ def test_ragged_list_and_rows_beyond_it(gpu, small_problem, slice_groups):
         assert _untouched(g[150:]), name
 
 
-def _problem(K, n_hap=64, S=200, seed=11):
-    tables = synth.make_model_tables(K)
-    haps = synth.make_haps(n_hap, S, seed=seed, cm_per_mb=25.0, switch_per_cm=0.6)
-    bits, derived, flipped = synth.fold_and_pack(haps.alleles)
-    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
-    gen = (haps.cm / 100.0).astype(np.float32)
-    pm = O.prepare_model(tables, gen, haps.bp, derived, n_hap, time=200)
-    return pm, bits, folded
-
-
 def _other_kernel_case(pm, bits, folded, n_pairs):
     """E3 (cut to the model's sites) on a list of two groups, the second ragged, slices of one group, against this
     model's own oracle rows."""
@@ -225,29 +195,6 @@ def test_errors(gpu, small_problem):
 
 
 # ---------------------------------------------------------------- the product path: ASMC.decodePairs
-
-def _example_files(tmp_path):
-    """The reference's exampleFile.n300.array.{hap.gz,map.gz,samples} (tests/golden) under a root of their own, with the
-    synthetic 69-state decoding quantities restricted to the rows this map uses."""
-    root = str(tmp_path / "exampleFile.n300.array")
-    for ext in (".hap.gz", ".map.gz", ".samples"):
-        shutil.copy(os.path.join(GOLD, "exampleFile.n300.array" + ext), root + ext)
-    cm = [float(line.split()[2]) for line in gzip.open(root + ".map.gz", "rt")]
-    gen = np.array([np.float32(np.float32(c) / np.float32(100.0)) for c in cm], np.float32)  # (Data.cpp:186)
-    t = copy.copy(synth.make_model_tables(69))
-    used = np.unique(np.concatenate([[0.0], O.step_rows(t.keys, gen)[1][1:]]))
-    sel = np.nonzero(np.isin(t.keys, used.astype(np.float32)))[0]
-    t.keys, t.D, t.B, t.U, t.RR = t.keys[sel], t.D[sel], t.B[sel], t.U[sel], t.RR[sel]
-    synth.write_decoding_quantities(root + ".decodingQuantities.gz", t)
-    return root, np.array(cm)
-
-
-def _asmc(root):
-    p = api.DecodingParams(root, root + ".decodingQuantities.gz", root, 1, 1, "array", False, True, False, False, 0.0,
-                           False, True, False, "", False, True)
-    p.useKnownSeed = True
-    return api.ASMC(p)
-
 
 def _five(res):
     return (np.array(res.bin_mean_posterior_means), np.array(res.bin_min_posterior_means),

@@ -3,10 +3,8 @@ FIRST pair that has it (DecodePairsReturnStruct::finaliseCalculations, DecodePai
 the device without the [pairs][sites] rows crossing the bus.  Everything is np.array_equal against numpy's first argmin
 of the oracle's rows (tests/pair_minima_lists.py; tests/test_pair_minima_lists.py shows what the list reaches)."""
 import copy
-import gzip
 import json
 import os
-import shutil
 import subprocess
 import sys
 
@@ -15,22 +13,21 @@ import pytest
 
 import pair_minima_lists as L
 from conftest import expected_member
-from fastsmc_amd import api, capi, synth
+from fastsmc_amd import capi, synth
 from oracle import oracle as O
+from pair_common import (pairs_array as _pairs_array, upload as _upload, open_context as _open, gpu_context,
+                         problem as _problem, example_files as _example_files, asmc as _asmc)
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture
+def gpu(small_problem):
+    yield from gpu_context(small_problem)
+
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 INT_MIN = np.iinfo(np.int32).min
-
-
-def _pairs_array(pairs):
-    return np.array(pairs, dtype=np.uint32).view(capi.PAIR_DTYPE).reshape(-1)
-
-
-def _upload(ctx, pm, pairs):
-    ctx.upload_worklist(_pairs_array(pairs), capi.whole_sequence_groups(len(pairs), pm.S))
 
 
 def _want(mean, mp, base=0):
@@ -47,20 +44,6 @@ def _assert_equal(got, want, msg=""):
 def want_192(small_problem):
     mean, mp = L.rows_192(small_problem)
     return _want(mean, mp)
-
-
-def _open(small_problem):
-    ctx = capi.Context(0)
-    model = ctx.create_model(small_problem["model"])
-    ctx.upload_haps(small_problem["bits"], small_problem["model"].S)
-    return ctx, model
-
-
-@pytest.fixture
-def gpu(small_problem):
-    ctx, model = _open(small_problem)
-    yield ctx, model
-    ctx.close()
 
 
 def test_minima_k69_both_kernels(small_problem, want_192, window_waves):
@@ -183,16 +166,6 @@ def test_nothing_is_written_outside_the_outputs(gpu, small_problem, want_192):
         assert (b[:guard] == INT_MIN).all() and (b[guard + pm.S:] == INT_MIN).all()
 
 
-def _problem(K, n_hap=64, S=200, seed=11):
-    tables = synth.make_model_tables(K)
-    haps = synth.make_haps(n_hap, S, seed=seed, cm_per_mb=25.0, switch_per_cm=0.6)
-    bits, derived, flipped = synth.fold_and_pack(haps.alleles)
-    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
-    gen = (haps.cm / 100.0).astype(np.float32)
-    pm = O.prepare_model(tables, gen, haps.bp, derived, n_hap, time=200)
-    return pm, bits, folded
-
-
 def _other_kernel_case(pm, bits, folded, n_pairs):
     """A list whose second group repeats pairs of the first (ties across the slice boundary), slices of one group."""
     base = O.enumerate_all_pairs(32)[:n_pairs]
@@ -266,29 +239,6 @@ def test_errors(gpu, small_problem, want_192):
 
 # ---------------------------------------------------------------- the product path: ASMC.decodePairs
 
-def _example_files(tmp_path):
-    """The reference's exampleFile.n300.array.{hap.gz,map.gz,samples} (tests/golden) under a root of their own, with the
-    synthetic 69-state decoding quantities restricted to the rows this map uses."""
-    root = str(tmp_path / "exampleFile.n300.array")
-    for ext in (".hap.gz", ".map.gz", ".samples"):
-        shutil.copy(os.path.join(GOLD, "exampleFile.n300.array" + ext), root + ext)
-    cm = [float(line.split()[2]) for line in gzip.open(root + ".map.gz", "rt")]
-    gen = np.array([np.float32(np.float32(c) / np.float32(100.0)) for c in cm], np.float32)  # (Data.cpp:186)
-    t = copy.copy(synth.make_model_tables(69))
-    used = np.unique(np.concatenate([[0.0], O.step_rows(t.keys, gen)[1][1:]]))
-    sel = np.nonzero(np.isin(t.keys, used.astype(np.float32)))[0]
-    t.keys, t.D, t.B, t.U, t.RR = t.keys[sel], t.D[sel], t.B[sel], t.U[sel], t.RR[sel]
-    synth.write_decoding_quantities(root + ".decodingQuantities.gz", t)
-    return root
-
-
-def _asmc(root):
-    p = api.DecodingParams(root, root + ".decodingQuantities.gz", root, 1, 1, "array", False, True, False, False, 0.0,
-                           False, True, False, "", False, True)
-    p.useKnownSeed = True
-    return api.ASMC(p)
-
-
 def _four(res):
     return (np.array(res.min_posterior_means), np.array(res.argmin_posterior_means), np.array(res.min_MAPs),
             np.array(res.argmin_MAPs))
@@ -310,7 +260,7 @@ def test_product_path_minima_equal_those_of_the_rows_path(tmp_path, monkeypatch,
     queue is decoded every 128 pairs: three flushes continue one chain (pair_base = pairs written so far)."""
     if flush_pairs:
         monkeypatch.setenv("FSMC_DIAG_FLUSH_PAIRS", str(flush_pairs))
-    asmc = _asmc(_example_files(tmp_path))
+    asmc = _asmc(_example_files(tmp_path)[0])
     for name, pairs in _product_lists().items():
         a, b = [int(p[0]) for p in pairs], [int(p[1]) for p in pairs]
         asmc.decodePairs(a, b, per_pair_posterior_means=True, per_pair_MAPs=True)

@@ -14,14 +14,11 @@ import pytest
 from conftest import expected_member
 from fastsmc_amd import api, capi, synth
 from oracle import oracle as O
+from pair_common import (pairs_array as _pairs_array, problem as _problem, upload as _upload)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _pairs_array(pairs):
-    return np.array(pairs, dtype=np.uint32).view(capi.PAIR_DTYPE).reshape(-1)
 
 
 def _oracle(pm, folded, pairs, acc=None):
@@ -36,16 +33,6 @@ def _oracle(pm, folded, pairs, acc=None):
         _, _, pp = O.per_pair_output(pm, post, len(chunk), want_post=True, sum_of_post=acc)
         rows.append(pp)
     return np.concatenate(rows), acc
-
-
-def _problem(K, n_hap=64, S=200, seed=11):
-    tables = synth.make_model_tables(K)
-    haps = synth.make_haps(n_hap, S, seed=seed, cm_per_mb=25.0, switch_per_cm=0.6)
-    bits, derived, flipped = synth.fold_and_pack(haps.alleles)
-    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
-    gen = (haps.cm / 100.0).astype(np.float32)
-    pm = O.prepare_model(tables, gen, haps.bp, derived, n_hap, time=200)
-    return pm, bits, folded
 
 
 PAIRS_150 = O.enumerate_all_pairs(32)[100:100 + 150]  # three groups, the last with 22 pairs
@@ -64,10 +51,6 @@ def gpu(small_problem, window_waves):
     ctx.upload_haps(small_problem["bits"], small_problem["model"].S)
     yield ctx, model
     ctx.close()
-
-
-def _upload(ctx, pm, pairs):
-    ctx.upload_worklist(_pairs_array(pairs), capi.whole_sequence_groups(len(pairs), pm.S))
 
 
 def test_rows_and_sum_k69(gpu, small_problem, want_150, window_waves):

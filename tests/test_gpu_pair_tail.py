@@ -6,7 +6,6 @@ tests/pair_tail_lists.py on the oracle's posteriors (tests/test_pair_tail_lists.
 The ABI's outputs have no rows beyond the list (a cut's cells are [n_pairs][n_bins], the next cut follows at once), so the
 sentinels are the caller's memory behind each array and, for the bin outputs, every cell before the call: a row written for
 a dead lane of a ragged group would land in the next cut's cells or behind the array."""
-import copy
 
 import numpy as np
 import pytest
@@ -14,35 +13,22 @@ import pytest
 import pair_cdf_lists as CL
 import pair_tail_lists as TL
 from conftest import expected_member
-from fastsmc_amd import api, capi, synth
+from fastsmc_amd import api, capi
 from oracle import oracle as O
+from pair_common import (EDGES_700, N_HAP, N_PAIRS, SITES, pairs_array as _pairs_array, upload as _upload,
+                         open_context as _open, gpu_context, problem as _problem, cohort_files as _cohort_files,
+                         params as _params, cohort_pairs as _cohort_pairs)
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64  # cells of caller memory behind every output, NaN before and after the call
-NAMES = ("tail_sum", "bin_tail_mean", "bin_tail_length")
-
-
-def _pairs_array(pairs):
-    return np.array(pairs, dtype=np.uint32).view(capi.PAIR_DTYPE).reshape(-1)
-
-
-def _upload(ctx, pm, pairs):
-    ctx.upload_worklist(_pairs_array(pairs), capi.whole_sequence_groups(len(pairs), pm.S))
-
-
-def _open(small_problem):
-    ctx = capi.Context(0)
-    model = ctx.create_model(small_problem["model"])
-    ctx.upload_haps(small_problem["bits"], small_problem["model"].S)
-    return ctx, model
 
 
 @pytest.fixture
 def gpu(small_problem):
-    ctx, model = _open(small_problem)
-    yield ctx, model
-    ctx.close()
+    yield from gpu_context(small_problem)
+
+
+GUARD = 64  # cells of caller memory behind every output, NaN before and after the call
+NAMES = ("tail_sum", "bin_tail_mean", "bin_tail_length")
 
 
 class Outputs:
@@ -187,16 +173,6 @@ def test_the_sum_alone_and_the_bins_alone(gpu, small_problem):
     _assert_equal(got, want)
 
 
-def _problem(K, n_hap=64, S=200, seed=11):
-    tables = synth.make_model_tables(K)
-    haps = synth.make_haps(n_hap, S, seed=seed, cm_per_mb=25.0, switch_per_cm=0.6)
-    bits, derived, flipped = synth.fold_and_pack(haps.alleles)
-    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
-    gen = (haps.cm / 100.0).astype(np.float32)
-    pm = O.prepare_model(tables, gen, haps.bp, derived, n_hap, time=200)
-    return pm, bits, folded
-
-
 def _other_kernel_case(pm, bits, folded, n_pairs):
     """Cuts [1, K / 2, K] -- the cut K reads the last state, and a walk into ghost states would move it -- on a list of
     two groups, the second ragged, slices of one group, against this model's own oracle posteriors; the edges end one site
@@ -290,36 +266,6 @@ def test_errors(gpu, small_problem):
 
 # ---------------------------------------------------------------- the product path: ASMC.decodePairs
 
-N_HAP, SITES, N_PAIRS = 64, 700, 200
-EDGES_700 = [5, 70, 71, 100, 400, 699]
-
-
-def _cohort_files(tmp_path):
-    """A synthetic cohort of 64 haplotypes x 700 sites (not a multiple of 64) as files, with the 69-state decoding
-    quantities restricted to the rows its map uses; returns (root, tables, haps, derived, folded)."""
-    tables = synth.make_model_tables(69)
-    haps = synth.make_haps(N_HAP, SITES, seed=17, cm_per_mb=25.0, switch_per_cm=0.6)
-    _, derived, flipped = synth.fold_and_pack(haps.alleles)
-    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
-    root = str(tmp_path / "cohort")
-    synth.write_haps_files(root, haps, fastsmc_map=False)
-    gen_file = np.array([np.float32(np.float32(c) / np.float32(100.0)) for c in haps.cm], np.float32)
-    gen_synth = (haps.cm / 100.0).astype(np.float32)
-    t = copy.copy(tables)
-    used = np.unique(np.concatenate([[0.0], O.step_rows(t.keys, gen_file)[1][1:], O.step_rows(t.keys, gen_synth)[1][1:]]))
-    sel = np.nonzero(np.isin(t.keys, used.astype(np.float32)))[0]
-    t.keys, t.D, t.B, t.U, t.RR = t.keys[sel], t.D[sel], t.B[sel], t.U[sel], t.RR[sel]
-    synth.write_decoding_quantities(root + ".decodingQuantities.gz", t)
-    return root, tables, haps, derived, folded
-
-
-def _params(root):
-    p = api.DecodingParams(root, root + ".decodingQuantities.gz", root, 1, 1, "array", False, True, False, False, 0.0,
-                           False, True, False, "", False, True)
-    p.useKnownSeed = True
-    return p
-
-
 NEW_FIELDS = ("tail_summary_times", "tail_summary_states", "site_weights", "sum_of_tail_probabilities",
               "per_pair_bin_tail_means", "per_pair_bin_tail_lengths")
 OLD_FIELDS = ("sum_of_posteriors", "per_pair_posterior_means", "min_posterior_means", "argmin_posterior_means",
@@ -346,10 +292,7 @@ def test_product_path(tmp_path, monkeypatch, flush_pairs):
     root, tables, haps, derived, folded = _cohort_files(tmp_path)
     p = _params(root)
     asmc = api.ASMC(p)
-    rng = np.random.default_rng(5)
-    all_pairs = [(x, y) for x in range(N_HAP) for y in range(x + 1, N_HAP)]
-    pairs = [all_pairs[i] for i in rng.choice(len(all_pairs), N_PAIRS, replace=False)]
-    a, b = [int(x) for x, _ in pairs], [int(y) for _, y in pairs]
+    pairs, a, b = _cohort_pairs()
     times = [50, 200]
     gen = np.array(api.Data(p).geneticPositions, np.float32)
     w = api.site_widths(gen)
