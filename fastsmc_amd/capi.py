@@ -39,6 +39,7 @@ SYMBOLS = [
     "fsmc_decode_pair_bins", "fsmc_ctx_set_pair_bins_slice", "fsmc_ctx_last_pair_bins_slices",
     "fsmc_decode_pair_cdf", "fsmc_ctx_set_pair_cdf_slice", "fsmc_ctx_last_pair_cdf_slices",
     "fsmc_decode_pair_tail_summaries", "fsmc_ctx_set_pair_tail_slice", "fsmc_ctx_last_pair_tail_slices",
+    "fsmc_decode_pair_loglik", "fsmc_ctx_set_pair_loglik_slice", "fsmc_ctx_last_pair_loglik_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -48,6 +49,13 @@ GROUP_DTYPE = np.dtype([("first_pair", "<u4"), ("n_pairs", "<u4"), ("from", "<u4
 CANDIDATE_DTYPE = np.dtype([("hap_a", "<u4"), ("hap_b", "<u4"), ("from", "<u4"), ("to", "<u4"), ("flush_word", "<u4")])
 IBD_DTYPE = np.dtype([("pair", "<u4"), ("start", "<i4"), ("end", "<i4"), ("prob", "<f4"), ("post_mean", "<f4"),
                       ("map", "<f4")])
+
+
+def log_likelihood(mant, expo):
+    """log(mant) + expo * ln 2 in float64: the natural logarithm of the likelihoods fsmc_decode_pair_loglik returns as
+    mantissa and exponent.  A zero mantissa gives -inf, a NaN stays a NaN."""
+    with np.errstate(divide="ignore"):
+        return np.log(np.asarray(mant, np.float64)) + np.asarray(expo, np.float64) * np.log(2.0)
 
 
 class FsmcError(RuntimeError):
@@ -139,6 +147,9 @@ def load():
         L.fsmc_decode_pair_tail_summaries.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
         L.fsmc_ctx_set_pair_tail_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_tail_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_loglik.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+        L.fsmc_ctx_set_pair_loglik_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_loglik_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -468,6 +479,46 @@ class Context:
     def last_pair_bins_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_bins_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_loglik(self, model: "Model", bin_edges=None, want_total=True, out=None):
+        """Per pair of the resident work list, the likelihood of its observations from the forward sweep alone
+        (fsmc_decode_pair_loglik), as mantissa and exponent: (mant f64 [n_pairs], expo i32 [n_pairs], bin_mant f64
+        [n_pairs][B], bin_expo i32 [n_pairs][B]); the bin outputs -- the same recurrence started afresh at every bin's
+        first site -- come with ``bin_edges``, the totals with ``want_total``; None for what was not asked for.
+        ``log_likelihood(mant, expo)`` gives the natural logarithm.  ``out``: four such arrays (None where not wanted, at
+        least n_pairs rows), written in place and returned as they are -- ``want_total`` is ignored then."""
+        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
+        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
+        if edges is not None and edges.size == 0:
+            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        n = self._n_pairs
+        dtypes = (np.float64, np.int32, np.float64, np.int32)
+        if out is None:
+            out = (np.zeros(n, np.float64) if want_total else None, np.zeros(n, np.int32) if want_total else None,
+                   np.zeros((n, n_bins), np.float64) if edges is not None else None,
+                   np.zeros((n, n_bins), np.int32) if edges is not None else None)
+        out = tuple(out)
+        if len(out) != 4:
+            raise ValueError("out: (mant, expo, bin_mant, bin_expo)")
+        for i, (a, dt) in enumerate(zip(out, dtypes)):
+            if a is None:
+                continue
+            shape_ok = (a.ndim == 1) if i < 2 else (a.ndim == 2 and a.shape[1] == n_bins)
+            if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or not shape_ok or a.shape[0] < n:
+                raise ValueError("out: writable C-contiguous arrays, float64 mantissas and int32 exponents, [>= n_pairs] "
+                                 "and [>= n_pairs][B]")
+        self._check(self._L.fsmc_decode_pair_loglik(self._h, model._h, _p(edges), n_bins, *[_p(a) for a in out]))
+        return out
+
+    def set_pair_loglik_slice(self, groups: int):
+        """Groups fsmc_decode_pair_loglik puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_loglik_slice(self._h, groups))
+
+    def last_pair_loglik_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_loglik_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):

@@ -65,7 +65,7 @@ struct DevBuf {
 
 // The entry points that send the work list through the device in slices of groups (planSlices): each has its own
 // slice setting and its own count of the last call's slices.
-enum PairSlicing { kSlicePosteriors, kSliceMinima, kSliceBins, kSliceCdf, kSliceTail, kPairSlicings };
+enum PairSlicing { kSlicePosteriors, kSliceMinima, kSliceBins, kSliceCdf, kSliceTail, kSliceLoglik, kPairSlicings };
 } // namespace
 
 struct fsmc_ctx {
@@ -149,6 +149,7 @@ struct fsmc_ctx {
   DevBuf pmAcc;             // minima: [expCoal KP floats][the carried state, 4 x S][the ranges' partials, 4 x nRanges x S]
   DevBuf pbAcc;             // bins: [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
   DevBuf pcSpec;            // cdf, tail summaries: the call's outputs, PairCdfSpec each
+  DevBuf plAcc;             // log-likelihoods: a slice's [mant][bin mant][expo][bin expo], then the edges, B + 1
   DevBuf ptAcc;             // tail summaries: [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
@@ -517,6 +518,33 @@ KernelChoice chooseTwoWaveKernel(const fsmc_model* m, int mode)
     break;
   }
   return k;
+}
+
+// The forward-only kernel of a model (fsmc_pair_loglik.h): every lane-per-pair member, array and sequence mode.  Carried
+// as a KernelChoice -- the occupancy query and the launch record take one -- with the function pointer under the decode
+// kernels' type; forwardFn gives it its own type back for the launch.  nullptr beyond 128 states.
+using ForwardFn = void (*)(const FwdParams);
+KernelChoice chooseForwardKernel(const fsmc_model* m)
+{
+  KernelChoice k{nullptr, kWave, m->K <= 128 ? familyMember(m) : 0, 1};
+  ForwardFn fn = nullptr;
+  switch (k.member) {
+#define FSMC_PICK_FWD(KTX)                                                                                              \
+  case KTX:                                                                                                            \
+    fn = m->sequence ? forward_kernel<KTX, true> : forward_kernel<KTX, false>;                                         \
+    break;
+    FSMC_ALL_KT(FSMC_PICK_FWD)
+    FSMC_EXACT_KT(FSMC_PICK_FWD)
+#undef FSMC_PICK_FWD
+  default:
+    break;
+  }
+  k.fn = reinterpret_cast<KernelFn>(fn);
+  return k;
+}
+ForwardFn forwardFn(const KernelChoice& k)
+{
+  return reinterpret_cast<ForwardFn>(k.fn);
 }
 
 // A diagnostic switch that lowers a count: NAME=<n> gives n / divisor where that is at least 1 and below `value`.
@@ -1122,11 +1150,13 @@ int checkWholeSequence(fsmc_ctx* ctx, const fsmc_model* m, const char* what)
   return FSMC_OK;
 }
 
-// The slices of a call and its decode plan, `mode` kModeDump or kModePerPair.  The slice is the caller's setting, or
+// The slices of a call and its decode plan, `mode` kModeDump or kModePerPair -- or kNoDecode: the slices alone, for an
+// entry point that launches a kernel of its own and needs no workspace (fsmc_decode_pair_loglik).  The slice is the caller's setting, or
 // what stagingLimit holds of `groupBytes` a group, of half the room the card has free with the `held` bytes this entry
 // point's buffers hold already counted as free -- the decode's workspace is allocated after this -- and `sliceMost`
 // groups at the most.  One wave per window: planned from the first slice's groups; two waves: a workgroup for each group
 // of a slice.
+constexpr int kNoDecode = -1;
 int planSlices(fsmc_ctx* ctx, const fsmc_model* m, int mode, PairSlicing kind, uint64_t held, size_t groupBytes,
                WorkSlices& ws, size_t sliceMost = SIZE_MAX)
 {
@@ -1138,8 +1168,10 @@ int planSlices(fsmc_ctx* ctx, const fsmc_model* m, int mode, PairSlicing kind, u
   ws.ctx = ctx;
   ws.slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, sliceMost}));
   ws.nSlices = (ctx->nGroups + ws.slice - 1) / ws.slice;
-  const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)ws.slice);
-  FSMC_TRY(prepareDecode(ctx, m, mode, ctx->betaStride, first, ws.slice, 0, ws.plan));
+  if (mode != kNoDecode) {
+    const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)ws.slice);
+    FSMC_TRY(prepareDecode(ctx, m, mode, ctx->betaStride, first, ws.slice, 0, ws.plan));
+  }
   ws.slicePairsMax = 0;
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     ws.slicePairsMax = std::max(ws.slicePairsMax, ws.pairs(sl));
@@ -1422,6 +1454,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->ppAcc.p) (void)hipFree(ctx->ppAcc.p);
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
+  if (ctx->plAcc.p) (void)hipFree(ctx->plAcc.p);
   for (int i = 0; i < 2; ++i) {
     if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
     if (ctx->evCopied[i]) (void)hipEventDestroy(ctx->evCopied[i]);
@@ -1547,6 +1580,8 @@ int fsmc_ctx_set_pair_cdf_slice(fsmc_ctx* ctx, uint32_t groups) { return setPair
 int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceCdf, slices); }
 int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceTail, groups); }
 int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceTail, slices); }
+int fsmc_ctx_set_pair_loglik_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceLoglik, groups); }
+int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceLoglik, slices); }
 
 int fsmc_ctx_last_kernel(const fsmc_ctx* ctx, int32_t* member)
 {
@@ -2721,6 +2756,105 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
     }
   }
   ctx->pairSlices[kSliceBins].last = (int)ws.nSlices;
+  return FSMC_OK;
+}
+
+// Per pair, the likelihood of its observations as a mantissa / exponent pair, over the whole sequence and over bins of
+// sites (fsmc_pair_loglik.h): the forward sweep alone, one launch of forward_kernel a slice -- no decode plan, no
+// workspace.  The slice's values are copied to the caller's arrays at the slice's first pair; slices are independent.
+int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* bin_edges, size_t n_bins, double* mant,
+                            int32_t* expo, double* bin_mant, int32_t* bin_expo)
+{
+  FSMC_TRY(checkReady(ctx, m));
+  if ((mant != nullptr) != (expo != nullptr) || (bin_mant != nullptr) != (bin_expo != nullptr)) {
+    return fail(ctx, FSMC_EINVAL, "a mantissa and its exponent come together");
+  }
+  if (!mant && !bin_mant) {
+    return fail(ctx, FSMC_EINVAL, "need at least one pair of outputs (mant / expo, bin_mant / bin_expo)");
+  }
+  if (bin_mant) {
+    if (!bin_edges) {
+      return fail(ctx, FSMC_EINVAL, "the bin outputs need bin edges");
+    }
+    FSMC_TRY(checkBinEdges(ctx, m, bin_edges, n_bins));
+  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair log-likelihoods"));
+  const KernelChoice k = chooseForwardKernel(m);
+  if (!k.fn) {
+    return fail(ctx, FSMC_EINVAL, "per-pair log-likelihoods: no forward kernel for a model of more than 128 states (" +
+                                      std::to_string(m->K) + ")");
+  }
+  const size_t B = bin_mant ? n_bins : 0;
+  const size_t groupBytes = (size_t)kWave * (sizeof(double) + sizeof(int32_t)) * (1 + B);
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceLoglik, ctx->plAcc.bytes, groupBytes, ws));
+  int perCU = 0;
+  const hipError_t eo = workgroupsPerCU(k, 8, 1, perCU);
+  if (eo != hipSuccess) {
+    return fail(ctx, FSMC_EHIP, std::string("occupancy query of the forward kernel: ") + hipGetErrorString(eo));
+  }
+  LaunchPlan plan;
+  plan.k = k;
+  plan.slots = (int)std::max<size_t>(1, std::min((size_t)ctx->nCU * (size_t)std::max(perCU, 1), ws.slice));
+
+  // [mant][bin mant] doubles, [expo][bin expo] ints of the largest slice, then the edges
+  const size_t n = ws.slicePairsMax;
+  const size_t offBinMant = n * sizeof(double), offExpo = offBinMant + n * B * sizeof(double),
+               offBinExpo = offExpo + n * sizeof(int32_t), offEdges = offBinExpo + n * B * sizeof(int32_t);
+  FSMC_TRY(ensure(ctx, ctx->plAcc, offEdges + (B + 1) * sizeof(int32_t)));
+  char* const acc = (char*)ctx->plAcc.p;
+  if (B) {
+    FSMC_HIP(ctx, hipMemcpyAsync(acc + offEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 ctx->stream));
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  FwdParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.S = m->S;
+  p.W = (int)ctx->W;
+  p.B = (int)B;
+  p.pi = m->pi;
+  p.cR = m->cR;
+  p.rowSets = m->rowSets;
+  p.stepRow = m->stepRow;
+  p.rowGapF = m->rowGapF;
+  p.emis3 = m->emis3;
+  p.haps = ctx->dHaps;
+  p.pairs = ctx->dPairs;
+  p.counter = ctx->dCounters;
+  p.edges = B ? (const int*)(acc + offEdges) : nullptr;
+  p.mant = mant ? (double*)acc : nullptr;
+  p.expo = mant ? (int*)(acc + offExpo) : nullptr;
+  p.binMant = B ? (double*)(acc + offBinMant) : nullptr;
+  p.binExpo = B ? (int*)(acc + offBinExpo) : nullptr;
+  recordLaunch(ctx, k, plan);
+
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    const size_t nG = ws.groups(sl), first = ws.firstPair(sl), nP = ws.pairs(sl);
+    p.groups = ctx->dGroups + ws.firstGroup(sl);
+    p.nGroups = (int)nG;
+    p.pairBase = (unsigned)first;
+    FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
+    if (sl == 0) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    }
+    hipLaunchKernelGGL(forwardFn(k), dim3((unsigned)std::min<size_t>((size_t)plan.slots, nG)), dim3(k.threads), 0,
+                       ctx->stream, p);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every slice's launch)
+    ctx->timed = true;
+    // the slice's values go to the caller before the next slice overwrites them (12 bytes a pair and output)
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (mant) {
+      FSMC_HIP(ctx, hipMemcpy(mant + first, acc, nP * sizeof(double), hipMemcpyDeviceToHost));
+      FSMC_HIP(ctx, hipMemcpy(expo + first, acc + offExpo, nP * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (B) {
+      FSMC_HIP(ctx, hipMemcpy(bin_mant + first * B, acc + offBinMant, nP * B * sizeof(double), hipMemcpyDeviceToHost));
+      FSMC_HIP(ctx, hipMemcpy(bin_expo + first * B, acc + offBinExpo, nP * B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+  }
+  ctx->pairSlices[kSliceLoglik].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 

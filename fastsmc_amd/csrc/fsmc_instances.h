@@ -20,6 +20,8 @@
 //   waves of 64; 512 < K <= 1024: eight waves of 80, 96 or 128 (no landing zones).
 // Any-K kernel (decode_kernel_any<MODE, TRACK, SEQ>, fsmc_kernels_any.h): K > 1024, a pair's K-vectors in the workspace
 //   instead of registers -- correct, not fast; small enough to be instantiated where it is picked (fsmc_capi.hip).
+// Forward-only kernel (forward_kernel<KT, SEQ>, fsmc_pair_loglik.h): the per-pair likelihoods of every lane-per-pair
+//   member, array and sequence mode; the wave-group and any-K families have none.
 // (The runtime-K instantiation KT = 0 and the four-lanes-per-pair kernel of earlier builds are gone: every model of at
 //  most 256 states, in every mode, runs one of the two families above.)
 #pragma once
@@ -28,6 +30,7 @@
 #include "fsmc_kernels_any.h"
 #include "fsmc_kernels_bidir.h"
 #include "fsmc_kernels_w2.h"
+#include "fsmc_pair_loglik.h"
 
 namespace fsmc
 {
@@ -96,6 +99,10 @@ constexpr bool halfSumsBuilt(const int KT)
 #define FSMC_DEFINE_KT_DUAL_HALF(KT)                                                                                   \
   template __global__ void decode_kernel<KT, kModeIbd, true, false, true, true>(const KParams);                      \
   template __global__ void decode_kernel<KT, kModeIbd, false, false, true, true>(const KParams);
+// the forward sweep alone (fsmc_pair_loglik.h): array mode and sequence mode
+#define FSMC_KT_FWD_KERNELS(X, KT) X(KT, false) X(KT, true)
+#define FSMC_DECLARE_KT_FWD(KT, SEQ) extern template __global__ void forward_kernel<KT, SEQ>(const FwdParams);
+#define FSMC_DEFINE_KT_FWD(KT, SEQ) template __global__ void forward_kernel<KT, SEQ>(const FwdParams);
 // NW waves per group of KH states each, lane = pair (fsmc_kernels_w2.h): 128 < K <= 512
 #define FSMC_W2_MODE_KERNELS(X, KH, NW, SEQ)                                                                           \
   X(KH, kModeIbd, true, SEQ, NW)                                                                                       \
@@ -115,12 +122,15 @@ constexpr bool halfSumsBuilt(const int KT)
 #define FSMC_ALL_W2(Y) Y(48, 4) Y(64, 4) Y(80, 4) Y(64, 6) Y(64, 7) Y(64, 8) Y(80, 8) Y(96, 8) Y(128, 8)
 
 #if !defined(FSMC_INSTANCE_KT) && !defined(FSMC_INSTANCE_W2)
-#define FSMC_DECLARE_MEMBER(KT) FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT) FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT)
+#define FSMC_DECLARE_MEMBER(KT)                                                                                         \
+  FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT)                                                                                  \
+  FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT) FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)
 FSMC_ALL_KT(FSMC_DECLARE_MEMBER)
 #define FSMC_DECLARE_EXACT_MEMBER(KT)                                                                                   \
   static_assert(KT % 16 != 0 && KT <= 128, "an exact member is not a multiple of 16 states and has at most 128");       \
   FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT)                                                                                  \
   FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT)                                                                      \
+  FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)                                                                          \
   FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, KT)                                                                             \
   FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, KT)                                                                        \
   FSMC_DECLARE_KT_DUAL_HALF(KT)                                                                                         \

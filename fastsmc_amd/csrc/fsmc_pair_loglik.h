@@ -1,0 +1,258 @@
+// fsmc_pair_loglik.h -- per pair, the likelihood of the pair's observations under the model from the forward sweep
+// alone (fsmc_decode_pair_loglik): one of the decode's three sweeps, no beta rows, no workspace, no checkpoints.
+//
+// The definition (the contract of the entry point).  For a pair whose group is the whole sequence let sum[t] (fp32) be
+// the scaling sum of the forward vector at site t: the `sums` of calculateScalingBatch at HMM.cpp:745 and 776-779,
+// accumulated from 0.f over k ascending in separately rounded adds (ghost states add +0).  Array mode: sum[0] comes
+// from pi * emission and sum[t] from the step into site t.  Sequence mode: the un-normalised half-step across the gap
+// contributes no sum of its own; sum[t] is the sum after the site step that follows it (HMM.cpp:760-779).  The product
+// of the sums is P(observations of the pair | model); it is carried as a mantissa / exponent pair so that the result is
+// bit-reproducible:
+//     m = 1.0 (fp64); e = 0 (int32)
+//     for t = 0 .. S-1, ascending:
+//         m = m * (double)sum[t]                                       // one fp64 multiply, round to nearest
+//         if (m != 0 && isfinite(m)) { m = frexp(m, &de); e += de; }   // exact
+// mant[i] = m (in [0.5, 1), or 0 / inf / NaN), expo[i] = e, in work-list order; the log-likelihood is
+// log(mant) + expo * ln 2, formed on the host in fp64 (a zero sum gives -inf, a NaN stays a NaN).
+// With bin edges e[0] < ... < e[B] (the rules of fsmc_decode_pair_bins) bin_mant[i][b] / bin_expo[i][b] are the same
+// recurrence started afresh at m = 1, e = 0 at site e[b] and taken at site e[b+1] - 1: the conditional likelihood of the
+// bin's observations given everything before it.  Sites outside every bin count towards the total only; the total is a
+// chain of its own over all sites, not a combination of the bins.
+//
+// forward_kernel<KT, SEQ>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue.
+// The arithmetic of a site is the decode's (fsmc_kernels.h): alpha_step<..., SCALE = false>, the ascending sum of what
+// it leaves (the adds of the scaled step, in its order: the compiler folds the two chains into one), scale_pk; the first
+// site is alpha_init with its sum handed back (forwardInit).  Everything around the steps is this kernel's own: the
+// observation classes from the packed haplotype words, a two-slot LDS ring of emission rows fed by LDS-DMA one site
+// ahead (three rows a site, four in sequence mode), the table rows of 64 consecutive sites in one register, the fp64
+// recurrence and the bins.  The site loop is wave-uniform, so the open bin is scalar state; a bin's two values leave
+// with ordinary vector stores when it closes.  No workspace: the kernel's HBM traffic is the emission rows (12 or 16
+// bytes a state and site for the WAVE, not the pair) and 12 bytes a pair and output.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+
+#include "fsmc_kernels.h"
+
+namespace fsmc
+{
+
+struct FwdParams {
+  int S;       // sites
+  int W;       // 64-bit words per haplotype row
+  int nGroups; // groups of the slice
+  int B;       // bins (0: none)
+  unsigned pairBase; // first pair of the slice: the outputs are indexed by pair of the work list minus this
+  const float* pi;      // [KP]
+  const float* cR;      // [KP]
+  const float* rowSets; // [rows][5][KP]
+  const int* stepRow;   // [S] row of the (site) step into site q
+  const int* rowGapF;   // [S] sequence mode: row of the half-step across the gap (q-1, q)
+  const float4* emis3;  // [S][3 or 4][KP/4]
+  const unsigned long long* haps; // [nHaps][W]
+  const fsmc_pair* pairs;
+  const fsmc_group* groups; // the slice's first group
+  unsigned* counter;        // head of the group queue
+  const int* edges;         // [B + 1], or null
+  double* mant;             // [pairs of the slice], or null
+  int* expo;
+  double* binMant;          // [pairs of the slice][B], or null
+  int* binExpo;
+};
+
+// Operand loads of the steps: asynchronous and one block ahead where the compiled instantiation passes the in-flight
+// check (tools/check_inflight_sgprs.py, tests/test_isa_hazards.py), synchronous (LD<N, true>) where it does not: the
+// 32-state member in both modes, whose allocation spills operand blocks behind their loads (v_writelane of
+// registers in flight); every other instantiation of the default build is clean.
+template <int KT, bool SEQ> constexpr bool kFwdSyncLoads = KT == 32;
+
+// alpha at the first site, NOT yet scaled, and its sum: the operations of alpha_init up to its 1.0f / sum
+// (HMM.cpp:736-747), k ascending from 0.f.
+template <int KT, int KA> __device__ __forceinline__ float forwardInit(float (&a)[KA], cfloat_p pi, const float4* e)
+{
+  float sum = 0.f;
+  float4 ev = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < KT; ++k) {
+    if ((k & 3) == 0) {
+      ev = e[k >> 2];
+    }
+    const float em = (k & 3) == 0 ? ev.x : (k & 3) == 1 ? ev.y : (k & 3) == 2 ? ev.z : ev.w;
+    a[k] = pi[k] * em;
+    sum = sum + a[k];
+  }
+  return sum;
+}
+
+// One site of the recurrence of the header: (m, e) <- (m, e) * s.
+__device__ __forceinline__ void likelihoodTimes(double& m, int& e, const double s)
+{
+  m = m * s;
+  if (m != 0.0 && __builtin_isfinite(m)) {
+    int de = 0;
+    m = __builtin_frexp(m, &de);
+    e += de;
+  }
+}
+
+// grid: any number of single-wave workgroups, no dynamic LDS.
+template <int KT, bool SEQ>
+__global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(const FwdParams p)
+{
+  static_assert(KT >= 2 && KT <= 128, "a lane-per-pair member (fsmc_instances.h)");
+  constexpr int KA = KT;
+  constexpr int K = KT;
+  constexpr int E4 = ((KT + kKPad - 1) / kKPad) * (kKPad / 4); // float4 per emission row: KP / 4 of the member's models
+  constexpr int NC = SEQ ? 4 : 3;                              // rows per site: the observation classes (+ the gap)
+  constexpr int NL = (NC * E4 + kWave - 1) / kWave;            // DMA requests per site
+  constexpr bool SY = kFwdSyncLoads<KT, SEQ>;
+
+  __shared__ float4 ring[2][NC * E4];
+
+  const int lane = threadIdx.x;
+  const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
+  const cfloat_p tPi = (cfloat_p)p.pi;
+  const Tables tabs = {(cfloat_p)p.rowSets, (cfloat_p)p.cR, (cfloat_p) nullptr};
+  const cint_p tEdges = (cint_p)p.edges;
+  const int S = p.S;
+  const int B = p.B;
+
+  for (;;) {
+    unsigned g = 0;
+    if (lane == 0) {
+      g = atomicAdd(p.counter, 1u);
+    }
+    g = __builtin_amdgcn_readfirstlane(g);
+    if (g >= (unsigned)p.nGroups) {
+      break;
+    }
+    const cuint_p gw = (cuint_p)(p.groups + (size_t)g);
+    const unsigned firstPair = gw[0];
+    const int nPairsInGroup = (int)gw[1];
+    const bool valid = lane < nPairsInGroup;
+    const unsigned pairIdx = firstPair + (valid ? (unsigned)lane : 0u); // (an idle lane repeats the group's first pair)
+    const size_t outIdx = (size_t)(pairIdx - p.pairBase);
+    const fsmc_pair pr = p.pairs[pairIdx];
+    const unsigned long long* rowA = p.haps + (size_t)pr.hap_a * p.W;
+    const unsigned long long* rowB = p.haps + (size_t)pr.hap_b * p.W;
+
+    // observation class of this lane's pair at site q: 0 het, 1 hom major, 2 hom minor (obsIsZero / obsIsTwo of
+    // HMM.cpp:647-652 as a row select); the two words of 64 sites are read once per 64 sites
+    int wordIdx = -1;
+    unsigned long long xw = 0, aw = 0;
+    auto obsClass = [&](const int q) -> int {
+      const int wi = q >> 6;
+      if (__builtin_expect(wi != wordIdx, 0)) {
+        const unsigned long long wa = rowA[wi];
+        const unsigned long long wb = rowB[wi];
+        xw = wa ^ wb;
+        aw = wa & wb;
+        wordIdx = wi;
+      }
+      const int bit = q & 63;
+      return ((xw >> bit) & 1ull) ? 0 : 1 + (int)((aw >> bit) & 1ull);
+    };
+    // site q's rows into ring slot (q & 1): asynchronous, counted in vmcnt, visible to this wave's LDS reads behind a
+    // vmcnt wait that covers it; the slot's previous rows must no longer be read
+    auto stage = [&](const int q) {
+      const gchar_p src = uniformPtr(p.emis3 + (size_t)q * (NC * E4));
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        if (lane + i * kWave < NC * E4) {
+          dmaToLds((gf32x4_p)(src + (size_t)i * (kWave * sizeof(float4)) + laneOff), &ring[q & 1][i * kWave]);
+        }
+      }
+    };
+    // every request so far has landed and this wave's LDS reads may see it
+    auto landedRows = [&]() {
+      waitVm0();
+      __builtin_amdgcn_wave_barrier();
+      FSMC_GCN_ASM("" ::: "memory");
+    };
+    // table rows: the indices of 64 consecutive sites sit in one register (lane = site % 64, one coalesced load per 64
+    // sites, waited for on the spot) and are picked with v_readlane
+    int stepBlk = -1, stepVec = 0, gapBlk = -1, gapVec = 0;
+    auto rowOf = [&](const int* rows, int& blkHeld, int& vec, const int site) -> int {
+      const int blk = site >> 6;
+      if (__builtin_expect(blk != blkHeld, 0)) {
+        const int idx = blk * kWave + lane;
+        vec = rows[idx < S ? idx : S - 1];
+        blkHeld = blk;
+        waitVm0();
+      }
+      return __builtin_amdgcn_readlane(vec, site & (kWave - 1));
+    };
+
+    // the open bin: [lo, hi) = edges[bin], edges[bin + 1]; beyond the last bin lo = INT_MAX
+    int bin = 0;
+    int lo = INT_MAX, hi = INT_MAX;
+    if (B > 0) {
+      lo = tEdges[0];
+      hi = tEdges[1];
+    }
+    double m = 1.0, bm = 1.0;
+    int e = 0, be = 0;
+
+    float a[KA], w[KA];
+    Diag dg;
+    stage(0);
+    for (int pos = 0; pos < S; ++pos) {
+      if (!SEQ || pos == 0) {
+        landedRows(); // the rows of site pos (sequence mode: the half-step towards pos waited for them)
+      }
+      if (pos + 1 < S) {
+        stage(pos + 1); // into the slot of site pos - 1, whose steps are over
+      }
+      const int c = obsClass(pos);
+      const float4* er = &ring[pos & 1][c * E4];
+      float sum;
+      if (__builtin_expect(pos == 0, 0)) {
+        sum = forwardInit<KT, KA>(a, tPi, er);
+      } else {
+        alpha_step<KT, KA, false, SY>(K, a, w, tabs, rowOf(p.stepRow, stepBlk, stepVec, pos), er, dg);
+        sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          sum = sum + a[k];
+        }
+      }
+      scale_pk<KT, KA>(a, a, sum);
+
+      const double sd = (double)sum;
+      likelihoodTimes(m, e, sd);
+      if (pos >= lo) { // inside the open bin (pos < hi: a bin is closed at its last site)
+        if (pos == lo) {
+          bm = 1.0;
+          be = 0;
+        }
+        likelihoodTimes(bm, be, sd);
+        if (pos == hi - 1) {
+          if (valid) {
+            p.binMant[outIdx * (size_t)B + (size_t)bin] = bm;
+            p.binExpo[outIdx * (size_t)B + (size_t)bin] = be;
+          }
+          ++bin;
+          lo = bin < B ? hi : INT_MAX;
+          hi = bin < B ? tEdges[bin + 1] : INT_MAX;
+        }
+      }
+
+      if constexpr (SEQ) {
+        // the un-normalised half-step across the gap to the next site (HMM.cpp:760-767): no sum of its own
+        if (pos + 1 < S) {
+          landedRows(); // the rows of site pos + 1: its fourth row is the homozygous emission of the gap before it
+          alpha_step<KT, KA, false, SY>(K, a, w, tabs, rowOf(p.rowGapF, gapBlk, gapVec, pos + 1),
+                                        &ring[(pos + 1) & 1][3 * E4], dg);
+        }
+      }
+    }
+    if (valid && p.mant) {
+      p.mant[outIdx] = m;
+      p.expo[outIdx] = e;
+    }
+  }
+}
+
+} // namespace fsmc

@@ -597,6 +597,13 @@ void HMM::setStoreSumOfPosterior(bool v) { changeOutputs([&] { mOutputs.sumOfPos
 void HMM::setStoreMinPosteriorMean(bool v) { changeOutputs([&] { mOutputs.minMeans = v; }); }
 void HMM::setStoreMinMap(bool v) { changeOutputs([&] { mOutputs.minMaps = v; }); }
 
+void HMM::setStoreLogLikelihoods(bool v)
+{
+  PairOutputs next = mOutputs;
+  next.logLikelihoods = v;
+  setPairOutputs(next);
+}
+
 // (the rest of the request passed its check when it was set: only the part that changes can be refused)
 void HMM::setSiteBins(const std::vector<int>& edges)
 {
@@ -995,6 +1002,9 @@ void HMM::flushPairOutputs(size_t nPairs)
   if (!o.siteBins.empty()) {
     flushPairBins();
   }
+  if (o.logLikelihoods) {
+    flushPairLogLik(nPairs);
+  }
   if (o.cdf()) {
     flushPairCdf();
   }
@@ -1048,6 +1058,36 @@ void HMM::flushPairBins()
                               R.binArgminPosteriorMeans.data() + at, R.binMinMAPs.data() + at,
                               R.binArgminMAPs.data() + at),
         "fsmc_decode_pair_bins");
+}
+
+// per pair the likelihood of its observations, and per bin where bins are set, flush after flush at the pairs written so
+// far: the forward sweep alone, 12 bytes a pair and output cross the bus; the logarithms are formed here in fp64
+void HMM::flushPairLogLik(size_t nPairs)
+{
+  auto& R = mPairsReturn;
+  const std::vector<int>& edges = mOutputs.siteBins;
+  const size_t nBins = edges.empty() ? 0 : edges.size() - 1;
+  if (R.perPairLikelihoodMantissas.size() != static_cast<size_t>(R.numPairs) ||
+      R.binLikelihoodMantissas.size() != static_cast<size_t>(R.numPairs) * nBins ||
+      (nBins > 0 && R.request.siteBins != edges)) {
+    throw std::runtime_error("the return structure was not initialised for the log-likelihoods asked for");
+  }
+  const size_t at = R.numWritten, atBin = R.numWritten * nBins;
+  check(mCtx,
+        fsmc_decode_pair_loglik(mCtx, mModel, nBins ? edges.data() : nullptr, nBins,
+                                R.perPairLikelihoodMantissas.data() + at, R.perPairLikelihoodExponents.data() + at,
+                                nBins ? R.binLikelihoodMantissas.data() + atBin : nullptr,
+                                nBins ? R.binLikelihoodExponents.data() + atBin : nullptr),
+        "fsmc_decode_pair_loglik");
+  const double ln2 = std::log(2.0);
+  for (size_t i = at; i < at + nPairs; ++i) {
+    R.perPairLogLikelihoods[i] =
+        std::log(R.perPairLikelihoodMantissas[i]) + static_cast<double>(R.perPairLikelihoodExponents[i]) * ln2;
+  }
+  for (size_t i = atBin; i < atBin + nPairs * nBins; ++i) {
+    R.binLogLikelihoods[i] =
+        std::log(R.binLikelihoodMantissas[i]) + static_cast<double>(R.binLikelihoodExponents[i]) * ln2;
+  }
 }
 
 // per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far: 4 bytes a

@@ -121,6 +121,9 @@ public:
   // structure's min / argmin vectors; where the rows themselves are stored as well, finaliseCalculations makes them
   void setStoreMinPosteriorMean(bool v);
   void setStoreMinMap(bool v);
+  // per pair the likelihood of its observations (mantissa, exponent, logarithm), and per site bin where bins are set:
+  // the forward sweep alone (fsmc_decode_pair_loglik)
+  void setStoreLogLikelihoods(bool v);
   // per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins of sites
   // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
   // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
@@ -204,6 +207,7 @@ private:
   void flushPairOutputs(size_t nPairs);
   void flushPairMinima();
   void flushPairBins();
+  void flushPairLogLik(size_t nPairs);
   void flushPairCdf();
   void flushPairTailSummaries(size_t nPairs);
   void flushPairPosteriors(size_t nPairs);

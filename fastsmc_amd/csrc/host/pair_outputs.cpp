@@ -88,6 +88,10 @@ void PairOutputs::check(long sites, long states) const
       }
     }
   }
+  if (logLikelihoods && states > 128) { // (the message of fsmc_decode_pair_loglik)
+    throw std::runtime_error("per-pair log-likelihoods: no forward kernel for a model of more than 128 states (" +
+                             std::to_string(states) + ")");
+  }
 }
 
 void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs)
@@ -123,6 +127,13 @@ void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states,
   sumOfTailProbabilities.assign(o.tailSummaryStates.size() * S, 0.0);
   binTailMeans.assign(o.tailSummaryStates.size() * cells, 0.f);
   binTailLengths.assign(o.siteWeights.empty() ? 0 : o.tailSummaryStates.size() * cells, 0.f);
+  // the likelihoods: [pairs] and [pairs][bins]
+  perPairLikelihoodMantissas.assign(o.logLikelihoods ? nPairs : 0, 0.0);
+  perPairLikelihoodExponents.assign(o.logLikelihoods ? nPairs : 0, 0);
+  perPairLogLikelihoods.assign(o.logLikelihoods ? nPairs : 0, 0.0);
+  binLikelihoodMantissas.assign(o.logLikelihoods ? cells : 0, 0.0);
+  binLikelihoodExponents.assign(o.logLikelihoods ? cells : 0, 0);
+  binLogLikelihoods.assign(o.logLikelihoods ? cells : 0, 0.0);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()

@@ -33,10 +33,14 @@ struct PairOutputs {
   std::vector<float> tailSummaryTimes;
   std::vector<int> tailSummaryStates;
   std::vector<float> siteWeights;
+  // per pair, the likelihood of its observations as mantissa, exponent and logarithm, from the forward sweep alone
+  // (fsmc_decode_pair_loglik); with siteBins also per bin, started afresh at the bin's first site
+  bool logLikelihoods = false;
 
   // Throws what the ABI would refuse, with its messages: more than 8 tail states or quantiles, a cut outside [1, states],
   // a quantile outside (0, 1]; then the same for the tail summaries, and weights without cuts, not one a site or not
-  // finite; then fewer than two bin edges, edges outside [0, sites] or not strictly ascending.
+  // finite; then fewer than two bin edges, edges outside [0, sites] or not strictly ascending; then log-likelihoods of a
+  // model of more than 128 states.
   void check(long sites, long states) const;
 
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
@@ -47,7 +51,7 @@ struct PairOutputs {
   bool any() const
   {
     return means || maps || posteriors || sumOfPosteriors || minMeansOnDevice() || minMapsOnDevice() ||
-           !siteBins.empty() || cdf() || !tailSummaryStates.empty();
+           !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods;
   }
 };
 
@@ -74,6 +78,12 @@ struct DecodePairsReturnStruct {
   // weights, the weighted sum over it, [tails][pairs][bins] (empty without bins / without weights)
   std::vector<double> sumOfTailProbabilities;
   std::vector<float> binTailMeans, binTailLengths;
+  // the likelihood of each pair's observations: likelihood = mantissa * 2^exponent, logLikelihood = log(mantissa) +
+  // exponent * ln 2 in fp64; [pairs], and with bins [pairs][bins]: the bin's observations given everything before it
+  std::vector<double> perPairLikelihoodMantissas, perPairLogLikelihoods;
+  std::vector<int> perPairLikelihoodExponents;
+  std::vector<double> binLikelihoodMantissas, binLogLikelihoods;
+  std::vector<int> binLikelihoodExponents;
   size_t numWritten = 0;
 
   void initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs);

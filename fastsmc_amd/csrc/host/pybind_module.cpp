@@ -100,10 +100,11 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
   c.def(
       "decodePairs",
       [](ASMC& self, const std::vector<Id>& a, const std::vector<Id>& b, bool perPairPosteriors, bool sumOfPosteriors,
-         bool perPairPosteriorMeans, bool perPairMAPs, bool minPosteriorMeans, bool minMAPs,
+         bool perPairPosteriorMeans, bool perPairMAPs, bool minPosteriorMeans, bool minMAPs, bool logLikelihoods,
          const std::vector<int>& siteBins, const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
          const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights) {
         PairOutputs o;
+        o.logLikelihoods = logLikelihoods;
         o.posteriors = perPairPosteriors;
         o.sumOfPosteriors = sumOfPosteriors;
         o.means = perPairPosteriorMeans;
@@ -119,7 +120,7 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       },
       py::arg(listA), py::arg(listB), "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
       "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-      "min_MAPs"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
+      "min_MAPs"_a = false, "log_likelihoods"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
       "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
       "site_weights"_a = std::vector<float>{},
       "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
@@ -141,7 +142,12 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       "and, with site_bins, per_pair_bin_tail_means ([tails][pairs][B] float32: the mean over the bin in the fp64 "
       "order of bin_mean_posterior_means) and, with site_weights ([sites] float32, finite; api.site_widths gives "
       "the centimorgans a site stands for) as well, per_pair_bin_tail_lengths (the sum of tail * weight over the bin "
-      "in that order).");
+      "in that order).  log_likelihoods: per pair the likelihood of its observations under the model from the forward "
+      "sweep alone (models of at most 128 states), bit-reproducible as per_pair_likelihood_mantissas ([pairs] float64 in "
+      "[0.5, 1), or 0 / inf / NaN) and per_pair_likelihood_exponents ([pairs] int32); per_pair_log_likelihoods ([pairs] "
+      "float64) is log(mantissa) + exponent * ln 2.  With site_bins also per_pair_bin_log_likelihoods, "
+      "per_pair_bin_likelihood_mantissas, per_pair_bin_likelihood_exponents ([pairs][B]): the likelihood of the bin's "
+      "observations given everything before it -- a bin a pair fits badly stands out.");
 }
 
 } // namespace
@@ -208,7 +214,15 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("site_weights", [](const Pairs& r) { return shaped(r.request.siteWeights, r.request.siteWeights.size()); })
       .def_property_readonly("sum_of_tail_probabilities", [](const Pairs& r) { return shaped(r.sumOfTailProbabilities, r.request.tailSummaryStates.size(), r.numSites); })
       .def_property_readonly("per_pair_bin_tail_means", [](const Pairs& r) { return shaped(r.binTailMeans, r.request.tailSummaryStates.size(), r.numPairs, numBins(r)); })
-      .def_property_readonly("per_pair_bin_tail_lengths", [](const Pairs& r) { return shaped(r.binTailLengths, r.request.tailSummaryStates.size(), r.numPairs, numBins(r)); });
+      .def_property_readonly("per_pair_bin_tail_lengths", [](const Pairs& r) { return shaped(r.binTailLengths, r.request.tailSummaryStates.size(), r.numPairs, numBins(r)); })
+      // the likelihood of each pair's observations, mantissa * 2^exponent, and its natural logarithm: [pairs], and per
+      // site bin (the bin's observations given everything before it) [pairs][bins]; empty where not asked for
+      .def_property_readonly("per_pair_log_likelihoods", [](const Pairs& r) { return shaped(r.perPairLogLikelihoods, r.perPairLogLikelihoods.size()); })
+      .def_property_readonly("per_pair_likelihood_mantissas", [](const Pairs& r) { return shaped(r.perPairLikelihoodMantissas, r.perPairLikelihoodMantissas.size()); })
+      .def_property_readonly("per_pair_likelihood_exponents", [](const Pairs& r) { return shaped(r.perPairLikelihoodExponents, r.perPairLikelihoodExponents.size()); })
+      .def_property_readonly("per_pair_bin_log_likelihoods", [](const Pairs& r) { return shaped(r.binLogLikelihoods, r.numPairs, numBins(r)); })
+      .def_property_readonly("per_pair_bin_likelihood_mantissas", [](const Pairs& r) { return shaped(r.binLikelihoodMantissas, r.numPairs, numBins(r)); })
+      .def_property_readonly("per_pair_bin_likelihood_exponents", [](const Pairs& r) { return shaped(r.binLikelihoodExponents, r.numPairs, numBins(r)); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -466,6 +480,9 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setStoreMinMap", &HMM::setStoreMinMap, "storeMinMAP"_a = true,
            "per site the smallest MAP state over the decoded pairs and the first pair that has it, computed on the "
            "device where the per-pair rows are not stored")
+      .def("setStoreLogLikelihoods", &HMM::setStoreLogLikelihoods, "storeLogLikelihoods"_a = true,
+           "per pair the likelihood of its observations (mantissa, exponent, logarithm), per site bin where bins are "
+           "set: the forward sweep alone, computed on the device")
       .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
            "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
            "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")

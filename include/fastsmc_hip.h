@@ -29,6 +29,9 @@
  *                             perPairPosteriors; the sum's order is the IBD scan's, HMM.cpp:1207-1224)
  *   fsmc_decode_pair_tail_summaries <- the tail probabilities of fsmc_decode_pair_cdf, summed over the pairs per site and
  *                             reduced over bins of sites per pair (none: the reference's callers do this in numpy)
+ *   fsmc_decode_pair_loglik <- the forward half of decodeBatch, its per-site scaling sums kept (HMM.cpp:725-784); the
+ *                             product of the sums, the pair's data likelihood, has no counterpart: the reference
+ *                             uses every sum for 1.0f / sum and drops it
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -220,6 +223,11 @@ int fsmc_ctx_last_pair_cdf_slices(const fsmc_ctx* ctx, int32_t* slices);
  * of staging plus 64 * 4 bytes * (S + n_bins a bin output) a group and cut).  Results do not depend on it. */
 int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_loglik.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of outputs (64 * 12 bytes * (1 + n_bins) a group): in practice the
+ * whole work list.  Results do not depend on it. */
+int fsmc_ctx_set_pair_loglik_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -375,6 +383,35 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
 int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_coal_times, const int32_t* bin_edges,
                           size_t n_bins, float* bin_mean, float* bin_min_mean, int32_t* bin_argmin_mean,
                           int32_t* bin_min_map, int32_t* bin_argmin_map);
+
+/* Per pair of the resident work list, the likelihood of the pair's observations under the model, from the forward sweep
+ * alone: one of the decode's three sweeps, no beta rows, no workspace (fsmc_pair_loglik.h; lane-per-pair kernels, K <=
+ * 128).  For a pair whose group is the whole sequence let sum[t] (fp32) be the scaling sum of the forward vector at site
+ * t: the `sums` of calculateScalingBatch at HMM.cpp:745 and 776-779, accumulated from 0.f over k ascending in separately
+ * rounded adds (ghost states add +0).  Array mode: sum[0] comes from pi * emission and sum[t] from the step into site t.
+ * Sequence mode: the un-normalised half-step across the gap contributes no sum of its own; sum[t] is the sum after the
+ * site step that follows it (HMM.cpp:760-779).  The likelihood, the product of the sums, is carried as a mantissa /
+ * exponent pair so that the result is bit-reproducible:
+ *     m = 1.0 (fp64); e = 0 (int32)
+ *     for t = 0 .. S-1, ascending:
+ *         m = m * (double)sum[t]                                       -- one fp64 multiply, round to nearest
+ *         if (m != 0 && isfinite(m)) { m = frexp(m, &de); e += de; }   -- exact
+ *   mant[i] (float64, in [0.5, 1), or 0 / inf / NaN) and expo[i] (int32), [n_pairs] each in work-list order.  The
+ *     log-likelihood is log(mant) + expo * ln 2, formed by the caller in fp64: a zero sum gives -inf, a NaN stays a NaN.
+ *   bin_mant[i * n_bins + b], bin_expo[i * n_bins + b]: the same recurrence started afresh at m = 1, e = 0 at site
+ *     bin_edges[b] and taken at site bin_edges[b + 1] - 1: the conditional likelihood of the bin's observations given
+ *     everything before it.  Sites outside every bin count towards the total only; the total is a chain of its own over
+ *     all sites, not a combination of the bins.
+ * mant / expo: both or neither; bin_mant / bin_expo: both or neither, and only with edges; one pair of outputs at least.
+ * bin_edges: n_bins + 1 int32 values under the rules of fsmc_decode_pair_bins; read only with the bin outputs.  The work
+ * list goes through the device in slices of groups (fsmc_ctx_set_pair_loglik_slice), which are independent; 12 bytes a
+ * pair and output cross the bus.  fsmc_ctx_last_kernel reports the member; fsmc_last_kernel_ms spans the call's launches
+ * (with several slices also the copies of their outputs in between).  FSMC_EINVAL, nothing touched: a mantissa without
+ * its exponent or the reverse; no output; bin outputs without edges, n_bins == 0, edges not strictly ascending or outside
+ * [0, S]; a group that is not the whole sequence (from = 0, to = S); a model of more than 128 states (the wave-group
+ * and any-K kernels have no forward-only member). */
+int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* bin_edges, size_t n_bins, double* mant,
+                            int32_t* expo, double* bin_mant, int32_t* bin_expo);
 
 /* Per pair of the resident work list and site, where the posterior mass lies, without the [K][S] tables leaving the
  * device.  post[k] is the pair's normalised fp32 posterior at the site over the model's K states (not multiplied by any
