@@ -15,7 +15,7 @@ from ._pyasmc import (ASMC, BinaryDataReader, Data, DecodePairsReturnStruct, Dec
 __all__ = ["ASMC", "BinaryDataReader", "IbdPairDataLine", "Data", "DecodePairsReturnStruct", "DecodingMode", "DecodingModeOverall", "DecodingParams",
            "DecodingQuantities", "DecodingReturnValues", "FastSMC", "HMM", "Individual", "PairObservations", "Match", "cmBetween",
            "hashingCandidates", "hashingCandidatesDevice", "hashingWords",
-           "decoding_quantities_from_tables", "PreparedModelView", "site_bins", "tail_states", "site_widths"]
+           "decoding_quantities_from_tables", "PreparedModelView", "site_bins", "tail_states", "site_widths", "state_runs"]
 
 
 def decoding_quantities_from_tables(t) -> DecodingQuantities:
@@ -76,6 +76,20 @@ def tail_states(discretization, times) -> np.ndarray:
         bad = float(t[np.nonzero(cuts == 0)[0][0]])
         raise ValueError(f"tail_states: tail time {bad}: no interval of the discretization starts below it")
     return cuts
+
+
+def state_runs(row):
+    """The run-length form of one row of ``per_pair_viterbi_states`` (or of any row of states): ``(starts, ends, states)``,
+    three arrays of one entry a run; run ``r`` is sites ``[starts[r], ends[r])``, all in state ``states[r]``, and
+    neighbouring runs differ in state.  ``starts[0] = 0`` and ``ends[-1] = len(row)``; an empty row gives three empty
+    arrays.  The piecewise-constant TMRCA track of a pair is ``expectedTimes[states]`` over these segments."""
+    row = np.asarray(row).reshape(-1)
+    if row.size == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), row.copy()
+    cut = np.flatnonzero(row[1:] != row[:-1]) + 1
+    starts = np.concatenate([np.zeros(1, np.int64), cut.astype(np.int64)])
+    ends = np.concatenate([cut.astype(np.int64), np.full(1, row.size, np.int64)])
+    return starts, ends, row[starts]
 
 
 def site_widths(genetic_positions) -> np.ndarray:

@@ -40,6 +40,7 @@ SYMBOLS = [
     "fsmc_decode_pair_cdf", "fsmc_ctx_set_pair_cdf_slice", "fsmc_ctx_last_pair_cdf_slices",
     "fsmc_decode_pair_tail_summaries", "fsmc_ctx_set_pair_tail_slice", "fsmc_ctx_last_pair_tail_slices",
     "fsmc_decode_pair_loglik", "fsmc_ctx_set_pair_loglik_slice", "fsmc_ctx_last_pair_loglik_slices",
+    "fsmc_decode_pair_viterbi", "fsmc_ctx_set_pair_viterbi_slice", "fsmc_ctx_last_pair_viterbi_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -150,6 +151,9 @@ def load():
         L.fsmc_decode_pair_loglik.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_ctx_set_pair_loglik_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_loglik_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_viterbi.argtypes = [vp, vp, vp, vp, vp]
+        L.fsmc_ctx_set_pair_viterbi_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_viterbi_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -519,6 +523,39 @@ class Context:
     def last_pair_loglik_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_loglik_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_viterbi(self, model: "Model", want_states=True, want_prob=True, out=None):
+        """Per pair of the resident work list, the most probable joint state sequence and its probability
+        (fsmc_decode_pair_viterbi): (states uint8 [n_pairs][S], mant f64 [n_pairs], expo i32 [n_pairs]); None for what was
+        not asked for.  ``log_likelihood(mant, expo)`` gives the natural logarithm of the probability of (path,
+        observations).  ``out``: three such arrays (None where not wanted, at least n_pairs rows), written in place and
+        returned as they are -- ``want_states`` and ``want_prob`` are ignored then."""
+        n, S = self._n_pairs, model.S
+        if out is None:
+            out = (np.zeros((n, S), np.uint8) if want_states else None, np.zeros(n, np.float64) if want_prob else None,
+                   np.zeros(n, np.int32) if want_prob else None)
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("out: (states, mant, expo)")
+        for i, (a, dt) in enumerate(zip(out, (np.uint8, np.float64, np.int32))):
+            if a is None:
+                continue
+            shape_ok = (a.ndim == 2 and a.shape[1] == S) if i == 0 else a.ndim == 1
+            if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or not shape_ok or a.shape[0] < n:
+                raise ValueError("out: writable C-contiguous arrays, uint8 states [>= n_pairs][S], float64 mantissas and "
+                                 "int32 exponents [>= n_pairs]")
+        self._check(self._L.fsmc_decode_pair_viterbi(self._h, model._h, *[_p(a) for a in out]))
+        return out
+
+    def set_pair_viterbi_slice(self, groups: int):
+        """Groups fsmc_decode_pair_viterbi puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_viterbi_slice(self._h, groups))
+
+    def last_pair_viterbi_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_viterbi_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):

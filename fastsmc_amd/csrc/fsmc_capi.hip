@@ -65,7 +65,16 @@ struct DevBuf {
 
 // The entry points that send the work list through the device in slices of groups (planSlices): each has its own
 // slice setting and its own count of the last call's slices.
-enum PairSlicing { kSlicePosteriors, kSliceMinima, kSliceBins, kSliceCdf, kSliceTail, kSliceLoglik, kPairSlicings };
+enum PairSlicing {
+  kSlicePosteriors,
+  kSliceMinima,
+  kSliceBins,
+  kSliceCdf,
+  kSliceTail,
+  kSliceLoglik,
+  kSliceViterbi,
+  kPairSlicings
+};
 } // namespace
 
 struct fsmc_ctx {
@@ -150,6 +159,7 @@ struct fsmc_ctx {
   DevBuf pbAcc;             // bins: [expCoal KP floats][edges, B + 1][a slice's outputs, up to 5 x pairs x B]
   DevBuf pcSpec;            // cdf, tail summaries: the call's outputs, PairCdfSpec each
   DevBuf plAcc;             // log-likelihoods: a slice's [mant][bin mant][expo][bin expo], then the edges, B + 1
+  DevBuf pvAcc;             // Viterbi paths: a slice's [mant][expo]; its state rows, [pair][S] bytes, are in ppRows
   DevBuf ptAcc;             // tail summaries: [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
@@ -547,6 +557,32 @@ ForwardFn forwardFn(const KernelChoice& k)
   return reinterpret_cast<ForwardFn>(k.fn);
 }
 
+// The Viterbi kernel of a model (fsmc_pair_viterbi.h): every lane-per-pair member, array mode; carried like the forward
+// kernel.  nullptr beyond 128 states.
+using ViterbiFn = void (*)(const VitParams);
+KernelChoice chooseViterbiKernel(const fsmc_model* m)
+{
+  KernelChoice k{nullptr, kWave, m->K <= 128 ? familyMember(m) : 0, 1};
+  ViterbiFn fn = nullptr;
+  switch (k.member) {
+#define FSMC_PICK_VITERBI(KTX)                                                                                          \
+  case KTX:                                                                                                            \
+    fn = viterbi_kernel<KTX>;                                                                                          \
+    break;
+    FSMC_ALL_KT(FSMC_PICK_VITERBI)
+    FSMC_EXACT_KT(FSMC_PICK_VITERBI)
+#undef FSMC_PICK_VITERBI
+  default:
+    break;
+  }
+  k.fn = reinterpret_cast<KernelFn>(fn);
+  return k;
+}
+ViterbiFn viterbiFn(const KernelChoice& k)
+{
+  return reinterpret_cast<ViterbiFn>(k.fn);
+}
+
 // A diagnostic switch that lowers a count: NAME=<n> gives n / divisor where that is at least 1 and below `value`.
 size_t loweredByEnv(const char* name, size_t value, int divisor = 1)
 {
@@ -785,6 +821,60 @@ int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const Kernel
   plan.k = k;
   plan.wavesPerWindow = 1;
   plan.bytes = plan.wsSlot * sizeof(float4) * slots;
+  return FSMC_OK;
+}
+
+// The launch of the Viterbi kernel (fsmc_pair_viterbi.h) over slices of at most `nGroups` whole-sequence groups.  A wave's
+// workspace is `chunk` rows of back-pointers (KT4 x 64 dwords a site) and a checkpoint (KT4 x 64 float4) a chunk; without
+// state rows (`wantStates` false) one row of back-pointers that nobody reads.  The waves: what is resident, the groups,
+// and what the hard budget holds of the smallest slot any chunk length gives (about 2 sqrt(S) sites a chunk: memory is
+// chunk + 4 x S / chunk rows).  The chunk: the caller's (fsmc_ctx_set_chunk_sites), otherwise the whole sequence -- one
+// sweep instead of two -- halved until the waves' slots fit what the context may spend (the soft budget; the hard one
+// for sequences of at most 512 sites, as planOneWave keeps short windows whole).  Computes only, like planOneWave.
+int planViterbi(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups, bool wantStates,
+                const WsBudget& budget, LaunchPlan& plan, std::string& why)
+{
+  int perCU = 0;
+  const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
+  if (e != hipSuccess) {
+    why = std::string("occupancy query of the Viterbi kernel: ") + hipGetErrorString(e);
+    return FSMC_EHIP;
+  }
+  size_t slots = std::max<size_t>(1, std::min((size_t)ctx->nCU * (size_t)std::max(perCU, 1), nGroups));
+  const size_t L = (size_t)m->S;
+  const size_t K4 = (size_t)(k.member + 3) / 4;
+  const size_t psiRow = K4 * kWave * sizeof(uint32_t), ckptRow = K4 * kWave * sizeof(float4);
+  auto slotBytes = [&](size_t c) { return c * psiRow + (L + c - 1) / c * ckptRow; };
+  size_t C = L, bytes = psiRow;
+  if (wantStates) {
+    size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(2.0 * std::sqrt((double)L))));
+    if (ctx->chunkSites) {
+      cMin = std::min<size_t>(ctx->chunkSites, L);
+    }
+    slots = std::min<size_t>(slots, (size_t)(budget.hard / slotBytes(cMin)));
+    if (slots == 0) {
+      why = "workspace limit too small for the back-pointers of one wave";
+      return FSMC_ENOMEM;
+    }
+    if (ctx->chunkSites) {
+      C = cMin;
+    } else {
+      const uint64_t room = L <= 512 ? budget.hard : budget.soft;
+      while (C > cMin && (uint64_t)slots * slotBytes(C) > room) {
+        C = std::max(cMin, (C + 1) / 2);
+      }
+    }
+    bytes = slotBytes(C);
+  }
+  plan = LaunchPlan();
+  plan.k = k;
+  plan.chunk = (int)C;
+  plan.chunkRows = (int)C;
+  plan.maxChunks = (int)((L + C - 1) / C);
+  plan.wsSlot = bytes / sizeof(float4);
+  plan.slots = (int)slots;
+  plan.wavesPerWindow = 1;
+  plan.bytes = bytes * slots;
   return FSMC_OK;
 }
 
@@ -1151,7 +1241,8 @@ int checkWholeSequence(fsmc_ctx* ctx, const fsmc_model* m, const char* what)
 }
 
 // The slices of a call and its decode plan, `mode` kModeDump or kModePerPair -- or kNoDecode: the slices alone, for an
-// entry point that launches a kernel of its own and needs no workspace (fsmc_decode_pair_loglik).  The slice is the caller's setting, or
+// entry point that launches a kernel of its own: fsmc_decode_pair_loglik, which needs no workspace, and
+// fsmc_decode_pair_viterbi, which plans its own (planViterbi).  The slice is the caller's setting, or
 // what stagingLimit holds of `groupBytes` a group, of half the room the card has free with the `held` bytes this entry
 // point's buffers hold already counted as free -- the decode's workspace is allocated after this -- and `sliceMost`
 // groups at the most.  One wave per window: planned from the first slice's groups; two waves: a workgroup for each group
@@ -1455,6 +1546,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
   if (ctx->plAcc.p) (void)hipFree(ctx->plAcc.p);
+  if (ctx->pvAcc.p) (void)hipFree(ctx->pvAcc.p);
   for (int i = 0; i < 2; ++i) {
     if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
     if (ctx->evCopied[i]) (void)hipEventDestroy(ctx->evCopied[i]);
@@ -1582,6 +1674,8 @@ int fsmc_ctx_set_pair_tail_slice(fsmc_ctx* ctx, uint32_t groups) { return setPai
 int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceTail, slices); }
 int fsmc_ctx_set_pair_loglik_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceLoglik, groups); }
 int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceLoglik, slices); }
+int fsmc_ctx_set_pair_viterbi_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceViterbi, groups); }
+int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceViterbi, slices); }
 
 int fsmc_ctx_last_kernel(const fsmc_ctx* ctx, int32_t* member)
 {
@@ -2855,6 +2949,115 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
     }
   }
   ctx->pairSlices[kSliceLoglik].last = (int)ws.nSlices;
+  return FSMC_OK;
+}
+
+// Per pair, the most probable joint state sequence and its probability (fsmc_pair_viterbi.h): one launch of
+// viterbi_kernel a slice, planned by planViterbi into the decode's workspace.  A slice's state rows, [pair][S] bytes in
+// ppRows, are one span of the caller's array: they leave through drainRows in copies that need not end with a row; the
+// mantissas and exponents by a blocking copy.  Slices are independent; a slice's rows have left before the next launch.
+int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states, double* mant, int32_t* expo)
+{
+  FSMC_TRY(checkReady(ctx, m));
+  if ((mant != nullptr) != (expo != nullptr)) {
+    return fail(ctx, FSMC_EINVAL, "a mantissa and its exponent come together");
+  }
+  if (!states && !mant) {
+    return fail(ctx, FSMC_EINVAL, "need at least one output (states, or mant and expo)");
+  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "per-pair Viterbi paths"));
+  if (m->K > 128) {
+    return fail(ctx, FSMC_EINVAL, "per-pair Viterbi paths: no Viterbi kernel for a model of more than 128 states (" +
+                                      std::to_string(m->K) + ")");
+  }
+  if (m->sequence) {
+    return fail(ctx, FSMC_EINVAL, "per-pair Viterbi paths: no Viterbi kernel for a sequence-mode model");
+  }
+  const KernelChoice k = chooseViterbiKernel(m);
+  if (!k.fn) {
+    return fail(ctx, FSMC_EUNSUPPORTED, "per-pair Viterbi paths: no kernel for this model");
+  }
+  const size_t S = (size_t)m->S;
+  const size_t pairBytes = (states ? S : 0) + (mant ? sizeof(double) + sizeof(int32_t) : 0);
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceViterbi, ctx->ppRows.bytes + ctx->pvAcc.bytes, (size_t)kWave * pairBytes,
+                      ws));
+  const size_t n = ws.slicePairsMax;
+  const size_t offExpo = n * sizeof(double);
+  if (states) {
+    FSMC_TRY(ensure(ctx, ctx->ppRows, (n * S + 3) / 4 * 4));
+  }
+  if (mant) {
+    FSMC_TRY(ensure(ctx, ctx->pvAcc, offExpo + n * sizeof(int32_t)));
+  }
+  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), n * S));
+  if (states) {
+    FSMC_TRY(ensureRowCopies(ctx, copyBytes));
+  }
+  earnWorkspace(ctx, m, kModePerPair);
+  LaunchPlan plan;
+  std::string why;
+  const int rc = planViterbi(ctx, m, k, ws.slice, states != nullptr, workspaceBudget(ctx, ctx->ws), plan, why);
+  if (rc != FSMC_OK) {
+    return fail(ctx, rc, why);
+  }
+  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+
+  char* const acc = (char*)ctx->pvAcc.p;
+  VitParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.S = m->S;
+  p.W = (int)ctx->W;
+  p.K = m->K;
+  p.chunk = plan.chunk;
+  p.nChunks = plan.maxChunks;
+  p.pi = m->pi;
+  p.cR = m->cR;
+  p.rowSets = m->rowSets;
+  p.stepRow = m->stepRow;
+  p.emis3 = m->emis3;
+  p.haps = ctx->dHaps;
+  p.pairs = ctx->dPairs;
+  p.counter = ctx->dCounters;
+  p.ws = (char*)ctx->ws.p;
+  p.slotBytes = plan.wsSlot * sizeof(float4);
+  p.states = states ? (unsigned char*)ctx->ppRows.p : nullptr;
+  p.mant = mant ? (double*)acc : nullptr;
+  p.expo = mant ? (int*)(acc + offExpo) : nullptr;
+  recordLaunch(ctx, k, plan);
+
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    const size_t nG = ws.groups(sl), first = ws.firstPair(sl), nP = ws.pairs(sl);
+    p.groups = ctx->dGroups + ws.firstGroup(sl);
+    p.nGroups = (int)nG;
+    p.pairBase = (unsigned)first;
+    FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
+    if (sl == 0) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    }
+    hipLaunchKernelGGL(viterbiFn(k), dim3((unsigned)std::min<size_t>((size_t)plan.slots, nG)), dim3(k.threads), 0,
+                       ctx->stream, p);
+    FSMC_HIP(ctx, hipGetLastError());
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every slice's launch)
+    ctx->timed = true;
+    if (states && nP > 0) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+      const size_t bytes = nP * S;
+      uint8_t* const dst = states + first * S;
+      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
+      FSMC_TRY(drainRows(
+          ctx, (bytes + copyBytes - 1) / copyBytes,
+          [&](size_t c) { return RowChunk{(const char*)ctx->ppRows.p + c * copyBytes, span(c)}; },
+          [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
+    }
+    // the slice's values go to the caller before the next slice overwrites them
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (mant) {
+      FSMC_HIP(ctx, hipMemcpy(mant + first, acc, nP * sizeof(double), hipMemcpyDeviceToHost));
+      FSMC_HIP(ctx, hipMemcpy(expo + first, acc + offExpo, nP * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+  }
+  ctx->pairSlices[kSliceViterbi].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 

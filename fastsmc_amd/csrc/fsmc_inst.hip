@@ -21,6 +21,8 @@ FSMC_KT_HALF_SUMS_KERNELS(FSMC_DEFINE_KT, FSMC_INSTANCE_KT)
 FSMC_DEFINE_KT_DUAL_HALF(FSMC_INSTANCE_KT)
 // (last: the decode kernels above keep their places in the unit, so their compiled text is what it was without these)
 FSMC_KT_FWD_KERNELS(FSMC_DEFINE_KT_FWD, FSMC_INSTANCE_KT)
+// (behind those in turn: the forward kernels keep their places too)
+FSMC_KT_VITERBI_KERNELS(FSMC_DEFINE_KT_VITERBI, FSMC_INSTANCE_KT)
 #elif defined(FSMC_INSTANCE_W2)
 #ifndef FSMC_INSTANCE_NW
 #define FSMC_INSTANCE_NW 4

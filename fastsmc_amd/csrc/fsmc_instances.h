@@ -22,6 +22,8 @@
 //   instead of registers -- correct, not fast; small enough to be instantiated where it is picked (fsmc_capi.hip).
 // Forward-only kernel (forward_kernel<KT, SEQ>, fsmc_pair_loglik.h): the per-pair likelihoods of every lane-per-pair
 //   member, array and sequence mode; the wave-group and any-K families have none.
+// Viterbi kernel (viterbi_kernel<KT>, fsmc_pair_viterbi.h): the per-pair most probable state paths of every lane-per-pair
+//   member, array mode; the wave-group and any-K families have none.
 // (The runtime-K instantiation KT = 0 and the four-lanes-per-pair kernel of earlier builds are gone: every model of at
 //  most 256 states, in every mode, runs one of the two families above.)
 #pragma once
@@ -31,6 +33,7 @@
 #include "fsmc_kernels_bidir.h"
 #include "fsmc_kernels_w2.h"
 #include "fsmc_pair_loglik.h"
+#include "fsmc_pair_viterbi.h"
 
 namespace fsmc
 {
@@ -103,6 +106,10 @@ constexpr bool halfSumsBuilt(const int KT)
 #define FSMC_KT_FWD_KERNELS(X, KT) X(KT, false) X(KT, true)
 #define FSMC_DECLARE_KT_FWD(KT, SEQ) extern template __global__ void forward_kernel<KT, SEQ>(const FwdParams);
 #define FSMC_DEFINE_KT_FWD(KT, SEQ) template __global__ void forward_kernel<KT, SEQ>(const FwdParams);
+// the max-product sweep with back-pointers and its traceback (fsmc_pair_viterbi.h): array mode
+#define FSMC_KT_VITERBI_KERNELS(X, KT) X(KT)
+#define FSMC_DECLARE_KT_VITERBI(KT) extern template __global__ void viterbi_kernel<KT>(const VitParams);
+#define FSMC_DEFINE_KT_VITERBI(KT) template __global__ void viterbi_kernel<KT>(const VitParams);
 // NW waves per group of KH states each, lane = pair (fsmc_kernels_w2.h): 128 < K <= 512
 #define FSMC_W2_MODE_KERNELS(X, KH, NW, SEQ)                                                                           \
   X(KH, kModeIbd, true, SEQ, NW)                                                                                       \
@@ -124,13 +131,15 @@ constexpr bool halfSumsBuilt(const int KT)
 #if !defined(FSMC_INSTANCE_KT) && !defined(FSMC_INSTANCE_W2)
 #define FSMC_DECLARE_MEMBER(KT)                                                                                         \
   FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT)                                                                                  \
-  FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT) FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)
+  FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT) FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)                        \
+  FSMC_KT_VITERBI_KERNELS(FSMC_DECLARE_KT_VITERBI, KT)
 FSMC_ALL_KT(FSMC_DECLARE_MEMBER)
 #define FSMC_DECLARE_EXACT_MEMBER(KT)                                                                                   \
   static_assert(KT % 16 != 0 && KT <= 128, "an exact member is not a multiple of 16 states and has at most 128");       \
   FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT)                                                                                  \
   FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT)                                                                      \
   FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)                                                                          \
+  FSMC_KT_VITERBI_KERNELS(FSMC_DECLARE_KT_VITERBI, KT)                                                                  \
   FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, KT)                                                                             \
   FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, KT)                                                                        \
   FSMC_DECLARE_KT_DUAL_HALF(KT)                                                                                         \

@@ -586,7 +586,7 @@ template <typename Assign> void HMM::changeOutputs(Assign&& assign)
 
 void HMM::setPairOutputs(const PairOutputs& outputs)
 {
-  outputs.check(mData.sites, static_cast<long>(mDq.states));
+  outputs.check(mData.sites, static_cast<long>(mDq.states), mParams.decodingSequence);
   changeOutputs([&] { mOutputs = outputs; });
 }
 
@@ -601,6 +601,13 @@ void HMM::setStoreLogLikelihoods(bool v)
 {
   PairOutputs next = mOutputs;
   next.logLikelihoods = v;
+  setPairOutputs(next);
+}
+
+void HMM::setStoreViterbiPaths(bool v)
+{
+  PairOutputs next = mOutputs;
+  next.viterbiPaths = v;
   setPairOutputs(next);
 }
 
@@ -1005,6 +1012,9 @@ void HMM::flushPairOutputs(size_t nPairs)
   if (o.logLikelihoods) {
     flushPairLogLik(nPairs);
   }
+  if (o.viterbiPaths) {
+    flushPairViterbi(nPairs);
+  }
   if (o.cdf()) {
     flushPairCdf();
   }
@@ -1087,6 +1097,28 @@ void HMM::flushPairLogLik(size_t nPairs)
   for (size_t i = atBin; i < atBin + nPairs * nBins; ++i) {
     R.binLogLikelihoods[i] =
         std::log(R.binLikelihoodMantissas[i]) + static_cast<double>(R.binLikelihoodExponents[i]) * ln2;
+  }
+}
+
+// per pair the most probable joint state sequence and its probability, flush after flush at the pairs written so far:
+// a byte a pair-site and 12 bytes a pair cross the bus; the logarithms are formed here in fp64
+void HMM::flushPairViterbi(size_t nPairs)
+{
+  auto& R = mPairsReturn;
+  const size_t S = static_cast<size_t>(R.numSites);
+  if (R.perPairViterbiMantissas.size() != static_cast<size_t>(R.numPairs) ||
+      R.perPairViterbiStates.size() != static_cast<size_t>(R.numPairs) * S) {
+    throw std::runtime_error("the return structure was not initialised for the Viterbi paths asked for");
+  }
+  const size_t at = R.numWritten;
+  check(mCtx,
+        fsmc_decode_pair_viterbi(mCtx, mModel, R.perPairViterbiStates.data() + at * S,
+                                 R.perPairViterbiMantissas.data() + at, R.perPairViterbiExponents.data() + at),
+        "fsmc_decode_pair_viterbi");
+  const double ln2 = std::log(2.0);
+  for (size_t i = at; i < at + nPairs; ++i) {
+    R.perPairViterbiLogProbabilities[i] =
+        std::log(R.perPairViterbiMantissas[i]) + static_cast<double>(R.perPairViterbiExponents[i]) * ln2;
   }
 }
 

@@ -124,6 +124,9 @@ public:
   // per pair the likelihood of its observations (mantissa, exponent, logarithm), and per site bin where bins are set:
   // the forward sweep alone (fsmc_decode_pair_loglik)
   void setStoreLogLikelihoods(bool v);
+  // per pair the most probable joint state sequence and its probability (mantissa, exponent, logarithm): a max-product
+  // sweep and a traceback on the device (fsmc_decode_pair_viterbi); throws for more than 128 states and sequence mode
+  void setStoreViterbiPaths(bool v);
   // per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins of sites
   // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
   // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
@@ -208,6 +211,7 @@ private:
   void flushPairMinima();
   void flushPairBins();
   void flushPairLogLik(size_t nPairs);
+  void flushPairViterbi(size_t nPairs);
   void flushPairCdf();
   void flushPairTailSummaries(size_t nPairs);
   void flushPairPosteriors(size_t nPairs);

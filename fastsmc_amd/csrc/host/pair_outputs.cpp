@@ -45,7 +45,7 @@ void firstMinima(const std::vector<T>& rows, long pairs, long sites, std::vector
 }
 } // namespace
 
-void PairOutputs::check(long sites, long states) const
+void PairOutputs::check(long sites, long states, bool sequence) const
 {
   // (the messages of fsmc_decode_pair_cdf)
   checkTailCount(tailStates);
@@ -92,6 +92,13 @@ void PairOutputs::check(long sites, long states) const
     throw std::runtime_error("per-pair log-likelihoods: no forward kernel for a model of more than 128 states (" +
                              std::to_string(states) + ")");
   }
+  if (viterbiPaths && states > 128) { // (the messages of fsmc_decode_pair_viterbi)
+    throw std::runtime_error("per-pair Viterbi paths: no Viterbi kernel for a model of more than 128 states (" +
+                             std::to_string(states) + ")");
+  }
+  if (viterbiPaths && sequence) {
+    throw std::runtime_error("per-pair Viterbi paths: no Viterbi kernel for a sequence-mode model");
+  }
 }
 
 void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs)
@@ -134,6 +141,11 @@ void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states,
   binLikelihoodMantissas.assign(o.logLikelihoods ? cells : 0, 0.0);
   binLikelihoodExponents.assign(o.logLikelihoods ? cells : 0, 0);
   binLogLikelihoods.assign(o.logLikelihoods ? cells : 0, 0.0);
+  // the Viterbi paths: [pairs][sites] and [pairs]
+  perPairViterbiStates.assign(o.viterbiPaths ? nPairs * S : 0, 0);
+  perPairViterbiMantissas.assign(o.viterbiPaths ? nPairs : 0, 0.0);
+  perPairViterbiExponents.assign(o.viterbiPaths ? nPairs : 0, 0);
+  perPairViterbiLogProbabilities.assign(o.viterbiPaths ? nPairs : 0, 0.0);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()

@@ -36,12 +36,15 @@ struct PairOutputs {
   // per pair, the likelihood of its observations as mantissa, exponent and logarithm, from the forward sweep alone
   // (fsmc_decode_pair_loglik); with siteBins also per bin, started afresh at the bin's first site
   bool logLikelihoods = false;
+  // per pair, the most probable joint state sequence (the Viterbi path) and its probability as mantissa, exponent and
+  // logarithm (fsmc_decode_pair_viterbi): models of at most 128 states, array mode
+  bool viterbiPaths = false;
 
   // Throws what the ABI would refuse, with its messages: more than 8 tail states or quantiles, a cut outside [1, states],
   // a quantile outside (0, 1]; then the same for the tail summaries, and weights without cuts, not one a site or not
   // finite; then fewer than two bin edges, edges outside [0, sites] or not strictly ascending; then log-likelihoods of a
-  // model of more than 128 states.
-  void check(long sites, long states) const;
+  // model of more than 128 states; then Viterbi paths of a model of more than 128 states or of a sequence-mode model.
+  void check(long sites, long states, bool sequence = false) const;
 
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
   bool minMeansOnDevice() const { return minMeans && !means; }
@@ -51,7 +54,7 @@ struct PairOutputs {
   bool any() const
   {
     return means || maps || posteriors || sumOfPosteriors || minMeansOnDevice() || minMapsOnDevice() ||
-           !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods;
+           !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods || viterbiPaths;
   }
 };
 
@@ -84,6 +87,11 @@ struct DecodePairsReturnStruct {
   std::vector<int> perPairLikelihoodExponents;
   std::vector<double> binLikelihoodMantissas, binLogLikelihoods;
   std::vector<int> binLikelihoodExponents;
+  // the most probable joint state sequence of each pair, [pairs][sites], and its probability P(path, observations) =
+  // mantissa * 2^exponent with its logarithm in fp64, [pairs]
+  std::vector<unsigned char> perPairViterbiStates;
+  std::vector<double> perPairViterbiMantissas, perPairViterbiLogProbabilities;
+  std::vector<int> perPairViterbiExponents;
   size_t numWritten = 0;
 
   void initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs);

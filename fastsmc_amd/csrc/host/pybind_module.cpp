@@ -101,10 +101,12 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       "decodePairs",
       [](ASMC& self, const std::vector<Id>& a, const std::vector<Id>& b, bool perPairPosteriors, bool sumOfPosteriors,
          bool perPairPosteriorMeans, bool perPairMAPs, bool minPosteriorMeans, bool minMAPs, bool logLikelihoods,
+         bool viterbiPaths,
          const std::vector<int>& siteBins, const std::vector<float>& tailTimes, const std::vector<float>& quantiles,
          const std::vector<float>& tailSummaryTimes, const std::vector<float>& siteWeights) {
         PairOutputs o;
         o.logLikelihoods = logLikelihoods;
+        o.viterbiPaths = viterbiPaths;
         o.posteriors = perPairPosteriors;
         o.sumOfPosteriors = sumOfPosteriors;
         o.means = perPairPosteriorMeans;
@@ -120,7 +122,7 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       },
       py::arg(listA), py::arg(listB), "per_pair_posteriors"_a = false, "sum_of_posteriors"_a = false,
       "per_pair_posterior_means"_a = false, "per_pair_MAPs"_a = false, "min_posterior_means"_a = false,
-      "min_MAPs"_a = false, "log_likelihoods"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
+      "min_MAPs"_a = false, "log_likelihoods"_a = false, "viterbi_paths"_a = false, "site_bins"_a = std::vector<int>{}, "tail_times"_a = std::vector<float>{},
       "quantiles"_a = std::vector<float>{}, "tail_summary_times"_a = std::vector<float>{},
       "site_weights"_a = std::vector<float>{},
       "Decode the listed pairs into the return structure.  site_bins: edges e[0] < ... < e[B] within [0, sites]; per "
@@ -147,7 +149,12 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       "[0.5, 1), or 0 / inf / NaN) and per_pair_likelihood_exponents ([pairs] int32); per_pair_log_likelihoods ([pairs] "
       "float64) is log(mantissa) + exponent * ln 2.  With site_bins also per_pair_bin_log_likelihoods, "
       "per_pair_bin_likelihood_mantissas, per_pair_bin_likelihood_exponents ([pairs][B]): the likelihood of the bin's "
-      "observations given everything before it -- a bin a pair fits badly stands out.");
+      "observations given everything before it -- a bin a pair fits badly stands out.  viterbi_paths: per pair the "
+      "single most probable JOINT state sequence (models of at most 128 states, array mode) as "
+      "per_pair_viterbi_states ([pairs][sites] uint8; per_pair_MAPs is the per-site argmax of the marginals instead) and "
+      "the probability of (path, observations), bit-reproducible as per_pair_viterbi_mantissas ([pairs] float64) and "
+      "per_pair_viterbi_exponents ([pairs] int32); per_pair_viterbi_log_probabilities ([pairs] float64) is log(mantissa) "
+      "+ exponent * ln 2.  api.state_runs gives the run-length form of a row.");
 }
 
 } // namespace
@@ -222,7 +229,13 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("per_pair_likelihood_exponents", [](const Pairs& r) { return shaped(r.perPairLikelihoodExponents, r.perPairLikelihoodExponents.size()); })
       .def_property_readonly("per_pair_bin_log_likelihoods", [](const Pairs& r) { return shaped(r.binLogLikelihoods, r.numPairs, numBins(r)); })
       .def_property_readonly("per_pair_bin_likelihood_mantissas", [](const Pairs& r) { return shaped(r.binLikelihoodMantissas, r.numPairs, numBins(r)); })
-      .def_property_readonly("per_pair_bin_likelihood_exponents", [](const Pairs& r) { return shaped(r.binLikelihoodExponents, r.numPairs, numBins(r)); });
+      .def_property_readonly("per_pair_bin_likelihood_exponents", [](const Pairs& r) { return shaped(r.binLikelihoodExponents, r.numPairs, numBins(r)); })
+      // the most probable joint state sequence of each pair, [pairs][sites], and the probability of (path,
+      // observations) as mantissa * 2^exponent with its natural logarithm, [pairs]; empty where not asked for
+      .def_property_readonly("per_pair_viterbi_states", [](const Pairs& r) { return shaped(r.perPairViterbiStates, r.numPairs, r.numSites); })
+      .def_property_readonly("per_pair_viterbi_log_probabilities", [](const Pairs& r) { return shaped(r.perPairViterbiLogProbabilities, r.perPairViterbiLogProbabilities.size()); })
+      .def_property_readonly("per_pair_viterbi_mantissas", [](const Pairs& r) { return shaped(r.perPairViterbiMantissas, r.perPairViterbiMantissas.size()); })
+      .def_property_readonly("per_pair_viterbi_exponents", [](const Pairs& r) { return shaped(r.perPairViterbiExponents, r.perPairViterbiExponents.size()); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -483,6 +496,9 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setStoreLogLikelihoods", &HMM::setStoreLogLikelihoods, "storeLogLikelihoods"_a = true,
            "per pair the likelihood of its observations (mantissa, exponent, logarithm), per site bin where bins are "
            "set: the forward sweep alone, computed on the device")
+      .def("setStoreViterbiPaths", &HMM::setStoreViterbiPaths, "storeViterbiPaths"_a = true,
+           "per pair the most probable joint state sequence and its probability (mantissa, exponent, logarithm): a "
+           "max-product sweep and a traceback on the device; models of at most 128 states, array mode")
       .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
            "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
            "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")

@@ -32,6 +32,8 @@
  *   fsmc_decode_pair_loglik <- the forward half of decodeBatch, its per-site scaling sums kept (HMM.cpp:725-784); the
  *                             product of the sums, the pair's data likelihood, has no counterpart: the reference
  *                             uses every sum for 1.0f / sum and drops it
+ *   fsmc_decode_pair_viterbi <- none: the reference decodes marginals only.  The forward step of decodeBatch
+ *                             (HMM.cpp:787-830) with max in place of +, back-pointers and a traceback
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -228,6 +230,11 @@ int fsmc_ctx_last_pair_tail_slices(const fsmc_ctx* ctx, int32_t* slices);
  * whole work list.  Results do not depend on it. */
 int fsmc_ctx_set_pair_loglik_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_viterbi.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of outputs (64 * (S + 12) bytes a group).  Results do not depend on
+ * it. */
+int fsmc_ctx_set_pair_viterbi_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -412,6 +419,48 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
  * and any-K kernels have no forward-only member). */
 int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* bin_edges, size_t n_bins, double* mant,
                             int32_t* expo, double* bin_mant, int32_t* bin_expo);
+
+/* Per pair of the resident work list, the single most probable JOINT state sequence of the pair under the model (the
+ * Viterbi path) and its probability, from a max-product forward sweep with back-pointers and a traceback
+ * (fsmc_pair_viterbi.h; lane-per-pair kernels: K <= 128, array mode, whole-sequence groups).  The map of
+ * fsmc_decode_per_pair is the per-site argmax of the marginals; this is the argmax over whole paths.  The transition is
+ * semiseparable with non-negative entries, so max distributes over the forward step's recurrences as + does.  The
+ * contract; every operation is one separately rounded IEEE fp32 operation, every comparison exactly the one written:
+ *     site 0:   v[k] = pi[k] * em0[k]
+ *     site t >= 1, from the scaled vector p of site t-1, table row step_row[t]:
+ *       suffix maximum, k descending:  mC[K-1] = p[K-1], cI[K-1] = K-1;
+ *           for k = K-2 .. 0:  if (p[k] >= mC[k+1]) (mC[k], cI[k]) = (p[k], k) else = (mC[k+1], cI[k+1])
+ *       MU = 0.f, uI = 0
+ *       for k = 0 .. K-1 ascending:
+ *           d = D[k] * p[k]
+ *           if k >= 1:  cand = U[k-1] * p[k-1];  car = cR[k-1] * MU
+ *                       if (car >= cand) MU = car  (uI stays)  else (MU, uI) = (cand, k-1)
+ *                       (best, arg) = (MU, uI);  if (d > best) (best, arg) = (d, k)
+ *           else        (best, arg) = (d, 0)
+ *           if k < K-1: l = B[k] * mC[k+1];  if (l > best) (best, arg) = (l, cI[k+1])
+ *           v[k] = em_t[k] * best;   psi[t][k] = arg
+ *     every site: sum[t] = ((0.f + v[0]) + v[1]) + ...  (k ascending);  delta_t = v * (1.0f / sum[t])
+ *     end:      x[S-1] = the smallest k with delta_{S-1}[k] > every earlier one (strict >, k ascending)
+ *               x[t-1] = psi[t][x[t]]   for t = S-1 .. 1
+ *     P(path, observations): m = 1.0, e = 0; for t ascending: (m, e) <- (m, e) * (double)sum[t], the recurrence of
+ *               fsmc_decode_pair_loglik; then once more with (double)delta_{S-1}[x[S-1]]
+ *   em_t is the emission row of the pair's observation class at site t.  On equal values the smaller predecessor index
+ *   wins everywhere.  Ghost states of a padded kernel member (p = 0, zero table entries) are never chosen.
+ *   states[i * S + t] = x[t] (uint8, in [0, K)); mant[i] (float64) and expo[i] (int32): the probability as in
+ *     fsmc_decode_pair_loglik, log(mant) + expo * ln 2 its logarithm; [n_pairs] in work-list order.
+ *   A pair whose mantissa is 0 or not finite (a zero scaling sum somewhere) has mantissa and exponent as defined; its
+ *     states only lie in [0, K).  The other pairs of its group are exact.
+ * states may be NULL (the probabilities alone: no second sweep, no traceback); mant / expo: both or neither; one output
+ * at least.  A wave keeps K bytes of back-pointers a pair and site in the decode's workspace; a sequence whose
+ * back-pointers do not fit is swept in chunks: a first sweep leaves a checkpoint a chunk, then chunk by chunk from the
+ * end a second sweep rebuilds the chunk's back-pointers and the traceback walks it (fsmc_ctx_set_chunk_sites and
+ * fsmc_ctx_set_workspace_limit are honoured, fsmc_ctx_last_plan and fsmc_ctx_last_kernel report; results do not depend
+ * on them).  The work list goes through the device in slices of groups (fsmc_ctx_set_pair_viterbi_slice), which are
+ * independent; the state rows leave through pinned buffers.  fsmc_last_kernel_ms spans the call's launches (with several
+ * slices also the copies in between).  FSMC_EINVAL, nothing touched: a mantissa without its exponent or the reverse; no
+ * output; a group that is not the whole sequence (from = 0, to = S); a model of more than 128 states; a sequence-mode
+ * model (its half-step doubles the trellis). */
+int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states, double* mant, int32_t* expo);
 
 /* Per pair of the resident work list and site, where the posterior mass lies, without the [K][S] tables leaving the
  * device.  post[k] is the pair's normalised fp32 posterior at the site over the model's K states (not multiplied by any

@@ -1,0 +1,258 @@
+"""Inputs and the numpy statement of fsmc_decode_pair_viterbi (per pair: the most probable joint state sequence under the
+model and its probability as mantissa and exponent) for its tests.  Nothing here calls the code under test.
+
+The statement is the contract of include/fastsmc_hip.h in float32, one numpy operation per IEEE operation and one numpy
+comparison per comparison, vectorised over the pairs (lanes are independent):
+  viterbi(pm, folded, pairs) -> (states [n][S] uint8, sums [n][S] float32, last [n] float32)
+    site 0: v = pi * em0.  Site t >= 1, from the scaled vector p of site t-1: the suffix maximum from the top with `>=`
+    (the smaller index wins a tie), MU / uI = the running maximum of U[k-1] * p[k-1] and cR[k-1] * MU with `>=` for the
+    carried value, best = MU, then d = D[k] * p[k] with `>`, then l = B[k] * mC[k+1] with `>`; v[k] = em[k] * best,
+    psi[t][k] = the index best came from.  Every site: the sum over k ascending from 0.f, delta = v * (1.0f / sum)
+    (pair_loglik_lists._sum_and_scale).  x[S-1] = the first maximum of the last delta, x[t-1] = psi[t][x[t]];
+    `last` = delta[S-1][x[S-1]].
+  expected(sums, last) -> (mant [n] float64, expo [n] int32): pair_loglik_lists.chain over the sums, then once more with
+    `last`.
+The emission rows are pair_loglik_lists.forward's: (e1 + e0m1 * z) + e2m0 * t.
+
+The yardstick is a textbook Viterbi in float64 on the dense transition matrices of tests/dense_reference.py
+(dense_viterbi), and the joint log-probability of any path on the same matrices (dense_path_log_probability)."""
+import numpy as np
+
+from fastsmc_amd import synth
+from oracle import oracle as O
+from pair_loglik_lists import (ALL_PAIRS, CASES as LL_CASES, PAIR_COUNTS, _pair_bits, _problem, _sum_and_scale,  # noqa: F401
+                               case as ll_case, chain, cohort_problem, zero_sum_problem)
+from pair_common import cohort_pairs
+
+F32 = np.float32
+
+
+def _next_delta(pm, row, prev, em):
+    """One max-product step: prev, em [n][K] float32 -> (v [n][K] float32, psi [n][K] uint8)."""
+    K = pm.K
+    D, B, U, cR = pm.D[row], pm.B[row], pm.U[row], pm.col_ratios
+    n = prev.shape[0]
+    mC = np.empty_like(prev)
+    cI = np.empty((n, K), np.int32)
+    mC[:, K - 1] = prev[:, K - 1]
+    cI[:, K - 1] = K - 1
+    for k in range(K - 2, -1, -1):
+        ge = prev[:, k] >= mC[:, k + 1]
+        mC[:, k] = np.where(ge, prev[:, k], mC[:, k + 1])
+        cI[:, k] = np.where(ge, k, cI[:, k + 1])
+    v = np.empty_like(prev)
+    psi = np.empty((n, K), np.uint8)
+    MU = np.zeros(n, F32)
+    uI = np.zeros(n, np.int32)
+    for k in range(K):
+        d = D[k] * prev[:, k]
+        if k >= 1:
+            cand = U[k - 1] * prev[:, k - 1]
+            car = cR[k - 1] * MU
+            ge = car >= cand
+            MU = np.where(ge, car, cand)
+            uI = np.where(ge, uI, k - 1)
+            gd = d > MU
+            best = np.where(gd, d, MU)
+            arg = np.where(gd, k, uI)
+        else:
+            best = d
+            arg = np.zeros(n, np.int32)
+        if k < K - 1:
+            l = B[k] * mC[:, k + 1]
+            gl = l > best
+            best = np.where(gl, l, best)
+            arg = np.where(gl, cI[:, k + 1], arg)
+        assert best.dtype == F32 and MU.dtype == F32
+        v[:, k] = em[:, k] * best
+        psi[:, k] = arg
+    return v, psi
+
+
+def viterbi(pm, folded, pairs):
+    """(states [n][S] uint8, sums [n][S] float32, last [n] float32) of `pairs` over the whole sequence, array mode."""
+    assert not pm.sequence and pm.K <= 128
+    ob, hb = _pair_bits(folded, pairs)
+    n, S, K = len(pairs), pm.S, pm.K
+    z = np.where(ob != 0, F32(0.0), F32(1.0)).astype(F32)  # isZero
+    t = np.where(hb != 0, F32(1.0), F32(0.0)).astype(F32)  # isTwo
+
+    def emission(pos):
+        return (pm.e1[pos][None, :] + pm.e0m1[pos][None, :] * z[:, pos, None]) + pm.e2m0[pos][None, :] * t[:, pos, None]
+
+    sums = np.empty((n, S), F32)
+    psi = np.zeros((S, n, K), np.uint8)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        sums[:, 0], delta = _sum_and_scale(pm.pi[None, :] * emission(0))
+        for pos in range(1, S):
+            v, psi[pos] = _next_delta(pm, int(pm.step_row[pos]), delta, emission(pos))
+            sums[:, pos], delta = _sum_and_scale(v)
+        best = delta[:, 0].copy()
+        x = np.zeros(n, np.int64)
+        for k in range(1, K):
+            gt = delta[:, k] > best
+            best = np.where(gt, delta[:, k], best)
+            x = np.where(gt, k, x)
+    assert best.dtype == F32
+    states = np.empty((n, S), np.uint8)
+    rows = np.arange(n)
+    for pos in range(S - 1, -1, -1):
+        states[:, pos] = x
+        if pos:
+            x = psi[pos][rows, x].astype(np.int64)
+    return states, sums, best
+
+
+def expected(sums, last):
+    """(mant float64 [n], expo int32 [n]): the chain over the sums and then `last`."""
+    return chain(np.concatenate([sums, last[:, None]], axis=1).astype(F32), 0, sums.shape[1] + 1)
+
+
+def log_probability(mant, expo):
+    with np.errstate(divide="ignore"):
+        return np.log(mant) + expo.astype(np.float64) * np.log(2.0)
+
+
+def state_runs(row):
+    """(starts, ends, states) of the runs of one row: the statement of fastsmc_amd.api.state_runs."""
+    row = np.asarray(row)
+    cut = np.flatnonzero(row[1:] != row[:-1]) + 1
+    starts = np.concatenate([[0], cut])
+    ends = np.concatenate([cut, [row.size]])
+    return starts, ends, row[starts]
+
+
+# ---------------------------------------------------------------- the fp64 yardstick
+
+def _dense(pm, folded, pair):
+    import dense_reference as DR
+
+    x = folded[pair[0]] ^ folded[pair[1]]
+    t = folded[pair[0]] & folded[pair[1]]
+    Ts = {}
+
+    def T(pos):
+        row = int(pm.step_row[pos])
+        return Ts.setdefault(row, DR.dense_T(pm, row))
+
+    def em(pos):
+        return DR.emission(pm, pos, x[pos], t[pos])
+
+    return T, em
+
+
+def dense_viterbi(pm, folded, pair):
+    """(path [S], log P(path, observations)) by a textbook Viterbi in float64 on the dense matrices: delta'[k] = em[k] *
+    max_i delta[i] * T[i][k] (the first maximum), renormalised at every site."""
+    T, em = _dense(pm, folded, pair)
+    S, K = pm.S, pm.K
+    d = pm.pi.astype(np.float64) * em(0)
+    lp = np.log(d.sum())
+    d = d / d.sum()
+    psi = np.zeros((S, K), np.int64)
+    for pos in range(1, S):
+        cand = d[:, None] * T(pos)  # [from][to]
+        psi[pos] = np.argmax(cand, axis=0)
+        d = em(pos) * cand.max(axis=0)
+        lp += np.log(d.sum())
+        d = d / d.sum()
+    x = int(np.argmax(d))
+    lp += np.log(d[x])
+    path = np.empty(S, np.int64)
+    for pos in range(S - 1, -1, -1):
+        path[pos] = x
+        if pos:
+            x = int(psi[pos][x])
+    return path, lp
+
+
+def dense_path_log_probability(pm, folded, pair, path):
+    """log P(path, observations of the pair) in float64 on the dense matrices."""
+    T, em = _dense(pm, folded, pair)
+    with np.errstate(divide="ignore"):
+        lp = np.log(pm.pi.astype(np.float64)[path[0]]) + np.log(em(0)[path[0]])
+        for pos in range(1, pm.S):
+            lp += np.log(T(pos)[path[pos - 1], path[pos]]) + np.log(em(pos)[path[pos]])
+    return lp
+
+
+# ---------------------------------------------------------------- the inputs
+
+def _rich_problem(K, S):
+    """A map dense in recombination (1000 cM / Mb): paths that move, up and down, every few dozen sites."""
+    n_hap = 64
+    tables = synth.make_model_tables(K)
+    haps = synth.make_haps(n_hap, S, seed=23, cm_per_mb=1000.0, switch_per_cm=0.6)
+    bits, derived, flipped = synth.fold_and_pack(haps.alleles)
+    folded = np.where(flipped[None, :], 1 - haps.alleles, haps.alleles).astype(np.uint8)
+    gen = (haps.cm / 100.0).astype(np.float32)
+    pm = O.prepare_model(tables, gen, haps.bp, derived, n_hap, time=200)
+    return pm, bits, folded
+
+
+# the array-mode cases of pair_loglik_lists (models K = 2 ... 128 at 129 sites; 1 ... 200 sites at K = 69; 200 pairs at
+# 65 sites) and the two rich ones: name -> (K, S, pairs)
+CASES = {name: (K, S, n) for name, (K, S, n, seq, _) in LL_CASES.items() if not seq}
+CASES["rich"] = (69, 700, 70)
+CASES["dense40"] = (40, 300, 70)
+RICH = ("rich", "dense40")
+CHUNKS_RICH = (16, 64, 150, 700, 0)  # chunk lengths of the GPU test on the rich case: 150 does not divide 700, 0 = automatic
+
+LIMITS_RICH = (1 << 20, 600 << 10)  # workspace limits of the GPU test on the rich case (two groups: two waves wanted)
+
+
+def planned(S, member, waves_wanted, limit):
+    """(chunk sites, chunks, waves) of fsmc_decode_pair_viterbi under a workspace limit, as its planner states them: a
+    wave's slot is chunk rows of back-pointers (ceil(member / 4) x 256 bytes a site) and a checkpoint (x 1024 bytes) a
+    chunk; the waves are what the limit holds of the smallest slot (about 2 sqrt(S) sites a chunk); the chunk is the whole
+    sequence halved (rounding up, never below that smallest chunk) until the waves' slots fit the limit."""
+    k4 = (member + 3) // 4
+
+    def slot(c):
+        return c * k4 * 256 + -(-S // c) * k4 * 1024
+
+    c_min = min(S, max(1, int(np.ceil(2.0 * np.sqrt(S)))))
+    waves = min(waves_wanted, limit // slot(c_min))
+    assert waves >= 1
+    c = S
+    while c > c_min and waves * slot(c) > limit:
+        c = max(c_min, (c + 1) // 2)
+    return c, -(-S // c), waves
+
+
+_cache = {}
+
+
+def case(name):
+    """(pm, bits, folded, pairs, states, sums, last) of a case; the restatement runs once a process and is read-only."""
+    if name not in _cache:
+        K, S, n = CASES[name]
+        if name in RICH:
+            pm, bits, folded = _rich_problem(K, S)
+            pairs = ALL_PAIRS[37:37 + n]
+        else:
+            pm, bits, folded, pairs, _, _ = ll_case(name)
+        out = viterbi(pm, folded, pairs)
+        for a in out:
+            a.setflags(write=False)
+        _cache[name] = (pm, bits, folded, pairs) + out
+    return _cache[name]
+
+
+def cohort_viterbi():
+    """viterbi() of pair_common.cohort_pairs() on the 700-site cohort, once a process."""
+    if "cohort" not in _cache:
+        pm, _, folded, _ = cohort_problem()
+        out = viterbi(pm, folded, cohort_pairs()[0])
+        for a in out:
+            a.setflags(write=False)
+        _cache["cohort"] = out
+    return _cache["cohort"]
+
+
+def zero_sum_viterbi():
+    """(pm, bits, folded, pairs, states, sums, last) of pair_loglik_lists.zero_sum_problem()."""
+    if "zero" not in _cache:
+        pm, bits, folded, pairs, _, _ = zero_sum_problem()
+        _cache["zero"] = (pm, bits, folded, pairs) + viterbi(pm, folded, pairs)
+    return _cache["zero"]

@@ -1,0 +1,163 @@
+"""What tests/pair_viterbi_lists.py claims, shown on the CPU: the paths of its float32 restatement of the contract are
+those of a textbook fp64 Viterbi on the dense transition matrices (or as probable, to rounding), the reported
+log-probabilities are the dense ones to fp32 rounding, and the inputs reach the regimes the GPU tests are there for."""
+import numpy as np
+import pytest
+
+import pair_loglik_lists as LL
+import pair_viterbi_lists as VL
+
+# Over the sampled pairs of every case, measured on the CPU (both relative to the dense optimum's log-probability):
+#   the fp64 joint log-probability of the restatement's path against the dense Viterbi optimum: at most 1.97e-15 (the
+#     rich case; every one of the 242 sampled paths is the dense one, what is left is the order of the fp64 additions)
+#   the reported log-probability, log(mant) + expo ln 2, against the dense optimum: at most 4.19e-8 (the 20-state case;
+#     1.1e-8 on S200, 4.4e-9 on the rich case): fp32 rounding of the sums, relative to log-probabilities of -0.7 ... -330
+# Nothing derives a tighter bound, so four times the measured values are allowed.
+MEASURED_PATH_DIFFERENCE = 1.97e-15
+MEASURED_REPORTED_DIFFERENCE = 4.19e-8
+PATH_BOUND = 4 * MEASURED_PATH_DIFFERENCE
+REPORTED_BOUND = 4 * MEASURED_REPORTED_DIFFERENCE
+
+
+def _sample(name):
+    """The pairs of a case that are compared with the dense Viterbi (a dense run costs K^2 a site)."""
+    n, S = VL.CASES[name][2], VL.CASES[name][1]
+    return range(0, n, 7 if S >= 300 else 5 if VL.CASES[name][0] < 100 else 10)
+
+
+_compared = {}
+
+
+def _compare(name):
+    """(sampled, paths that differ, worst relative difference of the path's log-probability, of the reported one), once."""
+    if name not in _compared:
+        pm, _, folded, pairs, states, sums, last = VL.case(name)
+        lp = VL.log_probability(*VL.expected(sums, last))
+        worst_path = worst_reported = 0.0
+        differ = 0
+        for i in _sample(name):
+            path, dense_lp = VL.dense_viterbi(pm, folded, pairs[i])
+            own = VL.dense_path_log_probability(pm, folded, pairs[i], states[i].astype(np.int64))
+            differ += not np.array_equal(path, states[i])
+            worst_path = max(worst_path, abs(own - dense_lp) / abs(dense_lp))
+            worst_reported = max(worst_reported, abs(lp[i] - dense_lp) / abs(dense_lp))
+        _compared[name] = (len(_sample(name)), differ, worst_path, worst_reported)
+    return _compared[name]
+
+
+@pytest.mark.parametrize("name", list(VL.CASES))
+def test_paths_and_probabilities_against_the_dense_viterbi(name):
+    pm, _, _, pairs, states, sums, last = VL.case(name)
+    assert states.dtype == np.uint8 and states.shape == (len(pairs), pm.S) and (states < pm.K).all()
+    mant, _ = VL.expected(sums, last)
+    assert ((mant >= 0.5) & (mant < 1)).all()
+    n, differ, worst_path, worst_reported = _compare(name)
+    print(f"{name}: {n} sampled, {differ} paths differ from the dense one; relative difference of the path's "
+          f"log-probability {worst_path:.3e}, of the reported one {worst_reported:.3e}")
+    assert worst_path <= PATH_BOUND, (name, worst_path)
+    assert worst_reported <= REPORTED_BOUND, (name, worst_reported)
+
+
+def test_at_most_five_per_cent_of_sampled_paths_differ():
+    """Near-ties may resolve differently in fp32 and fp64; over all cases together."""
+    done = [_compare(name) for name in VL.CASES]
+    sampled, differ = sum(d[0] for d in done), sum(d[1] for d in done)
+    print(f"{differ} of {sampled} sampled paths differ from the dense Viterbi's")
+    assert differ <= 0.05 * sampled, (differ, sampled)
+
+
+def test_on_the_cohort():
+    pm, _, folded, _ = VL.cohort_problem()
+    pairs = VL.cohort_pairs()[0]
+    states, sums, last = VL.cohort_viterbi()
+    assert states.shape == (200, 700)
+    assert np.array_equal(sums > 0, np.ones_like(sums, bool))
+    lp = VL.log_probability(*VL.expected(sums, last))
+    for i in range(0, 200, 40):
+        path, dense_lp = VL.dense_viterbi(pm, folded, pairs[i])
+        own = VL.dense_path_log_probability(pm, folded, pairs[i], states[i].astype(np.int64))
+        assert abs(own - dense_lp) <= PATH_BOUND * abs(dense_lp) and abs(lp[i] - dense_lp) <= REPORTED_BOUND * abs(dense_lp)
+    # below the data likelihood: one path against the sum over all of them
+    ll = LL.log_likelihood(*LL.expected(LL.cohort_sums())[:2])
+    assert (lp <= ll).all()
+
+
+def _predecessor_kinds(states):
+    """On final paths, at states k >= 1: came from below (i < k), stayed (i = k), came from above (i > k)."""
+    prev, cur = states[:, :-1].astype(int), states[:, 1:].astype(int)
+    at = cur >= 1
+    return int(((prev < cur) & at).sum()), int(((prev == cur) & at).sum()), int(((prev > cur) & at).sum())
+
+
+@pytest.mark.parametrize("name", VL.RICH)
+def test_rich_cases_move(name):
+    """A kernel whose back-pointer was always `stay` passes where paths never move: here they do."""
+    _, _, _, pairs, states, _, _ = VL.case(name)
+    runs = np.array([len(VL.state_runs(r)[0]) for r in states])
+    move = np.diff(states.astype(int), axis=1)
+    up, down = int((move > 0).sum()), int((move < 0).sum())
+    below, stay, above = _predecessor_kinds(states)
+    print(f"{name}: runs a pair min {runs.min()} median {np.median(runs)} max {runs.max()}, {int((runs >= 4).sum())} of "
+          f"{len(pairs)} pairs with >= 4 runs, {up} upward and {down} downward moves; predecessors at k >= 1: {below} "
+          f"below, {stay} equal, {above} above")
+    assert (runs >= 4).sum() * 2 >= len(pairs)
+    assert up > 0 and down > 0
+    assert below > 0 and stay > 0 and above > 0
+
+
+def test_rich_case_moves_across_chunk_boundaries():
+    """For every chunk length the GPU test runs the rich case with -- the ones it sets and the ones the planner picks
+    under its workspace limits -- some pair changes state from the last site of a chunk to the first of the next (the
+    traceback's hand-over between chunks), and some pair across a multiple of 64 (a new word of haplotype bits, a new
+    register of table rows)."""
+    _, _, _, _, states, _, _ = VL.case("rich")
+    S = states.shape[1]
+    changes = states[:, 1:] != states[:, :-1]  # [pair][t - 1]: between site t - 1 and t
+    planned = [VL.planned(S, 69, 2, limit) for limit in VL.LIMITS_RICH]
+    assert planned == [(53, 14, 2), (88, 8, 1)], planned  # (what the GPU test asserts of fsmc_ctx_last_plan)
+    for C in VL.CHUNKS_RICH + tuple(c for c, _, _ in planned):
+        if C in (0, S):
+            continue
+        at = np.arange(C, S, C)
+        assert changes[:, at - 1].any(), C
+    assert changes[:, np.arange(64, S, 64) - 1].any()
+    assert any(C and S % C for C in VL.CHUNKS_RICH) and S in VL.CHUNKS_RICH and 0 in VL.CHUNKS_RICH
+
+
+def test_small_models_move_too():
+    for name, lo in (("K2", 1), ("K3", 2)):
+        _, _, _, _, states, _, _ = VL.case(name)
+        runs = np.array([len(VL.state_runs(r)[0]) for r in states])
+        print(f"{name}: {runs.min()} - {runs.max()} runs a pair")
+        assert runs.max() >= 4 and runs.min() >= lo
+
+
+def test_zero_sum_problem():
+    """The affected pairs have mantissa 0 / NaN, the others are finite, and every state lies in [0, K)."""
+    pm, _, _, pairs, states, sums, last = VL.zero_sum_viterbi()
+    mant, expo = VL.expected(sums, last)
+    bad = (mant == 0) | ~np.isfinite(mant)
+    hit = (sums == 0).any(axis=1)
+    assert np.array_equal(bad, hit) and 2 <= bad.sum() <= len(pairs) - 2
+    assert ((mant[~bad] >= 0.5) & (mant[~bad] < 1)).all()
+    assert (states < pm.K).all()
+    # lanes are independent: the pairs that are not hit, decoded without the others, give the same rows
+    again = VL.viterbi(pm, VL.zero_sum_viterbi()[2], [pairs[i] for i in np.flatnonzero(~bad)])
+    assert np.array_equal(again[0], states[~bad]) and np.array_equal(again[1], sums[~bad])
+
+
+@pytest.mark.parametrize("name", list(VL.CASES))
+def test_viterbi_probability_is_at_most_the_likelihood(name):
+    pm, _, folded, pairs, _, sums, last = VL.case(name)
+    lp = VL.log_probability(*VL.expected(sums, last))
+    if name in VL.RICH:
+        fsums, _ = LL.forward(pm, folded, pairs)
+    else:
+        fsums = LL.case(name)[4]
+    ll = LL.log_likelihood(*LL.expected(fsums)[:2])
+    assert (lp <= ll).all() and (lp < ll).any()
+
+
+def test_state_runs():
+    starts, ends, states = VL.state_runs(np.array([3, 3, 5, 5, 5, 2], np.uint8))
+    assert starts.tolist() == [0, 2, 5] and ends.tolist() == [2, 5, 6] and states.tolist() == [3, 5, 2]

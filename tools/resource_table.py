@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of the HIP library as the compiler reports it (-Rpass-analysis=kernel-resource-usage): VGPRs,
 AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, LDS bytes per workgroup, waves per SIMD -- one row per
-instantiation of every family member (the forward-only kernels of fsmc_pair_loglik.h among them) and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
+instantiation of every family member (the forward-only kernels of fsmc_pair_loglik.h and the Viterbi kernels of fsmc_pair_viterbi.h among them) and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
 transposition, the per-pair minima and their combine step, the per-pair site bins, the per-pair tails and quantile states, the tail summaries), stamped with the hash of the sources they were compiled from.
-Usage: tools/resource_table.py [out.json]   (default profiles/r13_kernel_resources.json; no GPU needed)"""
+Usage: tools/resource_table.py [out.json]   (default profiles/r14_kernel_resources.json; no GPU needed)"""
 import json
 import os
 import re
@@ -46,7 +46,7 @@ def member(define, src="fsmc_inst.hip"):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r13_kernel_resources.json")
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r14_kernel_resources.json")
     # every member the build compiles (fastsmc_amd/build.py): padded and exact lane-per-pair members, wave-group members
     defs = ([f"-DFSMC_INSTANCE_KT={k}" for k in KT_MEMBERS + EXACT_MEMBERS]
             + [f"-DFSMC_INSTANCE_W2={kh} -DFSMC_INSTANCE_NW={nw}" for kh, nw in W2_MEMBERS])
@@ -60,7 +60,7 @@ def main():
     rows.sort(key=lambda r: r["kernel"])
     doc = {"lib_hash": hip_source_hash(), "flags": " ".join(HIPCC_FLAGS),
            "template_arguments": {"decode_kernel": "<KT, MODE (0 IBD, 1 dump, 2 per pair, 3 sums), TRACK, SEQ, HALF, DUAL>",
-                                  "decode_kernel_w2": "<KH, MODE, TRACK, SEQ, NW>", "forward_kernel": "<KT, SEQ>"},
+                                  "decode_kernel_w2": "<KH, MODE, TRACK, SEQ, NW>", "forward_kernel": "<KT, SEQ>", "viterbi_kernel": "<KT>"},
            "kernels": rows}
     json.dump(doc, open(out, "w"), indent=1)
     print(f"{len(rows)} kernels -> {out}")
