@@ -15,6 +15,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fsmc_identify.h"
@@ -530,57 +531,31 @@ KernelChoice chooseTwoWaveKernel(const fsmc_model* m, int mode)
   return k;
 }
 
-// The forward-only kernel of a model (fsmc_pair_loglik.h): every lane-per-pair member, array and sequence mode.  Carried
-// as a KernelChoice -- the occupancy query and the launch record take one -- with the function pointer under the decode
-// kernels' type; forwardFn gives it its own type back for the launch.  nullptr beyond 128 states.
-using ForwardFn = void (*)(const FwdParams);
-KernelChoice chooseForwardKernel(const fsmc_model* m)
+// The sweep kernel of a model (fsmc_pair_sweep.h): forward_kernel or viterbi_kernel of its lane-per-pair member, nullptr
+// beyond 128 states.  `fn` is the kernel under its own type, for the launch; `k` carries it as a KernelChoice -- the
+// occupancy query and the launch record take one -- with the pointer under the decode kernels' type.
+template <typename Params> struct SweepKernel {
+  KernelChoice k;                     // (k.fn is fn, cast: chooseSweepKernel sets the two together)
+  void (*fn)(const Params) = nullptr;
+};
+// `pick(std::integral_constant<int, KT>)` names the instantiation of member KT.
+template <typename Params, typename Pick> SweepKernel<Params> chooseSweepKernel(const fsmc_model* m, Pick pick)
 {
-  KernelChoice k{nullptr, kWave, m->K <= 128 ? familyMember(m) : 0, 1};
-  ForwardFn fn = nullptr;
-  switch (k.member) {
-#define FSMC_PICK_FWD(KTX)                                                                                              \
+  SweepKernel<Params> s;
+  s.k = KernelChoice{nullptr, kWave, m->K <= 128 ? familyMember(m) : 0, 1};
+  switch (s.k.member) {
+#define FSMC_PICK_SWEEP(KTX)                                                                                            \
   case KTX:                                                                                                            \
-    fn = m->sequence ? forward_kernel<KTX, true> : forward_kernel<KTX, false>;                                         \
+    s.fn = pick(std::integral_constant<int, KTX>{});                                                                   \
     break;
-    FSMC_ALL_KT(FSMC_PICK_FWD)
-    FSMC_EXACT_KT(FSMC_PICK_FWD)
-#undef FSMC_PICK_FWD
+    FSMC_ALL_KT(FSMC_PICK_SWEEP)
+    FSMC_EXACT_KT(FSMC_PICK_SWEEP)
+#undef FSMC_PICK_SWEEP
   default:
     break;
   }
-  k.fn = reinterpret_cast<KernelFn>(fn);
-  return k;
-}
-ForwardFn forwardFn(const KernelChoice& k)
-{
-  return reinterpret_cast<ForwardFn>(k.fn);
-}
-
-// The Viterbi kernel of a model (fsmc_pair_viterbi.h): every lane-per-pair member, array mode; carried like the forward
-// kernel.  nullptr beyond 128 states.
-using ViterbiFn = void (*)(const VitParams);
-KernelChoice chooseViterbiKernel(const fsmc_model* m)
-{
-  KernelChoice k{nullptr, kWave, m->K <= 128 ? familyMember(m) : 0, 1};
-  ViterbiFn fn = nullptr;
-  switch (k.member) {
-#define FSMC_PICK_VITERBI(KTX)                                                                                          \
-  case KTX:                                                                                                            \
-    fn = viterbi_kernel<KTX>;                                                                                          \
-    break;
-    FSMC_ALL_KT(FSMC_PICK_VITERBI)
-    FSMC_EXACT_KT(FSMC_PICK_VITERBI)
-#undef FSMC_PICK_VITERBI
-  default:
-    break;
-  }
-  k.fn = reinterpret_cast<KernelFn>(fn);
-  return k;
-}
-ViterbiFn viterbiFn(const KernelChoice& k)
-{
-  return reinterpret_cast<ViterbiFn>(k.fn);
+  s.k.fn = reinterpret_cast<KernelFn>(s.fn);
+  return s;
 }
 
 // A diagnostic switch that lowers a count: NAME=<n> gives n / divisor where that is at least 1 and below `value`.
@@ -1319,6 +1294,54 @@ int launchSlice(fsmc_ctx* ctx, const WorkSlices& ws, size_t sl, KParams& p)
   p.ppMean = ws.stageMean ? ws.stageMean - back : nullptr;
   p.ppMap = ws.stageMap ? ws.stageMap - back : nullptr;
   return launch(ctx, ws.plan.k, p, (int)std::min<size_t>((size_t)ws.plan.slots, nG), 0, sl != 0);
+}
+
+// The fields every sweep kernel's argument carries (FwdParams, VitParams: SweepParams of fsmc_pair_sweep.h, flat); the
+// slice's own are launchSweepSlice's.
+template <typename Params> void fillSweepParams(const fsmc_ctx* ctx, const fsmc_model* m, Params& p)
+{
+  p.S = m->S;
+  p.W = (int)ctx->W;
+  p.pi = m->pi;
+  p.cR = m->cR;
+  p.rowSets = m->rowSets;
+  p.stepRow = m->stepRow;
+  p.emis3 = m->emis3;
+  p.haps = ctx->dHaps;
+  p.pairs = ctx->dPairs;
+  p.counter = ctx->dCounters;
+}
+
+// The sweep of slice `sl`: min(slots, groups) workgroups pull the slice's groups from the queue.  The call's timed span
+// runs from the first slice's launch to the last one's end.
+template <typename Params>
+int launchSweepSlice(fsmc_ctx* ctx, const WorkSlices& ws, size_t sl, const SweepKernel<Params>& kern, int slots, Params& p)
+{
+  const size_t nG = ws.groups(sl);
+  p.groups = ctx->dGroups + ws.firstGroup(sl);
+  p.nGroups = (int)nG;
+  p.pairBase = (unsigned)ws.firstPair(sl);
+  FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
+  if (sl == 0) {
+    FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  }
+  hipLaunchKernelGGL(kern.fn, dim3((unsigned)std::min<size_t>((size_t)slots, nG)), dim3(kern.k.threads), 0, ctx->stream,
+                     p);
+  FSMC_HIP(ctx, hipGetLastError());
+  FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = true;
+  return FSMC_OK;
+}
+
+// A slice's per-pair values, `pairBytes` a pair from the start of `dev`, go to the caller's array at the slice's first
+// pair: a blocking copy, before the next slice overwrites them.  A null `host` is an output that was not asked for.
+int sliceToCaller(fsmc_ctx* ctx, const WorkSlices& ws, size_t sl, void* host, const void* dev, size_t pairBytes)
+{
+  if (host) {
+    FSMC_HIP(ctx, hipMemcpy((char*)host + ws.firstPair(sl) * pairBytes, dev, ws.pairs(sl) * pairBytes,
+                            hipMemcpyDeviceToHost));
+  }
+  return FSMC_OK;
 }
 
 // The pinned buffers' size, each: 128 MiB, FSMC_DIAG_ROW_COPY_BYTES=<bytes> for less -- tests: several copies a slice
@@ -2843,10 +2866,7 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
     // 552 bytes a pair-site of the decode: no second buffer, no overlap)
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 5; ++i) {
-      if (hOut[i]) {
-        FSMC_HIP(ctx, hipMemcpy((char*)hOut[i] + ws.firstPair(sl) * B * sizeof(float), dOut[i], n * B * sizeof(float),
-                                hipMemcpyDeviceToHost));
-      }
+      FSMC_TRY(sliceToCaller(ctx, ws, sl, hOut[i], dOut[i], B * sizeof(float)));
     }
   }
   ctx->pairSlices[kSliceBins].last = (int)ws.nSlices;
@@ -2873,8 +2893,10 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
     FSMC_TRY(checkBinEdges(ctx, m, bin_edges, n_bins));
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "per-pair log-likelihoods"));
-  const KernelChoice k = chooseForwardKernel(m);
-  if (!k.fn) {
+  const SweepKernel<FwdParams> kern = chooseSweepKernel<FwdParams>(m, [&](auto kt) {
+    return m->sequence ? forward_kernel<decltype(kt)::value, true> : forward_kernel<decltype(kt)::value, false>;
+  });
+  if (!kern.fn) {
     return fail(ctx, FSMC_EINVAL, "per-pair log-likelihoods: no forward kernel for a model of more than 128 states (" +
                                       std::to_string(m->K) + ")");
   }
@@ -2883,12 +2905,12 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceLoglik, ctx->plAcc.bytes, groupBytes, ws));
   int perCU = 0;
-  const hipError_t eo = workgroupsPerCU(k, 8, 1, perCU);
+  const hipError_t eo = workgroupsPerCU(kern.k, 8, 1, perCU);
   if (eo != hipSuccess) {
     return fail(ctx, FSMC_EHIP, std::string("occupancy query of the forward kernel: ") + hipGetErrorString(eo));
   }
   LaunchPlan plan;
-  plan.k = k;
+  plan.k = kern.k;
   plan.slots = (int)std::max<size_t>(1, std::min((size_t)ctx->nCU * (size_t)std::max(perCU, 1), ws.slice));
 
   // [mant][bin mant] doubles, [expo][bin expo] ints of the largest slice, then the edges
@@ -2904,49 +2926,24 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
   }
   FwdParams p;
   std::memset(&p, 0, sizeof(p));
-  p.S = m->S;
-  p.W = (int)ctx->W;
+  fillSweepParams(ctx, m, p);
   p.B = (int)B;
-  p.pi = m->pi;
-  p.cR = m->cR;
-  p.rowSets = m->rowSets;
-  p.stepRow = m->stepRow;
   p.rowGapF = m->rowGapF;
-  p.emis3 = m->emis3;
-  p.haps = ctx->dHaps;
-  p.pairs = ctx->dPairs;
-  p.counter = ctx->dCounters;
   p.edges = B ? (const int*)(acc + offEdges) : nullptr;
   p.mant = mant ? (double*)acc : nullptr;
   p.expo = mant ? (int*)(acc + offExpo) : nullptr;
   p.binMant = B ? (double*)(acc + offBinMant) : nullptr;
   p.binExpo = B ? (int*)(acc + offBinExpo) : nullptr;
-  recordLaunch(ctx, k, plan);
+  recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
-    const size_t nG = ws.groups(sl), first = ws.firstPair(sl), nP = ws.pairs(sl);
-    p.groups = ctx->dGroups + ws.firstGroup(sl);
-    p.nGroups = (int)nG;
-    p.pairBase = (unsigned)first;
-    FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
-    if (sl == 0) {
-      FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    }
-    hipLaunchKernelGGL(forwardFn(k), dim3((unsigned)std::min<size_t>((size_t)plan.slots, nG)), dim3(k.threads), 0,
-                       ctx->stream, p);
-    FSMC_HIP(ctx, hipGetLastError());
-    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every slice's launch)
-    ctx->timed = true;
+    FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     // the slice's values go to the caller before the next slice overwrites them (12 bytes a pair and output)
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (mant) {
-      FSMC_HIP(ctx, hipMemcpy(mant + first, acc, nP * sizeof(double), hipMemcpyDeviceToHost));
-      FSMC_HIP(ctx, hipMemcpy(expo + first, acc + offExpo, nP * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (B) {
-      FSMC_HIP(ctx, hipMemcpy(bin_mant + first * B, acc + offBinMant, nP * B * sizeof(double), hipMemcpyDeviceToHost));
-      FSMC_HIP(ctx, hipMemcpy(bin_expo + first * B, acc + offBinExpo, nP * B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc, sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + offExpo, sizeof(int32_t)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_mant, acc + offBinMant, B * sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_expo, acc + offBinExpo, B * sizeof(int32_t)));
   }
   ctx->pairSlices[kSliceLoglik].last = (int)ws.nSlices;
   return FSMC_OK;
@@ -2973,8 +2970,9 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
   if (m->sequence) {
     return fail(ctx, FSMC_EINVAL, "per-pair Viterbi paths: no Viterbi kernel for a sequence-mode model");
   }
-  const KernelChoice k = chooseViterbiKernel(m);
-  if (!k.fn) {
+  const SweepKernel<VitParams> kern =
+      chooseSweepKernel<VitParams>(m, [](auto kt) { return viterbi_kernel<decltype(kt)::value>; });
+  if (!kern.fn) {
     return fail(ctx, FSMC_EUNSUPPORTED, "per-pair Viterbi paths: no kernel for this model");
   }
   const size_t S = (size_t)m->S;
@@ -2997,7 +2995,7 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
   earnWorkspace(ctx, m, kModePerPair);
   LaunchPlan plan;
   std::string why;
-  const int rc = planViterbi(ctx, m, k, ws.slice, states != nullptr, workspaceBudget(ctx, ctx->ws), plan, why);
+  const int rc = planViterbi(ctx, m, kern.k, ws.slice, states != nullptr, workspaceBudget(ctx, ctx->ws), plan, why);
   if (rc != FSMC_OK) {
     return fail(ctx, rc, why);
   }
@@ -3006,40 +3004,20 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
   char* const acc = (char*)ctx->pvAcc.p;
   VitParams p;
   std::memset(&p, 0, sizeof(p));
-  p.S = m->S;
-  p.W = (int)ctx->W;
+  fillSweepParams(ctx, m, p);
   p.K = m->K;
   p.chunk = plan.chunk;
   p.nChunks = plan.maxChunks;
-  p.pi = m->pi;
-  p.cR = m->cR;
-  p.rowSets = m->rowSets;
-  p.stepRow = m->stepRow;
-  p.emis3 = m->emis3;
-  p.haps = ctx->dHaps;
-  p.pairs = ctx->dPairs;
-  p.counter = ctx->dCounters;
   p.ws = (char*)ctx->ws.p;
   p.slotBytes = plan.wsSlot * sizeof(float4);
   p.states = states ? (unsigned char*)ctx->ppRows.p : nullptr;
   p.mant = mant ? (double*)acc : nullptr;
   p.expo = mant ? (int*)(acc + offExpo) : nullptr;
-  recordLaunch(ctx, k, plan);
+  recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
-    const size_t nG = ws.groups(sl), first = ws.firstPair(sl), nP = ws.pairs(sl);
-    p.groups = ctx->dGroups + ws.firstGroup(sl);
-    p.nGroups = (int)nG;
-    p.pairBase = (unsigned)first;
-    FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
-    if (sl == 0) {
-      FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    }
-    hipLaunchKernelGGL(viterbiFn(k), dim3((unsigned)std::min<size_t>((size_t)plan.slots, nG)), dim3(k.threads), 0,
-                       ctx->stream, p);
-    FSMC_HIP(ctx, hipGetLastError());
-    FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every slice's launch)
-    ctx->timed = true;
+    const size_t first = ws.firstPair(sl), nP = ws.pairs(sl);
+    FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     if (states && nP > 0) {
       FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
       const size_t bytes = nP * S;
@@ -3052,10 +3030,8 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
     }
     // the slice's values go to the caller before the next slice overwrites them
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (mant) {
-      FSMC_HIP(ctx, hipMemcpy(mant + first, acc, nP * sizeof(double), hipMemcpyDeviceToHost));
-      FSMC_HIP(ctx, hipMemcpy(expo + first, acc + offExpo, nP * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc, sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + offExpo, sizeof(int32_t)));
   }
   ctx->pairSlices[kSliceViterbi].last = (int)ws.nSlices;
   return FSMC_OK;
@@ -3291,9 +3267,9 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
       // overlap: 8 bytes a cell at most against the 4 K bytes a pair-site of the dump)
       FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
       for (int o = 0; o < 2; ++o) {
-        for (size_t j = 0; hOut[o] && j < nT; ++j) {
-          FSMC_HIP(ctx, hipMemcpy(hOut[o] + (j * ctx->nPairs + firstPair) * B, dOut[o] + j * ws.slicePairsMax * B,
-                                  n * B * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t j = 0; hOut[o] && j < nT; ++j) { // (cut j: [pairs][B] of the caller's, [pairs of the slice][B] here)
+          FSMC_TRY(sliceToCaller(ctx, ws, sl, hOut[o] + j * ctx->nPairs * B, dOut[o] + j * ws.slicePairsMax * B,
+                                 B * sizeof(float)));
         }
       }
     }

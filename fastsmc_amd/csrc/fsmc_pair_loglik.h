@@ -22,10 +22,11 @@
 // forward_kernel<KT, SEQ>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue.
 // The arithmetic of a site is the decode's (fsmc_kernels.h): alpha_step<..., SCALE = false>, the ascending sum of what
 // it leaves (the adds of the scaled step, in its order: the compiler folds the two chains into one), scale_pk; the first
-// site is alpha_init with its sum handed back (forwardInit).  Everything around the steps is this kernel's own: the
-// observation classes from the packed haplotype words, a two-slot LDS ring of emission rows fed by LDS-DMA one site
-// ahead (three rows a site, four in sequence mode), the table rows of 64 consecutive sites in one register, the fp64
-// recurrence and the bins.  The site loop is wave-uniform, so the open bin is scalar state; a bin's two values leave
+// site is alpha_init with its sum handed back (forwardInit).  What surrounds the steps is fsmc_pair_sweep.h's, shared with
+// viterbi_kernel (fsmc_pair_viterbi.h): the group queue, the observation classes from the packed haplotype words, a
+// two-slot LDS ring of emission rows fed by LDS-DMA one site ahead (three rows a site, four in sequence mode), the table
+// rows of 64 consecutive sites in one register.  This kernel's own are the fp64 recurrence over the sums, the bins and
+// the sequence-mode half-step.  The site loop is wave-uniform, so the open bin is scalar state; a bin's two values leave
 // with ordinary vector stores when it closes.  No workspace: the kernel's HBM traffic is the emission rows (12 or 16
 // bytes a state and site for the WAVE, not the pair) and 12 bytes a pair and output.
 #pragma once
@@ -35,6 +36,7 @@
 #include <climits>
 
 #include "fsmc_kernels.h"
+#include "fsmc_pair_sweep.h"
 
 namespace fsmc
 {
@@ -68,35 +70,6 @@ struct FwdParams {
 // registers in flight); every other instantiation of the default build is clean.
 template <int KT, bool SEQ> constexpr bool kFwdSyncLoads = KT == 32;
 
-// alpha at the first site, NOT yet scaled, and its sum: the operations of alpha_init up to its 1.0f / sum
-// (HMM.cpp:736-747), k ascending from 0.f.
-template <int KT, int KA> __device__ __forceinline__ float forwardInit(float (&a)[KA], cfloat_p pi, const float4* e)
-{
-  float sum = 0.f;
-  float4 ev = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < KT; ++k) {
-    if ((k & 3) == 0) {
-      ev = e[k >> 2];
-    }
-    const float em = (k & 3) == 0 ? ev.x : (k & 3) == 1 ? ev.y : (k & 3) == 2 ? ev.z : ev.w;
-    a[k] = pi[k] * em;
-    sum = sum + a[k];
-  }
-  return sum;
-}
-
-// One site of the recurrence of the header: (m, e) <- (m, e) * s.
-__device__ __forceinline__ void likelihoodTimes(double& m, int& e, const double s)
-{
-  m = m * s;
-  if (m != 0.0 && __builtin_isfinite(m)) {
-    int de = 0;
-    m = __builtin_frexp(m, &de);
-    e += de;
-  }
-}
-
 // grid: any number of single-wave workgroups, no dynamic LDS.
 template <int KT, bool SEQ>
 __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(const FwdParams p)
@@ -113,76 +86,24 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
 
   const int lane = threadIdx.x;
   const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
-  const cfloat_p tPi = (cfloat_p)p.pi;
-  const Tables tabs = {(cfloat_p)p.rowSets, (cfloat_p)p.cR, (cfloat_p) nullptr};
+  const SweepParams sp = sweepParams(p);
+  const cfloat_p tPi = (cfloat_p)sp.pi;
+  const Tables tabs = {(cfloat_p)sp.rowSets, (cfloat_p)sp.cR, (cfloat_p) nullptr};
   const cint_p tEdges = (cint_p)p.edges;
-  const int S = p.S;
+  const int S = sp.S;
   const int B = p.B;
 
   for (;;) {
-    unsigned g = 0;
-    if (lane == 0) {
-      g = atomicAdd(p.counter, 1u);
-    }
-    g = __builtin_amdgcn_readfirstlane(g);
-    if (g >= (unsigned)p.nGroups) {
+    const unsigned g = pullGroup(sp.counter, lane);
+    if (g >= (unsigned)sp.nGroups) {
       break;
     }
-    const cuint_p gw = (cuint_p)(p.groups + (size_t)g);
-    const unsigned firstPair = gw[0];
-    const int nPairsInGroup = (int)gw[1];
-    const bool valid = lane < nPairsInGroup;
-    const unsigned pairIdx = firstPair + (valid ? (unsigned)lane : 0u); // (an idle lane repeats the group's first pair)
-    const size_t outIdx = (size_t)(pairIdx - p.pairBase);
-    const fsmc_pair pr = p.pairs[pairIdx];
-    const unsigned long long* rowA = p.haps + (size_t)pr.hap_a * p.W;
-    const unsigned long long* rowB = p.haps + (size_t)pr.hap_b * p.W;
-
-    // observation class of this lane's pair at site q: 0 het, 1 hom major, 2 hom minor (obsIsZero / obsIsTwo of
-    // HMM.cpp:647-652 as a row select); the two words of 64 sites are read once per 64 sites
-    int wordIdx = -1;
-    unsigned long long xw = 0, aw = 0;
-    auto obsClass = [&](const int q) -> int {
-      const int wi = q >> 6;
-      if (__builtin_expect(wi != wordIdx, 0)) {
-        const unsigned long long wa = rowA[wi];
-        const unsigned long long wb = rowB[wi];
-        xw = wa ^ wb;
-        aw = wa & wb;
-        wordIdx = wi;
-      }
-      const int bit = q & 63;
-      return ((xw >> bit) & 1ull) ? 0 : 1 + (int)((aw >> bit) & 1ull);
-    };
-    // site q's rows into ring slot (q & 1): asynchronous, counted in vmcnt, visible to this wave's LDS reads behind a
-    // vmcnt wait that covers it; the slot's previous rows must no longer be read
+    const PairLane pl = pairLane(sp, g, lane);
+    ObsWords obs{pl.rowA, pl.rowB};
+    RowIndexBlock stepRows, gapRows;
+    // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      const gchar_p src = uniformPtr(p.emis3 + (size_t)q * (NC * E4));
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        if (lane + i * kWave < NC * E4) {
-          dmaToLds((gf32x4_p)(src + (size_t)i * (kWave * sizeof(float4)) + laneOff), &ring[q & 1][i * kWave]);
-        }
-      }
-    };
-    // every request so far has landed and this wave's LDS reads may see it
-    auto landedRows = [&]() {
-      waitVm0();
-      __builtin_amdgcn_wave_barrier();
-      FSMC_GCN_ASM("" ::: "memory");
-    };
-    // table rows: the indices of 64 consecutive sites sit in one register (lane = site % 64, one coalesced load per 64
-    // sites, waited for on the spot) and are picked with v_readlane
-    int stepBlk = -1, stepVec = 0, gapBlk = -1, gapVec = 0;
-    auto rowOf = [&](const int* rows, int& blkHeld, int& vec, const int site) -> int {
-      const int blk = site >> 6;
-      if (__builtin_expect(blk != blkHeld, 0)) {
-        const int idx = blk * kWave + lane;
-        vec = rows[idx < S ? idx : S - 1];
-        blkHeld = blk;
-        waitVm0();
-      }
-      return __builtin_amdgcn_readlane(vec, site & (kWave - 1));
+      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
     };
 
     // the open bin: [lo, hi) = edges[bin], edges[bin + 1]; beyond the last bin lo = INT_MAX
@@ -205,13 +126,13 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
       if (pos + 1 < S) {
         stage(pos + 1); // into the slot of site pos - 1, whose steps are over
       }
-      const int c = obsClass(pos);
+      const int c = obs.classAt(pos);
       const float4* er = &ring[pos & 1][c * E4];
       float sum;
       if (__builtin_expect(pos == 0, 0)) {
         sum = forwardInit<KT, KA>(a, tPi, er);
       } else {
-        alpha_step<KT, KA, false, SY>(K, a, w, tabs, rowOf(p.stepRow, stepBlk, stepVec, pos), er, dg);
+        alpha_step<KT, KA, false, SY>(K, a, w, tabs, stepRows.at(sp.stepRow, S, lane, pos), er, dg);
         sum = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -229,9 +150,9 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
         }
         likelihoodTimes(bm, be, sd);
         if (pos == hi - 1) {
-          if (valid) {
-            p.binMant[outIdx * (size_t)B + (size_t)bin] = bm;
-            p.binExpo[outIdx * (size_t)B + (size_t)bin] = be;
+          if (pl.valid) {
+            p.binMant[pl.outIdx * (size_t)B + (size_t)bin] = bm;
+            p.binExpo[pl.outIdx * (size_t)B + (size_t)bin] = be;
           }
           ++bin;
           lo = bin < B ? hi : INT_MAX;
@@ -243,14 +164,14 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
         // the un-normalised half-step across the gap to the next site (HMM.cpp:760-767): no sum of its own
         if (pos + 1 < S) {
           landedRows(); // the rows of site pos + 1: its fourth row is the homozygous emission of the gap before it
-          alpha_step<KT, KA, false, SY>(K, a, w, tabs, rowOf(p.rowGapF, gapBlk, gapVec, pos + 1),
+          alpha_step<KT, KA, false, SY>(K, a, w, tabs, gapRows.at(p.rowGapF, S, lane, pos + 1),
                                         &ring[(pos + 1) & 1][3 * E4], dg);
         }
       }
     }
-    if (valid && p.mant) {
-      p.mant[outIdx] = m;
-      p.expo[outIdx] = e;
+    if (pl.valid && p.mant) {
+      p.mant[pl.outIdx] = m;
+      p.expo[pl.outIdx] = e;
     }
   }
 }

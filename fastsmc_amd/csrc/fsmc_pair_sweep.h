@@ -1,0 +1,181 @@
+// fsmc_pair_sweep.h -- what surrounds a step in the per-pair sweep kernels, once: forward_kernel (fsmc_pair_loglik.h)
+// and viterbi_kernel (fsmc_pair_viterbi.h) are built from these pieces and keep only their own recurrences.
+//
+// A sweep kernel: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue
+// (pullGroup, pairLane).  Per site it needs the observation class of the lane's pair from the packed haplotype words
+// (ObsWords), the emission rows of the site in a two-slot LDS ring fed by LDS-DMA one site ahead (stageRows,
+// landedRows), and the table row of the step, the indices of 64 consecutive sites held in one register
+// (RowIndexBlock).  The first site is pi * emission, scaled (firstSite); the scaling sums are multiplied up as a
+// mantissa / exponent pair (likelihoodTimes).  Everything is force-inlined and lives in registers; the decode kernels
+// of fsmc_kernels*.h keep their own copies of these pieces and do not see this header.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "fsmc_kernels.h"
+
+namespace fsmc
+{
+
+// What every sweep kernel needs of its launch.
+struct SweepParams {
+  int S;       // sites
+  int W;       // 64-bit words per haplotype row
+  int nGroups; // groups of the slice
+  unsigned pairBase; // first pair of the slice: the outputs are indexed by pair of the work list minus this
+  const float* pi;      // [KP]
+  const float* cR;      // [KP]
+  const float* rowSets; // [rows][5][KP]
+  const int* stepRow;   // [S] row of the (site) step into site q
+  const float4* emis3;  // [S][3 or 4][KP/4]
+  const unsigned long long* haps; // [nHaps][W]
+  const fsmc_pair* pairs;
+  const fsmc_group* groups; // the slice's first group
+  unsigned* counter;        // head of the group queue
+};
+// FwdParams and VitParams are flat kernel arguments that carry these fields under these names, each at the place it
+// always had (moving an argument moves the compiled kernels); the kernels read them through this view.
+template <typename Params> __device__ __forceinline__ SweepParams sweepParams(const Params& p)
+{
+  return SweepParams{p.S,     p.W,    p.nGroups, p.pairBase, p.pi,     p.cR,     p.rowSets,
+                     p.stepRow, p.emis3, p.haps,  p.pairs,    p.groups, p.counter};
+}
+
+// The next group of the queue, wave-uniform (the slice is done when it is not below nGroups).
+__device__ __forceinline__ unsigned pullGroup(unsigned* counter, const int lane)
+{
+  unsigned g = 0;
+  if (lane == 0) {
+    g = atomicAdd(counter, 1u);
+  }
+  return __builtin_amdgcn_readfirstlane(g);
+}
+
+// This lane's pair of group g: whether the lane has one, its index in the work list and in the slice's outputs, and
+// its two haplotype rows.
+struct PairLane {
+  bool valid;
+  unsigned pairIdx;
+  size_t outIdx;
+  const unsigned long long* rowA;
+  const unsigned long long* rowB;
+};
+__device__ __forceinline__ PairLane pairLane(const SweepParams& p, const unsigned g, const int lane)
+{
+  const cuint_p gw = (cuint_p)(p.groups + (size_t)g);
+  const unsigned firstPair = gw[0];
+  const int nPairsInGroup = (int)gw[1];
+  PairLane pl;
+  pl.valid = lane < nPairsInGroup;
+  pl.pairIdx = firstPair + (pl.valid ? (unsigned)lane : 0u); // (an idle lane repeats the group's first pair)
+  pl.outIdx = (size_t)(pl.pairIdx - p.pairBase);
+  const fsmc_pair pr = p.pairs[pl.pairIdx];
+  pl.rowA = p.haps + (size_t)pr.hap_a * p.W;
+  pl.rowB = p.haps + (size_t)pr.hap_b * p.W;
+  return pl;
+}
+
+// Observation class of a lane's pair at site q: 0 het, 1 hom major, 2 hom minor (obsIsZero / obsIsTwo of
+// HMM.cpp:647-652 as a row select).  The two words of 64 sites are read once per 64 sites, or after restart() when a
+// sweep starts somewhere else.
+struct ObsWords {
+  const unsigned long long* rowA;
+  const unsigned long long* rowB;
+  int wordIdx = -1;
+  unsigned long long xw = 0, aw = 0;
+  __device__ __forceinline__ int classAt(const int q)
+  {
+    const int wi = q >> 6;
+    if (__builtin_expect(wi != wordIdx, 0)) {
+      const unsigned long long wa = rowA[wi];
+      const unsigned long long wb = rowB[wi];
+      xw = wa ^ wb;
+      aw = wa & wb;
+      wordIdx = wi;
+    }
+    const int bit = q & 63;
+    return ((xw >> bit) & 1ull) ? 0 : 1 + (int)((aw >> bit) & 1ull);
+  }
+  __device__ __forceinline__ void restart()
+  {
+    wordIdx = -1;
+  }
+};
+
+// The n4 float4 of a site's emission rows at `rows` into the ring slot `slot` (NL requests of a wave, laneOff = 16 *
+// lane): asynchronous, counted in vmcnt, visible to this wave's LDS reads behind a vmcnt wait that covers it
+// (landedRows); the slot's previous rows must no longer be read.
+template <int NL>
+__device__ __forceinline__ void stageRows(const float4* rows, float4* slot, const int n4, const int lane,
+                                          const unsigned laneOff)
+{
+  const gchar_p src = uniformPtr(rows);
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    if (lane + i * kWave < n4) {
+      dmaToLds((gf32x4_p)(src + (size_t)i * (kWave * sizeof(float4)) + laneOff), slot + i * kWave);
+    }
+  }
+}
+// Every request so far has landed and this wave's LDS reads may see it.
+__device__ __forceinline__ void landedRows()
+{
+  waitVm0();
+  __builtin_amdgcn_wave_barrier();
+  FSMC_GCN_ASM("" ::: "memory");
+}
+
+// Table rows: the indices of 64 consecutive sites of rows[0 .. S) sit in one register (lane = site % 64, one coalesced
+// load per 64 sites, waited for on the spot; lanes beyond the last site repeat it) and are picked with v_readlane.
+struct RowIndexBlock {
+  int vec = 0, blk = -1; // (in this order: the other way round costs the kernels two registers a lane)
+  __device__ __forceinline__ int at(const int* rows, const int S, const int lane, const int site)
+  {
+    const int b = site >> 6;
+    if (__builtin_expect(b != blk, 0)) {
+      const int idx = b * kWave + lane;
+      vec = rows[idx < S ? idx : S - 1];
+      blk = b;
+      waitVm0();
+    }
+    return __builtin_amdgcn_readlane(vec, site & (kWave - 1));
+  }
+};
+
+// alpha at the first site, NOT yet scaled, and its sum: the operations of alpha_init up to its 1.0f / sum
+// (HMM.cpp:736-747), k ascending from 0.f.
+template <int KT, int KA> __device__ __forceinline__ float forwardInit(float (&a)[KA], cfloat_p pi, const float4* e)
+{
+  float sum = 0.f;
+  float4 ev = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < KT; ++k) {
+    if ((k & 3) == 0) {
+      ev = e[k >> 2];
+    }
+    const float em = (k & 3) == 0 ? ev.x : (k & 3) == 1 ? ev.y : (k & 3) == 2 ? ev.z : ev.w;
+    a[k] = pi[k] * em;
+    sum = sum + a[k];
+  }
+  return sum;
+}
+// ... and scaled: the vector of the first site as every later step leaves it, and its sum.
+template <int KT, int KA> __device__ __forceinline__ float firstSite(float (&a)[KA], cfloat_p pi, const float4* e)
+{
+  const float sum = forwardInit<KT, KA>(a, pi, e);
+  scale_pk<KT, KA>(a, a, sum);
+  return sum;
+}
+
+// One site of the likelihood recurrence (fsmc_pair_loglik.h): (m, e) <- (m, e) * s.
+__device__ __forceinline__ void likelihoodTimes(double& m, int& e, const double s)
+{
+  m = m * s;
+  if (m != 0.0 && __builtin_isfinite(m)) {
+    int de = 0;
+    m = __builtin_frexp(m, &de);
+    e += de;
+  }
+}
+
+} // namespace fsmc

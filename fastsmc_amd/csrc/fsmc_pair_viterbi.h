@@ -26,7 +26,7 @@
 //   end:      x[S-1] = the smallest k with delta_{S-1}[k] > every earlier one (strict >, k ascending)
 //             x[t-1] = psi[t][x[t]]   for t = S-1 .. 1
 //   probability of (path, observations): m = 1.0, e = 0; for t ascending: likelihoodTimes(m, e, (double)sum[t]);
-//             then likelihoodTimes(m, e, (double)delta_{S-1}[x[S-1]])          (fsmc_pair_loglik.h's function)
+//             then likelihoodTimes(m, e, (double)delta_{S-1}[x[S-1]])          (fsmc_pair_sweep.h's function)
 // em_t is the emission row of the pair's observation class at site t (emis3, as the decode reads it).  On equal values
 // the smaller predecessor index wins everywhere: that is what the comparisons above say.
 // states[i * S + t] = x[t] (uint8), mant[i] = m, expo[i] = e, in work-list order.  A pair whose mantissa is 0 or not
@@ -39,8 +39,10 @@
 // = 0 * best = +0, which adds +0 to the sum.
 //
 // viterbi_kernel<KT>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue.  The
-// surroundings of the step -- observation classes, the two-slot LDS-DMA emission ring one site ahead, the table rows of
-// 64 consecutive sites in one register -- are forward_kernel's (fsmc_pair_loglik.h), copied.  viterbi_step takes its
+// surroundings of the step -- the group queue, observation classes, the two-slot LDS-DMA emission ring one site ahead,
+// the table rows of 64 consecutive sites in one register, the first site -- are fsmc_pair_sweep.h's, shared with
+// forward_kernel (fsmc_pair_loglik.h); the step, the checkpoints, the second sweep and the traceback are this file's.
+// viterbi_step takes its
 // operand blocks by scalar loads one block ahead like alpha_step.  Registers: p and the vector under construction (the
 // suffix maxima one slot down, as alpha_step keeps alphaC: w[k] = mC[k+1] until state k is done, then v[k]), cI packed
 // four bytes to a register, the back-pointers of four states packed to one dword and stored as they complete.
@@ -59,7 +61,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fsmc_kernels.h"
-#include "fsmc_pair_loglik.h"
+#include "fsmc_pair_sweep.h"
 
 namespace fsmc
 {
@@ -228,9 +230,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
   const int lane = threadIdx.x;
   const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
   const unsigned laneOff4 = threadIdx.x * (unsigned)sizeof(unsigned);
-  const cfloat_p tPi = (cfloat_p)p.pi;
-  const Tables tabs = {(cfloat_p)p.rowSets, (cfloat_p)p.cR, (cfloat_p) nullptr};
-  const int S = p.S;
+  const SweepParams sp = sweepParams(p);
+  const cfloat_p tPi = (cfloat_p)sp.pi;
+  const Tables tabs = {(cfloat_p)sp.rowSets, (cfloat_p)sp.cR, (cfloat_p) nullptr};
+  const int S = sp.S;
   const int C = p.chunk;
   const int nChunks = p.nChunks;
   const bool trace = p.states != nullptr;
@@ -240,68 +243,16 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
   const int lastStart = trace ? (nChunks - 1) * C : S; // sweep 1 keeps the back-pointers from this site on
 
   for (;;) {
-    unsigned g = 0;
-    if (lane == 0) {
-      g = atomicAdd(p.counter, 1u);
-    }
-    g = __builtin_amdgcn_readfirstlane(g);
-    if (g >= (unsigned)p.nGroups) {
+    const unsigned g = pullGroup(sp.counter, lane);
+    if (g >= (unsigned)sp.nGroups) {
       break;
     }
-    const cuint_p gw = (cuint_p)(p.groups + (size_t)g);
-    const unsigned firstPair = gw[0];
-    const int nPairsInGroup = (int)gw[1];
-    const bool valid = lane < nPairsInGroup;
-    const unsigned pairIdx = firstPair + (valid ? (unsigned)lane : 0u); // (an idle lane repeats the group's first pair)
-    const size_t outIdx = (size_t)(pairIdx - p.pairBase);
-    const fsmc_pair pr = p.pairs[pairIdx];
-    const unsigned long long* rowA = p.haps + (size_t)pr.hap_a * p.W;
-    const unsigned long long* rowB = p.haps + (size_t)pr.hap_b * p.W;
-
-    // observation class of this lane's pair at site q: 0 het, 1 hom major, 2 hom minor; the two words of 64 sites are
-    // read once per 64 sites (or when a sweep starts somewhere else)
-    int wordIdx = -1;
-    unsigned long long xw = 0, aw = 0;
-    auto obsClass = [&](const int q) -> int {
-      const int wi = q >> 6;
-      if (__builtin_expect(wi != wordIdx, 0)) {
-        const unsigned long long wa = rowA[wi];
-        const unsigned long long wb = rowB[wi];
-        xw = wa ^ wb;
-        aw = wa & wb;
-        wordIdx = wi;
-      }
-      const int bit = q & 63;
-      return ((xw >> bit) & 1ull) ? 0 : 1 + (int)((aw >> bit) & 1ull);
-    };
-    // site q's rows into ring slot (q & 1): asynchronous, counted in vmcnt, visible to this wave's LDS reads behind a
-    // vmcnt wait that covers it; the slot's previous rows must no longer be read
+    const PairLane pl = pairLane(sp, g, lane);
+    ObsWords obs{pl.rowA, pl.rowB};
+    RowIndexBlock stepRows;
+    // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      const gchar_p src = uniformPtr(p.emis3 + (size_t)q * (NC * E4));
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        if (lane + i * kWave < NC * E4) {
-          dmaToLds((gf32x4_p)(src + (size_t)i * (kWave * sizeof(float4)) + laneOff), &ring[q & 1][i * kWave]);
-        }
-      }
-    };
-    // every request so far has landed and this wave's LDS reads may see it
-    auto landedRows = [&]() {
-      waitVm0();
-      __builtin_amdgcn_wave_barrier();
-      FSMC_GCN_ASM("" ::: "memory");
-    };
-    // table rows: the indices of 64 consecutive sites sit in one register and are picked with v_readlane
-    int stepBlk = -1, stepVec = 0;
-    auto rowOf = [&](const int site) -> int {
-      const int blk = site >> 6;
-      if (__builtin_expect(blk != stepBlk, 0)) {
-        const int idx = blk * kWave + lane;
-        stepVec = p.stepRow[idx < S ? idx : S - 1];
-        stepBlk = blk;
-        waitVm0();
-      }
-      return __builtin_amdgcn_readlane(stepVec, site & (kWave - 1));
+      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
     };
 
     float a[KA], w[KA];
@@ -316,18 +267,17 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
       if (pos + 1 < S) {
         stage(pos + 1); // into the slot of site pos - 1, whose step is over
       }
-      const int c = obsClass(pos);
+      const int c = obs.classAt(pos);
       const float4* er = &ring[pos & 1][c * E4];
       float sum;
       if (__builtin_expect(pos == 0, 0)) {
-        sum = forwardInit<KT, KA>(a, tPi, er);
-        scale_pk<KT, KA>(a, a, sum);
+        sum = firstSite<KT, KA>(a, tPi, er);
       } else {
         if (trace && pos % C == 0) { // delta of the site before chunk pos / C
           store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * kCkptRow), laneOff, a);
         }
         const int r = pos >= lastStart ? pos - lastStart : 0;
-        sum = viterbi_step<KT, KA, SY>(a, w, rowSetOf<KT>(tabs, rowOf(pos)), tabs.cR, er,
+        sum = viterbi_step<KT, KA, SY>(a, w, rowSetOf<KT>(tabs, stepRows.at(sp.stepRow, S, lane, pos)), tabs.cR, er,
                                        uniformPtr(psiBuf + (size_t)r * kPsiRow), laneOff4, dg);
       }
       likelihoodTimes(m, e, (double)sum);
@@ -344,9 +294,9 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
       }
       likelihoodTimes(m, e, (double)best);
     }
-    if (valid && p.mant) {
-      p.mant[outIdx] = m;
-      p.expo[outIdx] = e;
+    if (pl.valid && p.mant) {
+      p.mant[pl.outIdx] = m;
+      p.expo[pl.outIdx] = e;
     }
     if (!trace) {
       continue;
@@ -354,14 +304,14 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
 
     // ---- the traceback, chunk by chunk descending; every chunk but the last is swept again from its checkpoint first
     const unsigned kTop = (unsigned)(p.K - 1);
-    const size_t rowByte = outIdx * (size_t)S; // this pair's row in the slice's state rows
+    const size_t rowByte = pl.outIdx * (size_t)S; // this pair's row in the slice's state rows
     unsigned char* const out = p.states;
     unsigned acc = 0u; // the bytes of the output dword under construction
     for (int ch = nChunks - 1; ch >= 0; --ch) {
       const int lo = ch * C;
       const int hi = (lo + C < S ? lo + C : S) - 1; // the chunk's last site
       if (ch != nChunks - 1) {
-        wordIdx = -1;
+        obs.restart();
         waitVm0(); // (nothing of the traceback before is in flight when the ring is restarted)
         stage(lo);
         if (lo > 0) {
@@ -372,13 +322,12 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
           if (pos < hi) {
             stage(pos + 1);
           }
-          const int c = obsClass(pos);
+          const int c = obs.classAt(pos);
           const float4* er = &ring[pos & 1][c * E4];
           if (__builtin_expect(pos == 0, 0)) {
-            const float sum = forwardInit<KT, KA>(a, tPi, er);
-            scale_pk<KT, KA>(a, a, sum);
+            (void)firstSite<KT, KA>(a, tPi, er);
           } else {
-            (void)viterbi_step<KT, KA, SY>(a, w, rowSetOf<KT>(tabs, rowOf(pos)), tabs.cR, er,
+            (void)viterbi_step<KT, KA, SY>(a, w, rowSetOf<KT>(tabs, stepRows.at(sp.stepRow, S, lane, pos)), tabs.cR, er,
                                            uniformPtr(psiBuf + (size_t)(pos - lo) * kPsiRow), laneOff4, dg);
           }
         }
@@ -392,7 +341,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         acc |= x << sh;
         if (((unsigned)A & 3u) == 0u || t == 0) {
           const size_t D4 = A & ~(size_t)3;
-          if (valid) {
+          if (pl.valid) {
             if (((unsigned)A & 3u) == 0u && t + 3 < S) {
               *(unsigned*)(out + D4) = acc;
             } else {
