@@ -24,6 +24,10 @@
 //   member, array and sequence mode; the wave-group and any-K families have none.
 // Viterbi kernel (viterbi_kernel<KT>, fsmc_pair_viterbi.h): the per-pair most probable state paths of every lane-per-pair
 //   member, array mode; the wave-group and any-K families have none.
+// What the families share is defined once: fsmc_lane_scaffold.h (a lane's pair and haplotype rows, the next group of a
+//   sums batch, the row-index block),
+//   fsmc_site_consumers.h (the per-pair mean / MAP consumer, the IBD record writer), both included by fsmc_kernels.h;
+//   fsmc_pair_sweep.h (what only the two sweep kernels need).
 // (The runtime-K instantiation KT = 0 and the four-lanes-per-pair kernel of earlier builds are gone: every model of at
 //  most 256 states, in every mode, runs one of the two families above.)
 #pragma once

@@ -1004,6 +1004,15 @@ __device__ __forceinline__ void scanBlocks(float (&w)[KA], float& s, const float
   }
 }
 
+} // namespace fsmc
+
+// the lane-per-pair scaffold and the site consumers, built on the helpers above
+#include "fsmc_lane_scaffold.h"
+#include "fsmc_site_consumers.h"
+
+namespace fsmc
+{
+
 // SEQ: sequence mode (DecodingParams::decodingSequence) -- every site step is preceded by an un-normalised
 // half-step across the homozygous stretch since the neighbouring site, and the vectors the posterior is built
 // from are the ones the reference's buffers end up holding (HMM.cpp:767, 922; oracle/hmm_oracle.h):
@@ -1114,19 +1123,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
 #endif
     unsigned g = 0;
     if (MODE == kModeSums) {
-      // one BATCH per wave and launch: wave i writes the sums of batch groupBase + i into plane i, and the host adds the
-      // planes to the accumulator one after the other -- the reference's order, batch by batch (HMM.cpp:1054-1073).  A
-      // batch of more than 64 pairs is several consecutive groups (p.batchFirst: first group of every batch): the wave
-      // decodes them in turn and every group continues the batch's running sums where the group before left them.
-      if (p.batchFirst) {
-        const cuint_p bf = (cuint_p)p.batchFirst;
-        g = bf[p.groupBase + blockIdx.x] + round;
-        if (g >= bf[p.groupBase + blockIdx.x + 1]) {
-          g = (unsigned)p.nGroups;
-        }
-      } else {
-        g = round == 0 ? (unsigned)p.groupBase + blockIdx.x : (unsigned)p.nGroups;
-      }
+      g = sumsGroupOf(p, round); // one BATCH per wave and launch, its groups in turn
     } else {
       if (lane == 0) {
         g = atomicAdd(&p.counters[p.groupBase], 1u);
@@ -1143,8 +1140,9 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
     int to = (int)gw[3];
     int scanFrom = (int)gw[4];
     int aEnd = (MODE == kModeIbd) ? (int)gw[5] : to; // the alpha sweep stops here
-    bool valid = lane < nPairsInGroup;
-    unsigned pairIdx = firstPair + (valid ? (unsigned)lane : 0u);
+    const LanePair me = laneInGroup(firstPair, nPairsInGroup, lane);
+    bool valid = me.valid;
+    unsigned pairIdx = me.pairIdx;
     // DUAL: this lane's own windows, and the wave-uniform windows of the two halves
     int myFrom = from, myTo = to, mySF = scanFrom, myST = aEnd;
     int toA = to, toB = to, fromA = from, fromB = from, stA = aEnd, stB = aEnd;
@@ -1169,9 +1167,9 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
         valid = lane < nPairsInGroup && lane < 32;
       }
     }
-    const fsmc_pair pr = p.pairs[pairIdx];
-    const unsigned long long* rowA = p.haps + (size_t)pr.hap_a * p.W;
-    const unsigned long long* rowB = p.haps + (size_t)pr.hap_b * p.W;
+    const HapRows hap = hapRows(p, pairIdx);
+    const unsigned long long* rowA = hap.rowA;
+    const unsigned long long* rowB = hap.rowB;
 
     const int nA = aEnd - from;
     const int nChunks = (nA + C - 1) / C;
@@ -1239,25 +1237,9 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
         }
       }
     };
-    // Table row of the step into `site`: the indices of 64 consecutive sites sit in one VGPR (lane = site % 64,
-    // one coalesced load per 64 sites) and are picked with v_readlane.  (As scalar loads, one per site, each was
-    // waited for on the spot -- the register allocator had no SGPR to keep it in flight -- a round trip to L2 per
-    // site in the loop heads.)
-    int rowBlk = -1;
-    int rowVec = 0;
-    auto stepRowOf = [&](const int site) -> int {
-      const int blk = site >> 6;
-      if (__builtin_expect(blk != rowBlk, 0)) { // once per 64 sites
-        const int idx = blk * kWave + lane;
-        rowVec = p.stepRow[idx < p.S ? idx : p.S - 1];
-        rowBlk = blk;
-        // waited for here, once per 64 sites: otherwise the compiler, which cannot tell at the v_readlane below
-        // whether this load is the pending one, waits for vmcnt(0) at EVERY site -- right behind the emission-row
-        // request that was just issued
-        waitVm0();
-      }
-      return __builtin_amdgcn_readlane(rowVec, site & (kWave - 1));
-    };
+    // Table row of the step into `site` (RowIndexBlock: the rows of 64 consecutive sites in one VGPR, picked with v_readlane)
+    RowIndexBlock stepRows;
+    auto stepRowOf = [&](const int site) -> int { return stepRows.at(p.stepRow, p.S, lane, site); };
     // Wait for the emission rows requested one iteration ago (prefetchEmis) while the beta-row stores issued behind
     // them may still be in flight: vector memory operations retire in order, so "at most K4 outstanding" means the
     // older request is done.  Explicit, because the compiler cannot count a conditional store burst and would wait
@@ -1448,22 +1430,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
         return;
       }
 #endif
-      const unsigned idx = atomicAdd(&p.counters[1], 1u);
-      float mean = 0.f, mapv = 0.f;
-      if constexpr (TRACK) {
-        segment_ages(K, p.ageThr, spsMem, tPi, tExpT, (p.flags & FSMC_WANT_MEAN) != 0,
-                     (p.flags & FSMC_WANT_MAP) != 0, mean, mapv);
-      }
-      if (idx < p.recCap) {
-        fsmc_ibd_record r;
-        r.pair = pairIdx;
-        r.start = s0;
-        r.end = s1;
-        r.prob = acc;
-        r.post_mean = mean;
-        r.map = mapv;
-        p.recs[idx] = r;
-      }
+      emitIbdRecord<TRACK>(p, K, spsMem, tPi, tExpT, pairIdx, s0, s1, acc);
     };
     // LDS-DMA of one stored beta row (K4 x 1 KiB) into the landing zone: asynchronous, no VGPRs
     auto fetchBeta = [&](const float4* row) { // row: wave-uniform address of the stored vector
@@ -1809,24 +1776,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
 
         FSMC_END(cycW, 11);
         if (MODE == kModePerPair) {
-          // HMM::writePerPairOutput (HMM.cpp:1378-1409): mean = sum_k post*E[t_k] (k ascending from 0.f),
-          // MAP = first strictly larger posterior
-          float mean = 0.f;
-          float best = 0.f;
-          int arg = 0;
-#pragma unroll
-          for (int k = 0; k < K; ++k) {
-            const float post = w[k] * cq;
-            mean = mean + post * coalLds[k];
-            if (best < post) {
-              arg = k;
-              best = post;
-            }
-          }
-          if (valid) {
-            if (p.ppMean) p.ppMean[(size_t)pairIdx * p.S + pos] = mean;
-            if (p.ppMap) p.ppMap[(size_t)pairIdx * p.S + pos] = arg;
-          }
+          consumePerPair<KT, KA>(w, cq, coalLds, valid, pairIdx, pos, p);
         }
 
         if (MODE == kModeSums) {

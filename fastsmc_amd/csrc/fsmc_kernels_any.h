@@ -188,15 +188,8 @@ __global__ __launch_bounds__(kWave) void decode_kernel_any(const KParams p)
 
   for (unsigned round = 0;; ++round) {
     unsigned g = 0;
-    if (MODE == kModeSums) { // one batch per wave and launch, its groups in turn (decode_kernel, same place)
-      if (p.batchFirst) {
-        g = p.batchFirst[p.groupBase + blockIdx.x] + round;
-        if (g >= p.batchFirst[p.groupBase + blockIdx.x + 1]) {
-          g = (unsigned)p.nGroups;
-        }
-      } else {
-        g = round == 0 ? (unsigned)p.groupBase + blockIdx.x : (unsigned)p.nGroups;
-      }
+    if (MODE == kModeSums) { // one batch per wave and launch, its groups in turn
+      g = sumsGroupOf(p, round);
     } else {
       if (lane == 0) {
         g = atomicAdd(&p.counters[p.groupBase], 1u);
@@ -501,22 +494,7 @@ __global__ __launch_bounds__(kWave) void decode_kernel_any(const KParams p)
           }
           const int level = s >= p.thr[0] ? 0 : s >= p.thr[1] ? 1 : s >= p.thr[2] ? 2 : s >= p.thr[3] ? 3 : 4;
           auto emit = [&](const int s0, const int s1) {
-            const unsigned idx = atomicAdd(&p.counters[1], 1u);
-            float mean = 0.f, mapv = 0.f;
-            if constexpr (TRACK) {
-              segment_ages(K, p.ageThr, sps + lane, (cfloat_p)p.pi, (cfloat_p)p.expT, (p.flags & FSMC_WANT_MEAN) != 0,
-                           (p.flags & FSMC_WANT_MAP) != 0, mean, mapv);
-            }
-            if (idx < p.recCap) {
-              fsmc_ibd_record r;
-              r.pair = pairIdx;
-              r.start = s0;
-              r.end = s1;
-              r.prob = acc;
-              r.post_mean = mean;
-              r.map = mapv;
-              p.recs[idx] = r;
-            }
+            emitIbdRecord<TRACK>(p, K, sps + lane, (cfloat_p)p.pi, (cfloat_p)p.expT, pairIdx, s0, s1, acc);
           };
           if (valid && cur != 4 && level != cur) { // a change of level closes the open segment at pos - 1
             emit(segStart, pos - 1);

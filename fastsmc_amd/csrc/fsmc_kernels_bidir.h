@@ -89,16 +89,8 @@ __global__ __launch_bounds__(2 * kWave, minWavesPerSimd(KT)) void decode_kernel_
   constexpr int wv = decltype(roleTag)::value; // 0: wave A (forward), 1: wave B (backward)
   for (unsigned round = 0;; ++round) {
     unsigned g = 0;
-    if (MODE == kModeSums) { // one BATCH per workgroup and launch, its groups in turn (fsmc_kernels.h, same place)
-      if (p.batchFirst) {
-        const cuint_p bf = (cuint_p)p.batchFirst;
-        g = bf[p.groupBase + blockIdx.x] + round;
-        if (g >= bf[p.groupBase + blockIdx.x + 1]) {
-          g = (unsigned)p.nGroups;
-        }
-      } else {
-        g = round == 0 ? (unsigned)p.groupBase + blockIdx.x : (unsigned)p.nGroups;
-      }
+    if (MODE == kModeSums) { // one BATCH per workgroup and launch, its groups in turn
+      g = sumsGroupOf(p, round);
     } else {
       if (wv == 0 && lane == 0) {
         groupLds = atomicAdd(&p.counters[p.groupBase], 1u);
@@ -116,19 +108,17 @@ __global__ __launch_bounds__(2 * kWave, minWavesPerSimd(KT)) void decode_kernel_
     const int from = (int)gw[2];
     const int to = (int)gw[3];
     const int mid = from + (to - from) / 2; // wave A stores alpha of [from, mid), wave B beta of [mid, to)
-    const bool valid = lane < nPairsInGroup;
-    const unsigned pairIdx = firstPair + (valid ? (unsigned)lane : 0u);
-    const fsmc_pair pr = p.pairs[pairIdx];
-    const unsigned long long* rowA = p.haps + (size_t)pr.hap_a * p.W;
-    const unsigned long long* rowB = p.haps + (size_t)pr.hap_b * p.W;
+    const LanePair me = laneInGroup(firstPair, nPairsInGroup, lane);
+    const bool valid = me.valid;
+    const HapRows hap = hapRows(p, me.pairIdx);
 
     int wordIdx = -1;
     unsigned long long xw = 0, aw = 0;
     auto obsClass = [&](const int q) -> int { // 0 het, 1 hom major, 2 hom minor (HMM.cpp:647-652)
       const int wi = q >> 6;
       if (__builtin_expect(wi != wordIdx, 0)) {
-        const unsigned long long wa = rowA[wi];
-        const unsigned long long wb = rowB[wi];
+        const unsigned long long wa = hap.rowA[wi];
+        const unsigned long long wb = hap.rowB[wi];
         xw = wa ^ wb;
         aw = wa & wb;
         wordIdx = wi;
@@ -160,18 +150,8 @@ __global__ __launch_bounds__(2 * kWave, minWavesPerSimd(KT)) void decode_kernel_
         }
       }
     };
-    int rowBlk = -1;
-    int rowVec = 0;
-    auto stepRowOf = [&](const int site) -> int { // table row of the step into `site` (fsmc_kernels.h, same place)
-      const int blk = site >> 6;
-      if (__builtin_expect(blk != rowBlk, 0)) {
-        const int idx = blk * kWave + lane;
-        rowVec = p.stepRow[idx < p.S ? idx : p.S - 1];
-        rowBlk = blk;
-        waitVm0();
-      }
-      return __builtin_amdgcn_readlane(rowVec, site & (kWave - 1));
-    };
+    RowIndexBlock stepRows; // table row of the step into `site`
+    auto stepRowOf = [&](const int site) -> int { return stepRows.at(p.stepRow, p.S, lane, site); };
     // "at most n vector-memory operations outstanding" (they retire in order): the older emission-row request is done
     auto waitVmAtMost = [&](auto nTag) {
 #if defined(FSMC_BIDIR_FULL_WAITS) // (diagnostic: every counted wait becomes a full one)
@@ -253,22 +233,7 @@ __global__ __launch_bounds__(2 * kWave, minWavesPerSimd(KT)) void decode_kernel_
     // slot whose rows are no longer needed (the sums' 00 / 01 / 11 split parks the classes of the 64 pairs there).
     auto consume = [&](const int pos, const float cq, const int c, const int freeSlot) {
       if (MODE == kModePerPair) { // HMM.cpp:1378-1409
-        float mean = 0.f;
-        float best = 0.f;
-        int arg = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const float post = w[k] * cq;
-          mean = mean + post * coalLds[k];
-          if (best < post) {
-            arg = k;
-            best = post;
-          }
-        }
-        if (valid) {
-          if (p.ppMean) p.ppMean[(size_t)pairIdx * p.S + pos] = mean;
-          if (p.ppMap) p.ppMap[(size_t)pairIdx * p.S + pos] = arg;
-        }
+        consumePerPair<KT, KA>(w, cq, coalLds, valid, me.pairIdx, pos, p);
       }
       if (MODE == kModeDump) {
         float* out = p.dumpOut + p.dumpOffsets[g] + (size_t)(pos - from) * Kreal * kWave + lane;

@@ -852,19 +852,7 @@ __global__ __launch_bounds__(NW * kWave, w2WorkgroupsPerCU(KH, NW)) void decode_
   for (unsigned round = 0;; ++round) {
     unsigned g;
     if (MODE == kModeSums) {
-      // one BATCH per workgroup and launch: workgroup i writes the sums of batch groupBase + i into plane i, and the
-      // host adds the planes to the accumulator one after the other -- the reference's order, batch by batch
-      // (HMM.cpp:1054-1073); the groups of a batch of more than 64 pairs are decoded in turn and continue the batch's
-      // running sums (fsmc_kernels.h)
-      if (p.batchFirst) {
-        const cuint_p bf = (cuint_p)p.batchFirst;
-        g = bf[p.groupBase + blockIdx.x] + round;
-        if (g >= bf[p.groupBase + blockIdx.x + 1]) {
-          g = (unsigned)p.nGroups;
-        }
-      } else {
-        g = round == 0 ? (unsigned)p.groupBase + blockIdx.x : (unsigned)p.nGroups;
-      }
+      g = sumsGroupOf(p, round); // one BATCH per workgroup and launch, its groups in turn
     } else {
       if (threadIdx.x == 0) {
         groupLds = atomicAdd(&p.counters[p.groupBase], 1u);
@@ -1158,6 +1146,8 @@ __global__ __launch_bounds__(NW * kWave, w2WorkgroupsPerCU(KH, NW)) void decode_
     int segStart = 0;
     float acc = 0.f;
     float a[KH];
+    // (emitIbdRecord of fsmc_site_consumers.h written out: the pair index is computed for a record that is kept only --
+    //  handed over as an argument it cost the IBD kernels of the members beyond 512 states spilled registers)
     auto emit = [&](const int s0, const int s1) { // wave 0 only (lane = pair)
       const unsigned idx = atomicAdd(&p.counters[1], 1u);
       float mean = 0.f, mapv = 0.f;

@@ -4,10 +4,10 @@
 // A sweep kernel: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue
 // (pullGroup, pairLane).  Per site it needs the observation class of the lane's pair from the packed haplotype words
 // (ObsWords), the emission rows of the site in a two-slot LDS ring fed by LDS-DMA one site ahead (stageRows,
-// landedRows), and the table row of the step, the indices of 64 consecutive sites held in one register
-// (RowIndexBlock).  The first site is pi * emission, scaled (firstSite); the scaling sums are multiplied up as a
-// mantissa / exponent pair (likelihoodTimes).  Everything is force-inlined and lives in registers; the decode kernels
-// of fsmc_kernels*.h keep their own copies of these pieces and do not see this header.
+// landedRows), and the table row of the step (RowIndexBlock).  The first site is pi * emission, scaled (firstSite); the
+// scaling sums are multiplied up as a mantissa / exponent pair (likelihoodTimes).  A lane's pair and rows (laneInGroup,
+// hapRows) and RowIndexBlock are fsmc_lane_scaffold.h's, shared with the decode kernels; the decode kernels keep their
+// own observation words and emission ring.  Everything is force-inlined and lives in registers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,16 +63,9 @@ struct PairLane {
 __device__ __forceinline__ PairLane pairLane(const SweepParams& p, const unsigned g, const int lane)
 {
   const cuint_p gw = (cuint_p)(p.groups + (size_t)g);
-  const unsigned firstPair = gw[0];
-  const int nPairsInGroup = (int)gw[1];
-  PairLane pl;
-  pl.valid = lane < nPairsInGroup;
-  pl.pairIdx = firstPair + (pl.valid ? (unsigned)lane : 0u); // (an idle lane repeats the group's first pair)
-  pl.outIdx = (size_t)(pl.pairIdx - p.pairBase);
-  const fsmc_pair pr = p.pairs[pl.pairIdx];
-  pl.rowA = p.haps + (size_t)pr.hap_a * p.W;
-  pl.rowB = p.haps + (size_t)pr.hap_b * p.W;
-  return pl;
+  const LanePair lp = laneInGroup(gw[0], (int)gw[1], lane);
+  const HapRows hap = hapRows(p, lp.pairIdx);
+  return PairLane{lp.valid, lp.pairIdx, (size_t)(lp.pairIdx - p.pairBase), hap.rowA, hap.rowB};
 }
 
 // Observation class of a lane's pair at site q: 0 het, 1 hom major, 2 hom minor (obsIsZero / obsIsTwo of
@@ -124,23 +117,6 @@ __device__ __forceinline__ void landedRows()
   __builtin_amdgcn_wave_barrier();
   FSMC_GCN_ASM("" ::: "memory");
 }
-
-// Table rows: the indices of 64 consecutive sites of rows[0 .. S) sit in one register (lane = site % 64, one coalesced
-// load per 64 sites, waited for on the spot; lanes beyond the last site repeat it) and are picked with v_readlane.
-struct RowIndexBlock {
-  int vec = 0, blk = -1; // (in this order: the other way round costs the kernels two registers a lane)
-  __device__ __forceinline__ int at(const int* rows, const int S, const int lane, const int site)
-  {
-    const int b = site >> 6;
-    if (__builtin_expect(b != blk, 0)) {
-      const int idx = b * kWave + lane;
-      vec = rows[idx < S ? idx : S - 1];
-      blk = b;
-      waitVm0();
-    }
-    return __builtin_amdgcn_readlane(vec, site & (kWave - 1));
-  }
-};
 
 // alpha at the first site, NOT yet scaled, and its sum: the operations of alpha_init up to its 1.0f / sum
 // (HMM.cpp:736-747), k ascending from 0.f.

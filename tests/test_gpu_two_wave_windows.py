@@ -320,3 +320,62 @@ def test_two_wave_workspace_that_cannot_be_had_falls_back_to_the_one_wave_plan(s
     assert served[0] == [2, 2, 2]
     same(served, plain)
     ctx.close()
+
+
+@pytest.mark.parametrize("K", [69, 16])
+def test_sums_walk_over_small_batches(K):
+    """The walk over a batch's pairs goes sixteen pairs a turn and then one pair a turn (the sums consumer of
+    csrc/fsmc_kernels.h and csrc/fsmc_kernels_bidir.h):
+    batches of 1 pair (tail only), 15 (just under one turn), 16 (exactly one turn), 17 (one turn plus one) and 63 (three
+    turns plus fifteen), each its own group -- alone in a launch and all five in one launch -- with and without the
+    00 / 01 / 11 split, one and two waves per window.  66 sites cross a 64-site word: the observation words and the block
+    of table-row indices are reloaded once."""
+    pm, bits, folded = _problem(K, S=66)
+    sizes = [1, 15, 16, 17, 63]
+    firsts = [sum(sizes[:i]) for i in range(len(sizes))]
+    pairs = O.enumerate_all_pairs(32)[:sum(sizes)]
+    want_all = [np.zeros((pm.S, pm.K), np.float32) for _ in range(4)]
+    want_each = []
+    for first, n in zip(firsts, sizes):
+        sub = pairs[first:first + n]
+        ob = np.stack([folded[a] ^ folded[b] for a, b in sub])
+        hb = np.stack([folded[a] & folded[b] for a, b in sub])
+        wpost, _ = O.decode_batch(pm, ob, hb, 0, pm.S)
+        each = [np.zeros((pm.S, pm.K), np.float32) for _ in range(4)]
+        O.augment_sum_over_pairs(pm, wpost, n, ob, hb, *each)
+        O.augment_sum_over_pairs(pm, wpost, n, ob, hb, *want_all)  # (the batches in turn, as the host adds the planes)
+        want_each.append(each)
+
+    def groups_of(spans):
+        gr = np.zeros(len(spans), capi.GROUP_DTYPE)
+        for g, (first, n) in zip(gr, spans):
+            g["first_pair"], g["n_pairs"], g["from"], g["to"], g["scan_from"], g["scan_to"] = first, n, 0, pm.S, 0, pm.S
+        return gr
+
+    # every batch alone in a launch, then the five in one launch
+    launches = [(pairs[first:first + n], groups_of([(0, n)]), each) for first, n, each in zip(firsts, sizes, want_each)]
+    launches.append((pairs, groups_of(list(zip(firsts, sizes))), want_all))
+    got = {}
+    for mode in (0, 1):  # automatic (these launches qualify), never
+        ctx = capi.Context(0)
+        ctx.set_two_wave_windows(mode)
+        model = ctx.create_model(pm)
+        ctx.upload_haps(bits, pm.S)
+        got[mode] = []
+        for li, (prs, groups, want) in enumerate(launches):
+            ctx.upload_worklist(_pairs_array(prs), groups)
+            s, mm = ctx.decode_sums(model, major_minor=True)
+            assert ctx.last_waves_per_window() == (2 if mode == 0 else 1)
+            s_only, _ = ctx.decode_sums(model)
+            assert ctx.last_waves_per_window() == (2 if mode == 0 else 1)
+            np.testing.assert_array_equal(s, want[0], err_msg=f"launch {li} mode {mode}")
+            for a, b in zip(mm, want[1:]):
+                np.testing.assert_array_equal(a, b, err_msg=f"launch {li} mode {mode}")
+            np.testing.assert_array_equal(s_only, want[0], err_msg=f"launch {li} mode {mode}, no split")
+            got[mode].append((s, mm, s_only))
+        ctx.close()
+    for (s2, mm2, o2), (s1, mm1, o1) in zip(got[0], got[1]):
+        np.testing.assert_array_equal(s2, s1)
+        for a, b in zip(mm2, mm1):
+            np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(o2, o1)

@@ -5,6 +5,8 @@
                                                          <tag>_kernel_stats.csv, <tag>_rocprofv3_summary.json
   tools/stamp_profiles.py c3n1 <bench_json> <tag>       `bench.py --workload c3` line -> profiles/<tag>_c3_n1.json
   tools/stamp_profiles.py pmc <prof_dir> <name>         tools/prof_counters.sh output -> profiles/<name>.txt (stamped)
+  tools/stamp_profiles.py ab <raw_jsonl> <tag> [<parent lib_hash>]   A/B of two libraries with bench.py --full, one
+                                                         {"built_from", "rep", "line"} record a run -> profiles/<tag>.jsonl
   tools/stamp_profiles.py round <round_dir> <tag>       tools/measure_round.sh output (gpurun_out/round_<tag>, with the C4
                                                          profile in gpurun_out/profile_<tag>_c4) -> profiles/<tag>_*
 
@@ -106,5 +108,25 @@ def pmc(src: str, name: str) -> None:
     print(f"profiles/{name}.txt")
 
 
+def ab(src: str, tag: str, parent_hash: str = "") -> None:
+    """Runs of bench.py --full with the parent's library (FSMC_HIP_LIB) and with this tree's, in the order they ran.  A
+    bench line states the hash of the SOURCES beside it, whichever library it loaded: every record is stamped with the
+    hash of the library that ran, and a parent run's own `lib_hash` fields are dropped."""
+    h = hip_source_hash()
+    with open(os.path.join(ROOT, "profiles", f"{tag}.jsonl"), "w") as out:
+        for ln in open(src).read().strip().splitlines():
+            rec = json.loads(ln)
+            if rec["built_from"] == "new":
+                assert rec["line"]["config"]["lib_hash"] == h, "measured with another build of the library"
+                rec["built_from"], rec["lib_hash"] = "this tree", h
+            else:
+                rec["built_from"], rec["lib_hash"] = "parent", parent_hash or None
+                rec["line"]["config"].pop("lib_hash", None)
+                for w in rec["line"]["config"].get("other_workloads", []):
+                    w.pop("lib_hash", None)
+            out.write(json.dumps(rec) + "\n")
+    print(f"profiles/{tag}.jsonl")
+
+
 if __name__ == "__main__":
-    {"traffic": traffic, "c3n1": c3n1, "round": round_files, "pmc": pmc}[sys.argv[1]](sys.argv[2], sys.argv[3])
+    {"traffic": traffic, "c3n1": c3n1, "round": round_files, "pmc": pmc, "ab": ab}[sys.argv[1]](*sys.argv[2:])
