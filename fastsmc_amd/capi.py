@@ -29,7 +29,7 @@ SYMBOLS = [
     "fsmc_ctx_expect_work",
     "fsmc_ctx_set_chunk_sites", "fsmc_ctx_set_beta_stride", "fsmc_ctx_last_beta_stride", "fsmc_ctx_last_plan",
     "fsmc_ctx_last_kernel", "fsmc_ctx_set_pairing", "fsmc_ctx_last_items", "fsmc_ctx_set_two_wave_windows", "fsmc_ctx_last_waves_per_window", "fsmc_ctx_last_segment_sums_in_lds", "fsmc_ctx_set_resident_chunks",
-    "fsmc_ctx_last_resident_chunks",
+    "fsmc_ctx_last_resident_chunks", "fsmc_ctx_set_chunk_pool", "fsmc_ctx_last_chunk_pool",
     "fsmc_model_create", "fsmc_model_destroy", "fsmc_haps_upload", "fsmc_worklist_upload",
     "fsmc_decode_ibd_launch", "fsmc_decode_ibd_fetch", "fsmc_sync", "fsmc_last_kernel_ms", "fsmc_phase_cycles",
     "fsmc_decode_ibd",
@@ -120,6 +120,8 @@ def load():
         L.fsmc_ctx_last_waves_per_window.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_ctx_last_items.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_ctx_last_segment_sums_in_lds.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_ctx_set_chunk_pool.argtypes = [vp, i32, u32]
+        L.fsmc_ctx_last_chunk_pool.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.fsmc_model_create.argtypes = [vp, C.POINTER(_ModelDesc), C.POINTER(vp)]
         L.fsmc_model_destroy.argtypes = [vp]
         L.fsmc_model_destroy.restype = None
@@ -232,6 +234,18 @@ class Context:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_resident_chunks(self._h, C.byref(v)))
         return v.value
+
+    def set_chunk_pool(self, mode: int, phi_percent: int = 0):
+        """The resident chunk buffers of a launch as one pool its waves claim from: -1 = in IBD launches of more than two
+        rounds, 0 = never, 1 = also in one or two rounds and the sums; a window asks for ``phi_percent`` / 100 x its share (0 = the default)."""
+        self._check(self._L.fsmc_ctx_set_chunk_pool(self._h, mode, phi_percent))
+
+    def last_chunk_pool(self) -> dict:
+        """Of the last launch, once it has completed: the pool's buffers (0: static layout), chunks kept, chunks
+        rebuilt, buffers still claimed."""
+        b, k, r, o = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.fsmc_ctx_last_chunk_pool(self._h, C.byref(b), C.byref(k), C.byref(r), C.byref(o)))
+        return {"buffers": b.value, "kept": k.value, "rebuilt": r.value, "outstanding": o.value}
 
     def set_beta_stride(self, stride: int):
         """0 = automatic, 1 = every beta row through HBM, 2 = every second row (the others recomputed)."""

@@ -64,6 +64,10 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// The pool of chunk buffers (fsmc_ctx_set_chunk_pool): the shipped defaults, chosen by measurement
+constexpr int kChunkPoolDefault = -1;
+constexpr uint32_t kChunkPoolPhiDefault = 200;
+
 // The entry points that send the work list through the device in slices of groups (planSlices): each has its own
 // slice setting and its own count of the last call's slices.
 enum PairSlicing {
@@ -113,6 +117,11 @@ struct fsmc_ctx {
   int lastSlots = 0;
   int lastChunk = 0, lastMaxChunks = 0, lastResident = 0;
   int residentChunks = -1; // chunks of a window that skip the rebuild: -1 = as many as the workspace limit allows, 0 = none
+  // The resident chunk buffers of a launch as one pool the waves claim from (decode_kernel_pool, KParamsPool)
+  int chunkPool = kChunkPoolDefault; // -1 = IBD launches of more than two rounds, 0 = never, 1 = wherever it is built
+  uint32_t chunkPoolPhi = kChunkPoolPhiDefault; // per cent of its share of the pool that a window may ask for
+  DevBuf poolState;        // the pool's cursor, counters and claim words: zeroed on the stream before every launch
+  uint32_t lastPoolBuffers = 0; // ... of the last launch (0: it kept the static layout)
   uint32_t chunkSites = 0; // 0 = automatic
   uint32_t betaStride = 0; // 0 = automatic (2 where the kernel exists), 1 = store every beta row
   int lastStride = 1;
@@ -301,6 +310,7 @@ std::vector<float> padRows(const float* src, size_t rows, int K, int KP)
 }
 
 using KernelFn = void (*)(const KParams);
+using PoolKernelFn = void (*)(const KParamsPool); // decode_kernel_pool: the same sweeps with the chunk pool
 
 // Which member of the lane-per-pair family decodes a model (fsmc_instances.h): 69 for the reference's 69-state
 // models and K itself where the library has an exact member of K states, the padded row length for every other model
@@ -311,6 +321,21 @@ int familyMember(const fsmc_model* m)
     return m->K;
   }
   return (m->K <= 128 && m->KP % kKPad == 0 && m->KP <= 128) ? m->KP : 0;
+}
+
+// The member's kernel with the chunk pool (array mode, one group per wave: IBD decode and sums), nullptr where none is built.
+template <int KT> PoolKernelFn pickPoolMember(int mode, bool track, bool half)
+{
+  if constexpr (poolBuilt(KT)) {
+    if (mode == kModeIbd) {
+      return half ? (track ? decode_kernel_pool<KT, kModeIbd, true, true> : decode_kernel_pool<KT, kModeIbd, false, true>)
+                  : (track ? decode_kernel_pool<KT, kModeIbd, true, false> : decode_kernel_pool<KT, kModeIbd, false, false>);
+    }
+    if (mode == kModeSums) {
+      return half ? decode_kernel_pool<KT, kModeSums, false, true> : decode_kernel_pool<KT, kModeSums, false, false>;
+    }
+  }
+  return nullptr;
 }
 
 template <int KT> KernelFn pickMember(int mode, bool track, bool seq, bool half, bool dual = false)
@@ -451,6 +476,7 @@ struct KernelChoice {
   unsigned threads = kWave;
   int member = 0;
   int stride = 1;
+  PoolKernelFn poolFn = nullptr; // the same kernel with the chunk pool, launched when the plan has one (planOneWave)
 };
 
 // The one-wave kernel of a model and mode.  `wantStride`: as fsmc_ctx::betaStride (the context's setting or the
@@ -486,6 +512,7 @@ KernelChoice chooseKernel(const fsmc_model* m, int mode, bool track, bool dual, 
 #define FSMC_PICK_CASE(KTX)                                                                                             \
   case KTX:                                                                                                            \
     k.fn = pickMember<KTX>(mode, track, m->sequence, half, dual);                                                      \
+    k.poolFn = (dual || m->sequence) ? nullptr : pickPoolMember<KTX>(mode, track, half);                               \
     break;
     FSMC_ALL_KT(FSMC_PICK_CASE)
     FSMC_EXACT_KT(FSMC_PICK_CASE)
@@ -594,7 +621,11 @@ struct LaunchPlan {
   size_t wsSlot = 0; // float4 per slot
   int slots = 0;
   int wavesPerWindow = 1; // 2: the two-waves-per-window kernel, a workgroup per slot
-  size_t bytes = 0;       // of workspace: wsSlot float4 for every slot
+  size_t bytes = 0;       // of workspace: wsSlot float4 for every slot, and the pool behind them
+  // The resident chunk buffers as a pool behind the slots (poolBuffers == 0: each slot holds its own, the static layout)
+  size_t poolOff = 0;       // float4 from the workspace's start to the pool: wsSlot x the slots planned
+  uint32_t poolBuffers = 0; // slots x residentChunks buffers of chunkRows rows
+  int poolCap = 0;          // the chunks of a window below this index ask for a buffer
 };
 
 // What a decode may spend on its workspace.
@@ -720,7 +751,9 @@ int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const Kernel
     return FSMC_EHIP;
   }
   const bool w2 = waveGroups(mode, m); // a workgroup of four waves takes a group, lane = pair
-  const size_t slots = std::max<size_t>(1, std::min((size_t)ctx->nCU * std::max(perCU, 1), list.size()));
+  // (diagnostic: FSMC_DIAG_MAX_SLOTS=<n> caps the resident waves -- tests: a short list that runs several rounds)
+  const size_t slots = loweredByEnv(
+      "FSMC_DIAG_MAX_SLOTS", std::max<size_t>(1, std::min((size_t)ctx->nCU * std::max(perCU, 1), list.size())));
   size_t L = 1;
   for (const fsmc_group& g : list) {
     const size_t aEnd = (mode == kModeIbd) ? g.scan_to : g.to;
@@ -773,28 +806,55 @@ int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const Kernel
   // lane-per-pair family, one group per wave -- the paired kernel is not built with them -- and of the wave-group kernel's
   // four-wave members).
   size_t resident = 0;
-  if (maxChunks > 1 && (mode == kModeIbd || mode == kModeSums) && !m->sequence && !paired && !anyStates(m) &&
-      (!w2 || w2ResidentBuilt(m->w2NW, false)) &&
-      ctx->residentChunks != 0) {
-    const size_t rowsBudget = rowsSoft;
-    // (exactly the rows of plan.wsSlot below: a plan must qualify again for the buffer it was given -- with a row of
-    //  slack here a context whose soft budget is the buffer it holds lost one resident chunk at its next launch)
-    const size_t fixed = chunkRows(C) + maxChunks + sideRows;
-    if (rowsBudget > fixed) {
-      resident = std::min<size_t>((rowsBudget - fixed) / chunkRows(C), maxChunks);
-      if (ctx->residentChunks > 0) {
-        resident = std::min<size_t>(resident, (size_t)ctx->residentChunks);
-      }
+  const size_t rowsBudget = rowsSoft;
+  // (exactly the rows of plan.wsSlot below: a plan must qualify again for the buffer it was given -- with a row of
+  //  slack here a context whose soft budget is the buffer it holds lost one resident chunk at its next launch)
+  const size_t fixed = chunkRows(C) + maxChunks + sideRows;
+  const bool residentBuilt = maxChunks > 1 && (mode == kModeIbd || mode == kModeSums) && !m->sequence && !paired &&
+                             !anyStates(m) && (!w2 || w2ResidentBuilt(m->w2NW, false));
+  if (residentBuilt && ctx->residentChunks != 0 && rowsBudget > fixed) {
+    resident = std::min<size_t>((rowsBudget - fixed) / chunkRows(C), maxChunks);
+    if (ctx->residentChunks > 0) {
+      resident = std::min<size_t>(resident, (size_t)ctx->residentChunks);
     }
+  }
+  // The pool (the kernels built with it: KernelChoice::poolFn): the same buffers, slots x resident of them, behind
+  // the slots instead of inside them, claimed by whichever wave has rows to keep.  A wave holds rows from the end of its pass B to the start of its
+  // pass A only, so a launch whose waves are spread over their groups -- one that runs several rounds -- keeps more
+  // chunks in the same memory.  Taken when the count is left to the library and is neither nothing nor everything, and
+  // the launch is an IBD decode of more than two rounds of groups -- what was measured (C2: 3.8 rounds).  One round has
+  // nobody to share with (a sums launch is always one: its batches run side by side, whatever the list holds), and in a
+  // launch of two rounds every wave's first group runs in phase with all the others; both keep the static layout, and
+  // so do the sums, until a measurement says otherwise.  A slot gains one row, the table of its window's chunks (a
+  // 32-bit entry each): where that row costs the last buffer, the plan has one buffer less a wave; it never exceeds the
+  // budget the static plan was given.  A window asks for a buffer for its first poolCap chunks: phi x its share.
+  size_t poolResident = 0;
+  if (residentBuilt && !w2 && k.poolFn && ctx->chunkPool != 0 && ctx->residentChunks < 0 &&
+      resident > 0 && resident < maxChunks && (ctx->chunkPool == 1 || (mode == kModeIbd && list.size() > 2 * slots)) &&
+      maxChunks * sizeof(int32_t) <= vecBytes && rowsBudget > fixed + 1) {
+    poolResident = std::min((rowsBudget - fixed - 1) / chunkRows(C), resident);
   }
   plan.chunk = (int)C;
   plan.chunkRows = (int)chunkRows(C);
   plan.maxChunks = (int)maxChunks;
-  plan.residentChunks = (int)resident;
-  plan.wsSlot = (chunkRows(C) * (1 + resident) + maxChunks + 2 + (sideRows - 2)) * K4 * kWave;
   plan.slots = (int)slots;
   plan.k = k;
   plan.wavesPerWindow = 1;
+  if (poolResident > 0 && slots * poolResident < (1u << 30)) {
+    const size_t want = ((size_t)ctx->chunkPoolPhi * poolResident + 99) / 100;
+    plan.residentChunks = (int)poolResident;
+    plan.wsSlot = (chunkRows(C) + maxChunks + 2 + (sideRows - 2) + 1) * K4 * kWave;
+    plan.poolOff = plan.wsSlot * slots;
+    plan.poolBuffers = (uint32_t)(slots * poolResident);
+    plan.poolCap = (int)std::min(maxChunks, std::max<size_t>(want, 1));
+    plan.bytes = (plan.poolOff + (size_t)plan.poolBuffers * chunkRows(C) * K4 * kWave) * sizeof(float4);
+    return FSMC_OK;
+  }
+  plan.residentChunks = (int)resident;
+  plan.wsSlot = (chunkRows(C) * (1 + resident) + maxChunks + 2 + (sideRows - 2)) * K4 * kWave;
+  plan.poolOff = 0;
+  plan.poolBuffers = 0;
+  plan.poolCap = 0;
   plan.bytes = plan.wsSlot * sizeof(float4) * slots;
   return FSMC_OK;
 }
@@ -922,7 +982,13 @@ int planAndHold(fsmc_ctx* ctx, const fsmc_model* m, int mode, const KernelChoice
 {
   std::string why;
   const int rc = planOneWave(ctx, m, mode, k, list, paired, workspaceBudget(ctx, buf), share, plan, why);
-  return rc != FSMC_OK ? fail(ctx, rc, why) : holdWorkspace(ctx, buf, plan.bytes);
+  if (rc != FSMC_OK) {
+    return fail(ctx, rc, why);
+  }
+  if (plan.poolBuffers) { // the pool's cursor, counters and claim words
+    FSMC_TRY(ensure(ctx, ctx->poolState, (kPoolClaims + (size_t)plan.poolBuffers) * sizeof(unsigned)));
+  }
+  return holdWorkspace(ctx, buf, plan.bytes);
 }
 
 // The launch the getters describe (fsmc_ctx_last_kernel, _last_beta_stride, _last_plan, _last_resident_chunks,
@@ -935,6 +1001,7 @@ void recordLaunch(fsmc_ctx* ctx, const KernelChoice& k, const LaunchPlan& plan, 
   ctx->lastChunk = plan.chunk;
   ctx->lastMaxChunks = plan.maxChunks;
   ctx->lastResident = plan.residentChunks;
+  ctx->lastPoolBuffers = plan.poolBuffers;
   ctx->lastWavesPerWindow = plan.wavesPerWindow;
   ctx->lastSlots = plan.slots + slotsBeside;
 }
@@ -1029,18 +1096,60 @@ int checkWorkspace(fsmc_ctx* ctx, const KParams& p, int slots)
   return FSMC_OK;
 }
 
+// The parameters of decode_kernel_pool for a plan with a pool: `p` and the pool's place.  Checked like the slots: every
+// buffer lies behind them, inside the workspace, and has its claim word.
+int poolParams(fsmc_ctx* ctx, const KernelChoice& k, const KParams& p, const LaunchPlan& plan, int slots, KParamsPool& pp)
+{
+  static_cast<KParams&>(pp) = p;
+  pp.poolOff = plan.poolOff;
+  pp.poolBuffers = plan.poolBuffers;
+  pp.poolCap = plan.poolCap;
+  pp.poolState = (unsigned*)ctx->poolState.p;
+  const DevBuf& buf = p.ws == (float4*)ctx->wsSide.p ? ctx->wsSide : ctx->ws;
+  const size_t rowF4 = (size_t)((p.K + 3) / 4) * kWave; // (at most the member's: a lower bound is checked)
+  const size_t poolF4 = (size_t)pp.poolBuffers * (size_t)p.chunkRows * rowF4;
+  if (!k.poolFn || pp.poolOff < p.wsSlot * (size_t)slots || buf.bytes / sizeof(float4) < pp.poolOff ||
+      buf.bytes / sizeof(float4) - pp.poolOff < poolF4 || !pp.poolState ||
+      ctx->poolState.bytes / sizeof(unsigned) < kPoolClaims + (size_t)pp.poolBuffers || pp.poolCap < 1 ||
+      pp.poolCap > p.maxChunks) {
+    return fail(ctx, FSMC_ESTATE, "the workspace does not hold the chunk pool planned for it");
+  }
+  return FSMC_OK;
+}
+
+// The pool's state starts every launch from zero: cursor, counters, every buffer free.
+int resetPool(fsmc_ctx* ctx, const KParamsPool& pp)
+{
+  FSMC_HIP(ctx, hipMemsetAsync(pp.poolState, 0, (kPoolClaims + (size_t)pp.poolBuffers) * sizeof(unsigned), ctx->stream));
+  return FSMC_OK;
+}
+
 // `continues`: a later launch of one call's sequence (the sums' batches, `slots` a launch): the timed span started with
 // the first one and ends behind the last (fsmc_last_kernel_ms: the whole sequence, its plane additions included).
-int launch(fsmc_ctx* ctx, const KernelChoice& k, const KParams& p, int slots, size_t dynLds = 0, bool continues = false)
+// `plan`: the launch's plan where it may hold a chunk pool -- decode_kernel_pool then runs in decode_kernel's place.
+int launch(fsmc_ctx* ctx, const KernelChoice& k, const KParams& p, int slots, size_t dynLds = 0, bool continues = false,
+           const LaunchPlan* plan = nullptr)
 {
   if (checkWorkspace(ctx, p, slots) != FSMC_OK) {
     return FSMC_ESTATE;
   }
+  const bool pool = plan && plan->poolBuffers != 0;
+  KParamsPool pp;
+  if (pool) {
+    FSMC_TRY(poolParams(ctx, k, p, *plan, slots, pp));
+  }
   FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
+  if (pool) {
+    FSMC_TRY(resetPool(ctx, pp));
+  }
   if (!continues) {
     FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   }
-  hipLaunchKernelGGL(k.fn, dim3((unsigned)slots), dim3(k.threads), dynLds, ctx->stream, p);
+  if (pool) {
+    hipLaunchKernelGGL(k.poolFn, dim3((unsigned)slots), dim3(k.threads), dynLds, ctx->stream, pp);
+  } else {
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)slots), dim3(k.threads), dynLds, ctx->stream, p);
+  }
   FSMC_HIP(ctx, hipGetLastError());
   FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = true;
@@ -1050,19 +1159,32 @@ int launch(fsmc_ctx* ctx, const KernelChoice& k, const KParams& p, int slots, si
 // One decode as two kernels side by side: `pSide` (one group per wave; the long windows, so it starts first) on the
 // side stream and `pMain` (two half-groups per wave) on the context's stream.  They share the record buffer and its
 // counter and have a queue head each; the timed span covers both.
-int launchBeside(fsmc_ctx* ctx, const KernelChoice& kSide, KParams& pSide, int slotsSide, const KernelChoice& kMain,
-                 KParams& pMain, int slotsMain)
+// `planSide`: the side kernel's plan, which may hold a chunk pool (the paired kernel keeps no resident chunks).
+int launchBeside(fsmc_ctx* ctx, const KernelChoice& kSide, KParams& pSide, int slotsSide, const LaunchPlan& planSide,
+                 const KernelChoice& kMain, KParams& pMain, int slotsMain)
 {
   if (checkWorkspace(ctx, pSide, slotsSide) != FSMC_OK || checkWorkspace(ctx, pMain, slotsMain) != FSMC_OK) {
     return FSMC_ESTATE;
   }
+  pMain.groupBase = 0;
+  pSide.groupBase = 2;
+  const bool pool = planSide.poolBuffers != 0;
+  KParamsPool ppSide;
+  if (pool) {
+    FSMC_TRY(poolParams(ctx, kSide, pSide, planSide, slotsSide, ppSide));
+  }
   FSMC_HIP(ctx, hipMemsetAsync(ctx->dCounters, 0, 4 * sizeof(unsigned), ctx->stream));
+  if (pool) {
+    FSMC_TRY(resetPool(ctx, ppSide));
+  }
   FSMC_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   FSMC_HIP(ctx, hipEventRecord(ctx->evFork, ctx->stream));
   FSMC_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->evFork, 0));
-  pMain.groupBase = 0;
-  pSide.groupBase = 2;
-  hipLaunchKernelGGL(kSide.fn, dim3((unsigned)slotsSide), dim3(kSide.threads), 0, ctx->side, pSide);
+  if (pool) {
+    hipLaunchKernelGGL(kSide.poolFn, dim3((unsigned)slotsSide), dim3(kSide.threads), 0, ctx->side, ppSide);
+  } else {
+    hipLaunchKernelGGL(kSide.fn, dim3((unsigned)slotsSide), dim3(kSide.threads), 0, ctx->side, pSide);
+  }
   FSMC_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(kMain.fn, dim3((unsigned)slotsMain), dim3(kMain.threads), 0, ctx->stream, pMain);
   FSMC_HIP(ctx, hipGetLastError());
@@ -1548,6 +1670,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->dItems) (void)hipFree(ctx->dItems);
   if (ctx->dRest) (void)hipFree(ctx->dRest);
   if (ctx->dCounters) (void)hipFree(ctx->dCounters);
+  if (ctx->poolState.p) (void)hipFree(ctx->poolState.p);
   if (ctx->dPhase) (void)hipFree(ctx->dPhase);
   if (ctx->idStash.p) (void)hipFree(ctx->idStash.p);
   if (ctx->ws.p) (void)hipFree(ctx->ws.p);
@@ -1682,6 +1805,46 @@ int fsmc_ctx_last_resident_chunks(const fsmc_ctx* ctx, int32_t* chunks)
     return FSMC_EINVAL;
   }
   *chunks = ctx->lastResident;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_set_chunk_pool(fsmc_ctx* ctx, int32_t mode, uint32_t phi_percent)
+{
+  if (!ctx || mode < -1 || mode > 1) {
+    return fail(ctx, FSMC_EINVAL, "chunk pool: -1 (automatic), 0 (never) or 1 (also in launches of one or two rounds and the sums)");
+  }
+  if (phi_percent != 0 && (phi_percent < 100 || phi_percent > 100000)) {
+    return fail(ctx, FSMC_EINVAL, "chunk pool: phi is 100 ... 100000 per cent of a wave's share (0: the default)");
+  }
+  ctx->chunkPool = mode;
+  ctx->chunkPoolPhi = phi_percent ? phi_percent : kChunkPoolPhiDefault;
+  return FSMC_OK;
+}
+
+int fsmc_ctx_last_chunk_pool(fsmc_ctx* ctx, uint32_t* buffers, uint32_t* kept, uint32_t* rebuilt, uint32_t* outstanding)
+{
+  if (!ctx) {
+    return FSMC_EINVAL;
+  }
+  uint32_t k = 0, r = 0, o = 0;
+  if (ctx->lastPoolBuffers) {
+    FSMC_HIP(ctx, hipSetDevice(ctx->device));
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<unsigned> st(kPoolClaims + (size_t)ctx->lastPoolBuffers);
+    if (!ctx->poolState.p || ctx->poolState.bytes < st.size() * sizeof(unsigned)) {
+      return fail(ctx, FSMC_ESTATE, "the chunk pool's state is gone");
+    }
+    FSMC_HIP(ctx, hipMemcpy(st.data(), ctx->poolState.p, st.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    k = st[kPoolKept];
+    r = st[kPoolRebuilt];
+    for (size_t i = kPoolClaims; i < st.size(); ++i) {
+      o += st[i] != 0u;
+    }
+  }
+  if (buffers) *buffers = ctx->lastPoolBuffers;
+  if (kept) *kept = k;
+  if (rebuilt) *rebuilt = r;
+  if (outstanding) *outstanding = o;
   return FSMC_OK;
 }
 
@@ -2214,8 +2377,9 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
     }
   }
   ctx->lastSpsLds = spsLdsBytes != 0;
-  rc = beside ? launchBeside(ctx, k, p, plan.slots, kDual, pDual, planDual.slots)
-              : q.dual ? launch(ctx, kDual, pDual, planDual.slots) : launch(ctx, k, p, plan.slots, spsLdsBytes);
+  rc = beside ? launchBeside(ctx, k, p, plan.slots, plan, kDual, pDual, planDual.slots)
+              : q.dual ? launch(ctx, kDual, pDual, planDual.slots)
+                       : launch(ctx, k, p, plan.slots, spsLdsBytes, false, &plan);
   if (rc != FSMC_OK) {
     return rc;
   }
@@ -3377,7 +3541,7 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   for (size_t base = 0; base < n_batches; base += slots) {
     const size_t n = std::min(slots, n_batches - base);
     p.groupBase = (int)base;
-    rc = launch(ctx, plan.k, p, (int)n, 0, base != 0);
+    rc = launch(ctx, plan.k, p, (int)n, 0, base != 0, &plan);
     if (rc != FSMC_OK) {
       return rc;
     }

@@ -23,6 +23,11 @@ FSMC_DEFINE_KT_DUAL_HALF(FSMC_INSTANCE_KT)
 FSMC_KT_FWD_KERNELS(FSMC_DEFINE_KT_FWD, FSMC_INSTANCE_KT)
 // (behind those in turn: the forward kernels keep their places too)
 FSMC_KT_VITERBI_KERNELS(FSMC_DEFINE_KT_VITERBI, FSMC_INSTANCE_KT)
+// (and last of all the decode kernels with the chunk pool, of the members built with it)
+#if FSMC_INSTANCE_KT == 69 // (poolBuilt, fsmc_instances.h)
+static_assert(poolBuilt(FSMC_INSTANCE_KT), "the members built with the chunk pool: poolBuilt()");
+FSMC_KT_POOL_KERNELS(FSMC_DEFINE_KT_POOL, FSMC_INSTANCE_KT)
+#endif
 #elif defined(FSMC_INSTANCE_W2)
 #ifndef FSMC_INSTANCE_NW
 #define FSMC_INSTANCE_NW 4

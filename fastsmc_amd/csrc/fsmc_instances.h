@@ -106,6 +106,20 @@ constexpr bool halfSumsBuilt(const int KT)
 #define FSMC_DEFINE_KT_DUAL_HALF(KT)                                                                                   \
   template __global__ void decode_kernel<KT, kModeIbd, true, false, true, true>(const KParams);                      \
   template __global__ void decode_kernel<KT, kModeIbd, false, false, true, true>(const KParams);
+// The chunk pool (decode_kernel_pool<KT, MODE, TRACK, HALF>: the array-mode IBD decode and sums over pairs, one group per
+// wave, with the resident chunk buffers claimed from a pool -- fsmc_decode_kernel_body.h): kernels of their own beside
+// decode_kernel, which stays as it is without them, built for the 69-state member, where the pool was measured.
+constexpr bool poolBuilt(const int KT)
+{
+  return KT == 69;
+}
+#define FSMC_KT_POOL_KERNELS(X, KT)                                                                                    \
+  X(KT, kModeIbd, true, false) X(KT, kModeIbd, false, false) X(KT, kModeIbd, true, true) X(KT, kModeIbd, false, true)  \
+  X(KT, kModeSums, false, false) X(KT, kModeSums, false, true)
+#define FSMC_DECLARE_KT_POOL(KT, MODE, TRACK, HALF)                                                                    \
+  extern template __global__ void decode_kernel_pool<KT, MODE, TRACK, HALF>(const KParamsPool);
+#define FSMC_DEFINE_KT_POOL(KT, MODE, TRACK, HALF)                                                                     \
+  template __global__ void decode_kernel_pool<KT, MODE, TRACK, HALF>(const KParamsPool);
 // the forward sweep alone (fsmc_pair_loglik.h): array mode and sequence mode
 #define FSMC_KT_FWD_KERNELS(X, KT) X(KT, false) X(KT, true)
 #define FSMC_DECLARE_KT_FWD(KT, SEQ) extern template __global__ void forward_kernel<KT, SEQ>(const FwdParams);
@@ -154,6 +168,7 @@ FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 32) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 48) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 48)
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 64) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 64)
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 69) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 69)
+FSMC_KT_POOL_KERNELS(FSMC_DECLARE_KT_POOL, 69)
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 80) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 80)
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 96) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 96)
 FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, 112) FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, 112)

@@ -178,6 +178,18 @@ int fsmc_ctx_last_plan(const fsmc_ctx* ctx, int32_t* chunk_sites, int32_t* max_c
  * the context has earned: see fsmc_ctx_set_workspace_limit); 0: none; n: at most n.  Results do not depend on it. */
 int fsmc_ctx_set_resident_chunks(fsmc_ctx* ctx, int32_t chunks);
 int fsmc_ctx_last_resident_chunks(const fsmc_ctx* ctx, int32_t* chunks);
+/* The chunk pool.  Where the number of resident chunks is left to the library (-1 above) and is neither none nor all of
+ * them, the resident buffers of all waves of a launch form one pool: a wave claims a buffer for a chunk when its backward
+ * pass reaches it, rebuilds the chunk if none is free, and gives the buffer back once the forward sweep has passed the
+ * chunk.  The same memory then keeps more chunks, because the waves of a launch that runs several rounds do not hold
+ * their rows at the same time.  mode = -1 (default): in IBD launches with more than twice as many groups as resident
+ * waves; 0: never (every wave keeps its own buffers); 1: also in launches of one or two rounds and in the sums over pairs.  phi_percent: a window asks for a buffer for its first
+ * ceil(phi_percent / 100 x resident chunks) chunks (100 ... 100000, 0 = the default).  Results do not depend on any of it.
+ * fsmc_ctx_last_chunk_pool (after the launch has completed; it waits for the context's stream): the pool's buffers
+ * (0: the last launch kept the static layout), the chunks whose rows were kept and those that were rebuilt -- of the
+ * last kernel launch where a call makes several -- and the buffers still claimed, 0 after every launch. */
+int fsmc_ctx_set_chunk_pool(fsmc_ctx* ctx, int32_t mode, uint32_t phi_percent);
+int fsmc_ctx_last_chunk_pool(fsmc_ctx* ctx, uint32_t* buffers, uint32_t* kept, uint32_t* rebuilt, uint32_t* outstanding);
 /* Two half-groups per wavefront.  A group of at most 32 pairs (a hashing-mode batch of the reference's default size)
  * fills half a wave; with pairing = 1 (default) the IBD decode puts two such groups with nearby windows on one wave,
  * each lane still decoded over its own group's windows (results do not depend on it); half-full groups that find no

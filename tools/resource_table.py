@@ -60,6 +60,7 @@ def main():
     rows.sort(key=lambda r: r["kernel"])
     doc = {"lib_hash": hip_source_hash(), "flags": " ".join(HIPCC_FLAGS),
            "template_arguments": {"decode_kernel": "<KT, MODE (0 IBD, 1 dump, 2 per pair, 3 sums), TRACK, SEQ, HALF, DUAL>",
+                                  "decode_kernel_pool": "<KT, MODE, TRACK, HALF> (array mode, one group per wave, with the chunk pool)",
                                   "decode_kernel_w2": "<KH, MODE, TRACK, SEQ, NW>", "forward_kernel": "<KT, SEQ>", "viterbi_kernel": "<KT>"},
            "kernels": rows}
     json.dump(doc, open(out, "w"), indent=1)
