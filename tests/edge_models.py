@@ -6,8 +6,14 @@ arrays (``Context.create_model`` takes any tables) and returns ``(pm, bits, fold
 the oracle's own output that its regime is reached, so that a later change to a generator cannot quietly turn an
 edge test into a benign one; ``regime`` counts what the oracle produces.
 
-Plain helper module imported by the tests (tests/test_gpu_numeric_edges.py, tests/test_oracle_dense_edges.py)."""
+``dyadic_ties`` is the model of the Viterbi tie rules: its regime is asserted on the numpy restatement of the
+max-product sweep (tests/pair_viterbi_lists.py), since the oracle has no Viterbi.
+
+Plain helper module imported by the tests (tests/test_gpu_numeric_edges.py, tests/test_oracle_dense_edges.py,
+tests/pair_viterbi_lists.py, tests/pair_loglik_lists.py)."""
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 
@@ -211,3 +217,106 @@ def identical_and_complement_pairs(K):
         assert np.count_nonzero(recs["pair"] == pairs.index((a, b))) == 0, (a, b)
     assert np.count_nonzero(~np.isin(recs["pair"], [pairs.index(p) for p in copies + compl])) > 0
     return pm, bits, folded, pairs
+
+
+def _blocks(rng, K, values, n_blocks):
+    """[K] float32, constant over n_blocks runs of states (fewer where K is smaller) with random edges."""
+    edges = np.sort(rng.choice(np.arange(1, K), min(n_blocks - 1, K - 1), replace=False))
+    out = np.empty(K, np.float32)
+    lo = 0
+    for hi in list(edges) + [K]:
+        out[lo:hi] = rng.choice(values)
+        lo = hi
+    return out
+
+
+TIE_MINIMUM = 1000  # equal operands at each of the step's comparisons (dyadic_ties)
+
+
+def dyadic_ties(K, S=129, seed=1, dead_top=False, regime=None):
+    """Bitwise ties at every comparison of the max-product sweep (csrc/fsmc_pair_viterbi.h): every number of the model is
+    a power of two (or 0) and constant over blocks of states -- pi = 2^-7; per site e1 in {1/4, 1/2, 1}, e0m1 in {0, 1/4,
+    1/2}, e2m0 in {0, 1/4} over about five blocks whose edges are drawn afresh for every site (no multiple of 4 or 16 is
+    preferred), where e0m1 and e2m0 keep a drawn value only where the class's emission (e1, e1 + e0m1, e1 + e0m1 + e2m0)
+    stays a power of two and are 0 elsewhere; per table row D, B, U in {1/8, 1/4, 1/2} and the column ratios in {1/2, 1}
+    over three blocks; RR[i] = U[i] cR[i+1] / U[i+1], exact for these values, so that the row-ratio form describes the
+    same matrix (dense_reference.dense_T asserts it); the last column of B, U, RR and the column ratios stays 0 as in
+    every model.  States of a block carry bitwise-equal values, products with powers of two are exact, and equal values
+    through equal operations stay equal after the 1 / sum scaling: the ties survive every site.  And since the scaling
+    factor is common to the states of a pair and commutes with a power of two, two states of a site either tie exactly or
+    differ by a factor of two at least, in fp32 and in fp64 alike: the restatement's path is the dense fp64 Viterbi's for
+    every pair.  (With emissions like 3/4 a product is rounded, two paths that take the same factors in another order
+    differ in the last bit, differently in the two precisions, and a third of the sampled paths differed from the dense
+    ones at equal probability.)  With ``dead_top`` the emissions of states K-2 and K-1 are exactly 0 at every site: their
+    values are +0 like those of the ghost states a padded member has above them.
+
+    70 pairs of 64 haplotypes.  Asserted on the restatement: at least TIE_MINIMUM bitwise-equal operands at each of the
+    step's comparisons that pair_viterbi_lists.tie_rules(K) names; at the final argmax, which compares K - 1 times a pair
+    and at one site only (TIE_MINIMUM is out of reach there: 140 comparisons in all at three states), at least one equal
+    operand a pair on average; none at a comparison tie_rules(K) does not name.  How many ties a seed gives at the final
+    argmax depends on the last site alone and varies widely, so a seed that misses fails here and not quietly in a
+    test.  ``regime``: a dict that receives the restatement's output ("viterbi") and its counter ("counts")."""
+    import pair_viterbi_lists as VL
+
+    pm, bits, folded = _prepare(K, _haps(S, False, 100 + K + S), False)
+    rng = np.random.default_rng(seed)
+    pm.pi = np.full(K, np.float32(2.0 ** -7), np.float32)
+    for pos in range(S):
+        e1 = _blocks(rng, K, [0.25, 0.5, 1.0], 5)
+        e0m1 = _blocks(rng, K, [0.0, 0.25, 0.5], 5)
+        e2m0 = _blocks(rng, K, [0.0, 0.25], 5)
+        # (each class's emission a power of two: e1, e1 + e0m1, e1 + e0m1 + e2m0)
+        e0m1 = np.where(e0m1 == e1, e0m1, np.float32(0.0))
+        e2m0 = np.where(e2m0 == e1 + e0m1, e2m0, np.float32(0.0))
+        pm.e1[pos], pm.e0m1[pos], pm.e2m0[pos] = e1, e0m1, e2m0
+    for r in range(pm.D.shape[0]):
+        for tab in (pm.D, pm.B, pm.U):
+            tab[r] = _blocks(rng, K, [0.125, 0.25, 0.5], 3)
+    pm.col_ratios[:] = _blocks(rng, K, [0.5, 1.0], 3)
+    pm.RR[:] = 0.0
+    pm.RR[:, :K - 2] = pm.U[:, :K - 2] * pm.col_ratios[None, 1:K - 1] / pm.U[:, 1:K - 1]
+    pm.B[:, K - 1] = pm.U[:, K - 1] = pm.col_ratios[K - 1] = 0.0
+    if dead_top:
+        for name in ("e1", "e0m1", "e2m0"):
+            getattr(pm, name)[:, K - 2:] = 0.0
+    pairs = O.enumerate_all_pairs(32)[37:37 + 70]
+    counts = VL.new_counts()
+    out = VL.viterbi(pm, folded, pairs, counts=counts)
+    mant, _ = VL.expected(out[1], out[2])
+    assert ((mant >= 0.5) & (mant < 1)).all(), "every pair has a finite, non-zero probability"
+    for name in VL.CONTRACT:
+        if name not in VL.tie_rules(K):
+            assert counts[name] == 0, (K, S, seed, dead_top, name, counts)
+        else:
+            assert counts[name] >= (len(pairs) if name == "last" else TIE_MINIMUM), (K, S, seed, dead_top, name, counts)
+    if regime is not None:
+        regime.update(viterbi=out, counts=counts)
+    return pm, bits, folded, pairs
+
+
+# ---------------------------------------------------------------- the edge models of the two pair sweeps
+
+# fsmc_decode_pair_loglik and fsmc_decode_pair_viterbi (forward_kernel, viterbi_kernel) at the edges above: every builder
+# whose edge is in the model or the haplotypes (threshold_equal's is in the scan, which the sweeps do not run), at an exact
+# member (69) and two padded ones (33 -> 48, 105 -> 112), 96 pairs = a full group and a half-full one; in sequence mode, which
+# only the forward kernel has, the two builders that have it, at 69 states.
+SWEEP_BUILDERS = {
+    "subnormal-1e-30": lambda K, seq: subnormal(K, 1e-30, seq),
+    "subnormal-1e-38": lambda K, seq: subnormal(K, 1e-38, seq),
+    "zero-states": lambda K, seq: zero_states(K),
+    "degenerate": lambda K, seq: degenerate(K, seq),
+    "identical-complement": lambda K, seq: identical_and_complement_pairs(K),
+}
+SWEEP_CASES = [(name, K, False) for K in (69, 33, 105) for name in SWEEP_BUILDERS]
+SWEEP_SEQ_CASES = [("subnormal-1e-30", 69, True), ("degenerate", 69, True)]
+
+
+def sweep_id(case):
+    return f"{case[0]}-K{case[1]}{'-seq' if case[2] else ''}"
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_model(name, K, seq=False):
+    """(pm, bits, folded, pairs) of a builder, built once a process and shared by the tests of both sweeps: read-only."""
+    assert (name, K, seq) in SWEEP_CASES + SWEEP_SEQ_CASES
+    return SWEEP_BUILDERS[name](K, seq)

@@ -255,3 +255,17 @@ def zero_sum_problem():
         sums.setflags(write=False)
         _cache["zero"] = (pm, bits, folded, pairs, sums, mid)
     return _cache["zero"]
+
+
+def edge_case(name, K, seq=False):
+    """(pm, bits, folded, pairs, sums) of edge_models.sweep_model(name, K, seq): the restatement on a model at a numeric
+    edge, once a process and read-only."""
+    key = ("edge", name, K, seq)
+    if key not in _cache:
+        import edge_models as E
+
+        pm, bits, folded, pairs = E.sweep_model(name, K, seq)
+        sums, _ = forward(pm, folded, pairs)
+        sums.setflags(write=False)
+        _cache[key] = (pm, bits, folded, pairs, sums)
+    return _cache[key]

@@ -13,9 +13,13 @@ comparison per comparison, vectorised over the pairs (lanes are independent):
   expected(sums, last) -> (mant [n] float64, expo [n] int32): pair_loglik_lists.chain over the sums, then once more with
     `last`.
 The emission rows are pair_loglik_lists.forward's: (e1 + e0m1 * z) + e2m0 * t.
+_next_delta and viterbi take the five comparisons as `rules` (CONTRACT by default) and an optional counter of bitwise-equal
+operands, so that a test can show on the CPU which ties an input contains and that each one decides a path.
 
 The yardstick is a textbook Viterbi in float64 on the dense transition matrices of tests/dense_reference.py
 (dense_viterbi), and the joint log-probability of any path on the same matrices (dense_path_log_probability)."""
+import operator
+
 import numpy as np
 
 from fastsmc_amd import synth
@@ -27,7 +31,28 @@ from pair_common import cohort_pairs
 F32 = np.float32
 
 
-def _next_delta(pm, row, prev, em):
+# The five comparisons of the contract (the header of csrc/fsmc_pair_viterbi.h): with these, the smaller predecessor index
+# wins every tie.  `rules` below maps each name to the comparison that takes its place (a function of two float32
+# arrays, first operand as the contract writes it); tests/test_pair_viterbi_lists.py flips one at a time to show that an
+# input tells the two apart.
+CONTRACT = {"suffix": operator.ge, "carry": operator.ge, "diag": operator.gt, "lower": operator.gt, "last": operator.gt}
+FLIPPED = {operator.ge: operator.gt, operator.gt: operator.ge}
+TINY = np.finfo(F32).tiny
+
+
+def new_counts():
+    """A counter for _next_delta / viterbi: per comparison, how often its two operands were bitwise equal (the suffix
+    comparison at k = 0 decides nothing that is read and is not counted), and under "subnormal" how many values of the
+    vectors v and delta were subnormal."""
+    return dict.fromkeys(tuple(CONTRACT) + ("subnormal",), 0)
+
+
+def _equal(counts, name, a, b):
+    if counts is not None:
+        counts[name] += int(np.count_nonzero(a == b))
+
+
+def _next_delta(pm, row, prev, em, rules=CONTRACT, counts=None):
     """One max-product step: prev, em [n][K] float32 -> (v [n][K] float32, psi [n][K] uint8)."""
     K = pm.K
     D, B, U, cR = pm.D[row], pm.B[row], pm.U[row], pm.col_ratios
@@ -37,7 +62,9 @@ def _next_delta(pm, row, prev, em):
     mC[:, K - 1] = prev[:, K - 1]
     cI[:, K - 1] = K - 1
     for k in range(K - 2, -1, -1):
-        ge = prev[:, k] >= mC[:, k + 1]
+        if k >= 1:
+            _equal(counts, "suffix", prev[:, k], mC[:, k + 1])
+        ge = rules["suffix"](prev[:, k], mC[:, k + 1])
         mC[:, k] = np.where(ge, prev[:, k], mC[:, k + 1])
         cI[:, k] = np.where(ge, k, cI[:, k + 1])
     v = np.empty_like(prev)
@@ -49,10 +76,12 @@ def _next_delta(pm, row, prev, em):
         if k >= 1:
             cand = U[k - 1] * prev[:, k - 1]
             car = cR[k - 1] * MU
-            ge = car >= cand
+            _equal(counts, "carry", car, cand)
+            ge = rules["carry"](car, cand)
             MU = np.where(ge, car, cand)
             uI = np.where(ge, uI, k - 1)
-            gd = d > MU
+            _equal(counts, "diag", d, MU)
+            gd = rules["diag"](d, MU)
             best = np.where(gd, d, MU)
             arg = np.where(gd, k, uI)
         else:
@@ -60,7 +89,8 @@ def _next_delta(pm, row, prev, em):
             arg = np.zeros(n, np.int32)
         if k < K - 1:
             l = B[k] * mC[:, k + 1]
-            gl = l > best
+            _equal(counts, "lower", l, best)
+            gl = rules["lower"](l, best)
             best = np.where(gl, l, best)
             arg = np.where(gl, cI[:, k + 1], arg)
         assert best.dtype == F32 and MU.dtype == F32
@@ -69,8 +99,9 @@ def _next_delta(pm, row, prev, em):
     return v, psi
 
 
-def viterbi(pm, folded, pairs):
-    """(states [n][S] uint8, sums [n][S] float32, last [n] float32) of `pairs` over the whole sequence, array mode."""
+def viterbi(pm, folded, pairs, rules=CONTRACT, counts=None):
+    """(states [n][S] uint8, sums [n][S] float32, last [n] float32) of `pairs` over the whole sequence, array mode.
+    `rules`: the comparisons, the contract's by default; `counts`: a new_counts() to fill, or None."""
     assert not pm.sequence and pm.K <= 128
     ob, hb = _pair_bits(folded, pairs)
     n, S, K = len(pairs), pm.S, pm.K
@@ -80,17 +111,25 @@ def viterbi(pm, folded, pairs):
     def emission(pos):
         return (pm.e1[pos][None, :] + pm.e0m1[pos][None, :] * z[:, pos, None]) + pm.e2m0[pos][None, :] * t[:, pos, None]
 
+    def subnormal(*vectors):
+        if counts is not None:
+            counts["subnormal"] += sum(int(np.count_nonzero((a > 0) & (a < TINY))) for a in vectors)
+
     sums = np.empty((n, S), F32)
     psi = np.zeros((S, n, K), np.uint8)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        sums[:, 0], delta = _sum_and_scale(pm.pi[None, :] * emission(0))
+        v = pm.pi[None, :] * emission(0)
+        sums[:, 0], delta = _sum_and_scale(v)
+        subnormal(v, delta)
         for pos in range(1, S):
-            v, psi[pos] = _next_delta(pm, int(pm.step_row[pos]), delta, emission(pos))
+            v, psi[pos] = _next_delta(pm, int(pm.step_row[pos]), delta, emission(pos), rules, counts)
             sums[:, pos], delta = _sum_and_scale(v)
+            subnormal(v, delta)
         best = delta[:, 0].copy()
         x = np.zeros(n, np.int64)
         for k in range(1, K):
-            gt = delta[:, k] > best
+            _equal(counts, "last", delta[:, k], best)
+            gt = rules["last"](delta[:, k], best)
             best = np.where(gt, delta[:, k], best)
             x = np.where(gt, k, x)
     assert best.dtype == F32
@@ -220,11 +259,60 @@ def planned(S, member, waves_wanted, limit):
     return c, -(-S // c), waves
 
 
+# the tie cases (edge_models.dyadic_ties: states in blocks of bitwise-equal values, so that every comparison of the
+# contract meets equal operands): name -> (K, S, seed, dead_top); 70 pairs each.  69 is an exact member, 33 and 105 are
+# padded (to 48 and 112: ghost states at +0 above the model, which `dead` real states tie with), 128 the top of the family,
+# 3 and 2 the smallest; 300 sites for the chunked runs.  The seeds are ones at which the builder's own assertion holds and
+# every comparison decides a path (tests/test_pair_viterbi_lists.py): with every seed tried the step's four do at 33 states
+# and more; the final argmax's ties depend on the last site alone, and at two and three states about half the seeds have
+# none.
+TIE_CASES = {
+    "ties-K69": (69, 129, 2, False),
+    "ties-K33": (33, 129, 4, False),
+    "ties-K105": (105, 129, 3, False),
+    "ties-K128": (128, 129, 2, False),
+    "ties-K3": (3, 129, 8, False),
+    "ties-K2": (2, 129, 7, False),
+    "ties-K33-dead": (33, 129, 4, True),
+    "ties-K105-dead": (105, 129, 3, True),
+    "ties-K69-S300": (69, 300, 3, False),
+}
+TIE_PAIRS = 70
+TIE_CHUNKED = "ties-K69-S300"
+CHUNKS_TIES = (16, 150, 0)  # chunk lengths of the GPU test on the 300-site tie case: 16 does not divide 300, 0 = automatic
+LIMIT_TIES = 1 << 20  # its workspace limit (two groups: two waves wanted)
+
+
+def tie_rules(K):
+    """The comparisons that can meet equal operands in a model of K states: all five, but for two states.  There no
+    suffix comparison is read (they are at k >= 1 and below K - 1), and the one carried MU is cR[0] * 0.f = +0 against
+    U[0] * p[0] > 0."""
+    return ("diag", "lower", "last") if K == 2 else tuple(CONTRACT)
+
+
 _cache = {}
+_counts = {}
+
+
+def tie_counts(name):
+    """The counter of the restatement's run on a tie case (new_counts())."""
+    case(name)
+    return _counts[name]
 
 
 def case(name):
     """(pm, bits, folded, pairs, states, sums, last) of a case; the restatement runs once a process and is read-only."""
+    if name not in _cache and name in TIE_CASES:
+        import edge_models as E
+
+        K, S, seed, dead_top = TIE_CASES[name]
+        regime = {}
+        pm, bits, folded, pairs = E.dyadic_ties(K, S, seed, dead_top, regime)
+        assert len(pairs) == TIE_PAIRS
+        out, _counts[name] = regime["viterbi"], regime["counts"]
+        for a in out:
+            a.setflags(write=False)
+        _cache[name] = (pm, bits, folded, pairs) + out
     if name not in _cache:
         K, S, n = CASES[name]
         if name in RICH:
@@ -256,3 +344,19 @@ def zero_sum_viterbi():
         pm, bits, folded, pairs, _, _ = zero_sum_problem()
         _cache["zero"] = (pm, bits, folded, pairs) + viterbi(pm, folded, pairs)
     return _cache["zero"]
+
+
+def edge_case(name, K):
+    """(pm, bits, folded, pairs, states, sums, last, counts) of edge_models.sweep_model(name, K): the restatement on a
+    model at a numeric edge with its counter (new_counts()), once a process and read-only."""
+    key = ("edge", name, K)
+    if key not in _cache:
+        import edge_models as E
+
+        pm, bits, folded, pairs = E.sweep_model(name, K, False)
+        counts = new_counts()
+        out = viterbi(pm, folded, pairs, counts=counts)
+        for a in out:
+            a.setflags(write=False)
+        _cache[key] = (pm, bits, folded, pairs) + out + (counts,)
+    return _cache[key]

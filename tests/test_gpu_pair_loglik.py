@@ -1,10 +1,12 @@
 """fsmc_decode_pair_loglik on the GPU: per pair, the likelihood of its observations from the forward sweep alone, as
 mantissa and exponent, over the whole sequence and over bins of sites.  Mantissas and exponents are np.array_equal to
 the numpy restatement of tests/pair_loglik_lists.py (tests/test_pair_loglik_lists.py shows on the CPU that the
-restatement is the oracle's forward sweep and what the inputs reach)."""
+restatement is the oracle's forward sweep and what the inputs reach).  The edge models (edge_models.SWEEP_CASES) are the
+numeric edges the decode kernels are tested at."""
 import numpy as np
 import pytest
 
+import edge_models as E
 import pair_loglik_lists as LL
 from conftest import expected_member
 from fastsmc_amd import api, capi
@@ -62,6 +64,22 @@ def test_models_sites_and_bins(name):
         _assert_equal(ctx.decode_pair_loglik(model, edges, want_total=False), (None, None) + want[2:],
                       f"{name} {ename}, bins alone")
     ctx.close()
+
+
+@pytest.mark.parametrize("case", E.SWEEP_CASES + E.SWEEP_SEQ_CASES, ids=E.sweep_id)
+def test_numeric_edges(case):
+    """The edge models of the decode kernels (subnormal table entries and vectors, states at exactly +0 beside the ghost
+    states, every state equal, identical and complementary haplotypes) at an exact and two padded members, and the two
+    sequence-mode ones at 69 states: all 96 pairs, two groups, bit for bit -- tests/test_pair_viterbi_lists.py shows that
+    every pair has a finite, non-zero likelihood."""
+    name, K, seq = case
+    pm, bits, _, pairs, sums = LL.edge_case(name, K, seq)
+    ctx, model = _open(pm, bits)
+    _upload(ctx, pm, pairs)
+    got = ctx.decode_pair_loglik(model)
+    assert ctx.last_kernel() == expected_member(K)
+    ctx.close()
+    _assert_equal(got, LL.expected(sums), E.sweep_id(case))
 
 
 @pytest.fixture

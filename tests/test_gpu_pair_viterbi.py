@@ -1,10 +1,13 @@
 """fsmc_decode_pair_viterbi on the GPU: per pair the most probable joint state sequence and its probability as mantissa
 and exponent.  States, mantissas and exponents are np.array_equal to the numpy restatement of
 tests/pair_viterbi_lists.py (tests/test_pair_viterbi_lists.py shows on the CPU that the restatement's paths are the dense
-fp64 Viterbi's and what the inputs reach)."""
+fp64 Viterbi's and what the inputs reach).  The tie cases (edge_models.dyadic_ties) pin the five comparisons of the
+contract: the same CPU tests show that each of them, flipped alone, changes a path of every tie case.  The edge models
+(edge_models.SWEEP_CASES) are the numeric edges the decode kernels are tested at."""
 import numpy as np
 import pytest
 
+import edge_models as E
 import pair_loglik_lists as LL
 import pair_viterbi_lists as VL
 from conftest import expected_member
@@ -72,6 +75,91 @@ def test_models_and_sites(name):
     ctx.close()
     assert (got[0] < pm.K).all()
     _assert_equal(got, _want(case), name)
+
+
+@pytest.mark.parametrize("name", list(VL.TIE_CASES))
+def test_tie_rules(name):
+    """States in blocks of bitwise-equal values: every comparison of the step and the final argmax meet equal operands
+    (thousands of times a case) and each one, taken the other way, changes a path.  Exact members, padded ones -- with
+    the two top states at +0 like the ghosts above them in the `dead` cases --, the largest and the two smallest."""
+    case = VL.case(name)
+    pm, bits, pairs = case[0], case[1], case[3]
+    ctx, model = _open(pm, bits)
+    _upload(ctx, pm, pairs)
+    got = ctx.decode_pair_viterbi(model)
+    assert ctx.last_kernel() == expected_member(pm.K)
+    info = ctx.info()
+    assert info["chunk_sites"] == pm.S and info["max_chunks"] == 1
+    ctx.close()
+    assert (got[0] < pm.K).all()
+    _assert_equal(got, _want(case), name)
+
+
+@pytest.fixture
+def ties300():
+    case = VL.case(VL.TIE_CHUNKED)
+    ctx, model = _open(case[0], case[1])
+    _upload(ctx, case[0], case[3])
+    yield ctx, model, case[0], _want(case)
+    ctx.close()
+
+
+def test_tie_rules_in_chunks(ties300):
+    """The 300-site tie case in chunks of 16 sites (a last chunk of 12), of 150 (two chunks) and automatic: sweep 2
+    rebuilds the back-pointers from a checkpoint and breaks the same ties the same way, and the traceback hands over
+    between chunks while the paths move through them."""
+    ctx, model, pm, want = ties300
+    for C in VL.CHUNKS_TIES:
+        ctx.set_chunk_sites(C)
+        got = ctx.decode_pair_viterbi(model)
+        info = ctx.info()
+        chunk = C if C else pm.S
+        assert info["chunk_sites"] == chunk and info["max_chunks"] == -(-pm.S // chunk), (C, info)
+        _assert_equal(got, want, f"chunk {C}")
+
+
+def test_tie_rules_under_a_workspace_limit(ties300):
+    """A megabyte of workspace for two waves' 1.4 MB of back-pointers each: the planner's four chunks of 75 sites."""
+    ctx, model, pm, want = ties300
+    ctx.set_workspace_limit(VL.LIMIT_TIES)
+    got = ctx.decode_pair_viterbi(model)
+    info = ctx.info()
+    chunk, chunks, waves = VL.planned(pm.S, 69, 2, VL.LIMIT_TIES)
+    assert (info["chunk_sites"], info["max_chunks"], info["n_slots"]) == (chunk, chunks, waves), info
+    assert chunks >= 2
+    _assert_equal(got, want, "a megabyte of workspace")
+
+
+def test_tie_rules_probabilities_alone_and_the_likelihood():
+    """Without states the probabilities take the same final tie; and on the same context one path stays below the sum
+    over all paths, which the forward kernel gives."""
+    case = VL.case("ties-K69")
+    pm, bits, pairs = case[0], case[1], case[3]
+    want = _want(case)
+    ctx, model = _open(pm, bits)
+    _upload(ctx, pm, pairs)
+    got = ctx.decode_pair_viterbi(model, want_states=False)
+    _assert_equal(got, (None,) + want[1:], "probabilities alone")
+    lm, le, _, _ = ctx.decode_pair_loglik(model)
+    ctx.close()
+    lp, ll = capi.log_likelihood(got[1], got[2]), capi.log_likelihood(lm, le)
+    assert (lp <= ll).all()
+
+
+@pytest.mark.parametrize("case", E.SWEEP_CASES, ids=E.sweep_id)
+def test_numeric_edges(case):
+    """The edge models of the decode kernels (subnormal table entries and vectors, states at exactly +0 beside the ghost
+    states, every state equal, identical and complementary haplotypes) at an exact and two padded members: all 96 pairs,
+    two groups, bit for bit -- tests/test_pair_viterbi_lists.py shows that every pair has a finite, non-zero probability."""
+    name, K, _ = case
+    pm, bits, _, pairs, states, sums, last, _ = VL.edge_case(name, K)
+    ctx, model = _open(pm, bits)
+    _upload(ctx, pm, pairs)
+    got = ctx.decode_pair_viterbi(model)
+    assert ctx.last_kernel() == expected_member(K)
+    ctx.close()
+    assert (got[0] < K).all()
+    _assert_equal(got, (states,) + VL.expected(sums, last), E.sweep_id(case))
 
 
 @pytest.fixture

@@ -4,6 +4,7 @@ forward to within fp32 rounding; and the inputs reach the regimes the GPU tests 
 import numpy as np
 import pytest
 
+import edge_models as E
 import pair_loglik_lists as LL
 from pair_common import EDGES_700
 
@@ -24,6 +25,24 @@ def test_restatement_is_the_oracles_forward_sweep(name):
     # the scaled vector of the last site sums to 1 give or take rounding: `sums` are the sums BEFORE the scaling
     assert np.allclose(alpha[pm.S - 1].sum(axis=0), 1.0, atol=1e-5)
     assert (sums > 0).all() and np.isfinite(sums).all()
+
+
+@pytest.mark.parametrize("case", E.SWEEP_CASES + E.SWEEP_SEQ_CASES, ids=E.sweep_id)
+def test_restatement_is_the_oracles_forward_sweep_at_the_edges(case):
+    """The edge models of tests/test_gpu_pair_loglik.py (subnormal table entries and vectors, states at exactly +0, every
+    state equal, identical and complementary haplotypes; array and sequence mode): the oracle's alphaFwd bit for bit,
+    subnormals and zeros included, and no zero sum, so that every pair has a likelihood to compare."""
+    name, K, seq = case
+    pm, _, folded, pairs, sums = LL.edge_case(name, K, seq)
+    again, alpha = LL.forward(pm, folded, pairs)
+    assert np.array_equal(again, sums)
+    assert np.array_equal(alpha, LL.oracle_alpha_fwd(pm, folded, pairs))
+    assert (sums > 0).all() and np.isfinite(sums).all()
+    tiny = np.finfo(np.float32).tiny
+    print(f"{E.sweep_id(case)}: {int(((alpha > 0) & (alpha < tiny)).sum())} subnormal and {int((alpha == 0).sum())} zero "
+          f"entries of alpha, smallest sum {sums.min():.3e}")
+    if name == "subnormal-1e-38":  # the forward vectors themselves carry subnormals, not only the tables
+        assert ((alpha > 0) & (alpha < tiny)).sum() > 100
 
 
 def test_restatement_on_the_cohort():
