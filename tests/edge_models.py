@@ -9,8 +9,13 @@ edge test into a benign one; ``regime`` counts what the oracle produces.
 ``dyadic_ties`` is the model of the Viterbi tie rules: its regime is asserted on the numpy restatement of the
 max-product sweep (tests/pair_viterbi_lists.py), since the oracle has no Viterbi.
 
+``degenerate_with_dead_states`` is the model of the quantile states' plateau rule (fsmc_decode_pair_cdf: the smallest k
+with cdf[k] >= q): equal posteriors put the running sum on the same value at thousands of cells, the exact zeros keep
+it there for a state.  tests/pair_edge_lists.py puts it and the subnormal, zero-state and degenerate builders through
+the five posterior-reducing decodePairs entry points.
+
 Plain helper module imported by the tests (tests/test_gpu_numeric_edges.py, tests/test_oracle_dense_edges.py,
-tests/pair_viterbi_lists.py, tests/pair_loglik_lists.py)."""
+tests/pair_viterbi_lists.py, tests/pair_loglik_lists.py, tests/pair_edge_lists.py)."""
 from __future__ import annotations
 
 import functools
@@ -153,6 +158,25 @@ def degenerate(K, seq=False):
         assert np.all(mp == 0)
     recs = O.decode_pairs_ibd(pm, folded, pairs, batch_size=64)
     assert recs.size > 0 and np.all(recs["map"] == pm.exp_times[0])
+    return pm, bits, folded, pairs
+
+
+def degenerate_with_dead_states(K, seq=False):
+    """``degenerate`` with the emissions of zero_states' states (1, K/2, K-2, K-1) exactly 0 at every site, in sequence
+    mode the homozygous row too: the running sum of a site's posterior over the states stands still on each of them,
+    at a value that thousands of cells share bitwise.  Dead states have posterior exactly +0, the live ones are bitwise
+    equal at every site, and the per-pair MAP is state 0 everywhere."""
+    pm, bits, folded, pairs = degenerate(K, seq)
+    dead = np.unique([1, K // 2, K - 2, K - 1])
+    for name in ("e1", "e0m1", "e2m0") + (("hom",) if seq else ()):
+        getattr(pm, name)[:, dead] = 0.0
+    live = np.setdiff1d(np.arange(K), dead)
+    for post, _, _ in oracle_posteriors(pm, folded, pairs):
+        d = post[:, dead]
+        assert np.all(d == 0) and not np.any(np.signbit(d)), "dead states: exactly +0"
+        assert np.all(post[:, live] > 0) and np.all(post[:, live] == post[:, :1]), "live states: equal and positive"
+        _, mp, _ = O.per_pair_output(pm, post, post.shape[2])
+        assert np.all(mp == 0)
     return pm, bits, folded, pairs
 
 

@@ -45,6 +45,20 @@ def problem(K, n_hap=64, S=200, seed=11):
     return pm, bits, folded
 
 
+def posterior_tables(pm, folded, pairs, acc=None):
+    """(rows [n][K][S], acc): the oracle's tables of `pairs`, its sum continued in `acc` (a new zero array if None)."""
+    acc = np.zeros((pm.K, pm.S), np.float32) if acc is None else acc
+    rows = []
+    for b0 in range(0, len(pairs), 64):
+        chunk = pairs[b0:b0 + 64]
+        ob = np.stack([folded[a] ^ folded[b] for a, b in chunk])
+        hb = np.stack([folded[a] & folded[b] for a, b in chunk])
+        post, _ = O.decode_batch(pm, ob, hb, 0, pm.S)
+        _, _, pp = O.per_pair_output(pm, post, len(chunk), want_post=True, sum_of_post=acc)
+        rows.append(pp)
+    return np.concatenate(rows), acc
+
+
 # ---------------------------------------------------------------- the product path: ASMC.decodePairs
 
 N_HAP, SITES, N_PAIRS = 64, 700, 200

@@ -14,25 +14,12 @@ import pytest
 from conftest import expected_member
 from fastsmc_amd import api, capi, synth
 from oracle import oracle as O
-from pair_common import (pairs_array as _pairs_array, problem as _problem, upload as _upload)
+from pair_common import (pairs_array as _pairs_array, posterior_tables as _oracle, problem as _problem,
+                         upload as _upload)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _oracle(pm, folded, pairs, acc=None):
-    """(rows [n][K][S], acc): the oracle's tables of `pairs`, its sum continued in `acc` (a new zero array if None)."""
-    acc = np.zeros((pm.K, pm.S), np.float32) if acc is None else acc
-    rows = []
-    for b0 in range(0, len(pairs), 64):
-        chunk = pairs[b0:b0 + 64]
-        ob = np.stack([folded[a] ^ folded[b] for a, b in chunk])
-        hb = np.stack([folded[a] & folded[b] for a, b in chunk])
-        post, _ = O.decode_batch(pm, ob, hb, 0, pm.S)
-        _, _, pp = O.per_pair_output(pm, post, len(chunk), want_post=True, sum_of_post=acc)
-        rows.append(pp)
-    return np.concatenate(rows), acc
 
 
 PAIRS_150 = O.enumerate_all_pairs(32)[100:100 + 150]  # three groups, the last with 22 pairs
