@@ -25,6 +25,7 @@
 #include "fsmc_pair_tail.h"
 #include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
+#include "fsmc_plan.h"
 
 namespace fsmc
 {
@@ -89,10 +90,7 @@ struct fsmc_ctx {
   int nCU = 0;
   uint64_t hbmBytes = 0;
   uint64_t wsLimit = 0;
-  double wsEarned = 0; // bytes of workspace the launches so far (and the announced job) have paid for and not yet
-                       // spent on an allocation (earnWorkspace, fsmc_ctx_expect_work, holdWorkspace)
-  double wsAnnounced = 0; // estimated kernel seconds of announced work not launched yet (it has earned already)
-  double wsAnnouncedCredit = 0; // ... and the bytes of credit that part of the announcement was given
+  plan::Credit credit; // what the launches and the announced job have earned for the workspace
   std::string err;
 
   unsigned long long* dHaps = nullptr;
@@ -129,13 +127,10 @@ struct fsmc_ctx {
   int lastMember = 0; // member of the last launch: KT of the lane-per-pair kernel; wave-group kernel: 1000 + KH (four waves of KH states), 1000 * NW + KH (NW = 5 ... 8 waves)
 
   // The queues an IBD decode's waves pull from (fsmc_decode_ibd_launch): built from the uploaded groups once per
-  // work list and budget, longest window first.
+  // work list and pairing, longest window first.
   struct IbdQueues {
     uint64_t serial = 0;  // work list they were built from
-    uint64_t maxLen = 0;  // pairing budgets they were built with: beside a second kernel ...
-    uint64_t maxLenAlone = 0; // ... and with the whole workspace (they move with the model member, the beta stride and
-                              // the workspace limit, not always together)
-    uint32_t pairing = 0;
+    bool pairing = false; // half-full groups were paired where they pair up (the setting, and a model it is built for)
     bool valid = false;
     bool dual = false;    // items/unions in use: two half-groups per wave
     bool reordered = false; // rest is in use (a reordered copy or subset of the uploaded groups)
@@ -389,44 +384,14 @@ bool waveGroups(int mode, const fsmc_model* m)
   return m->w2NW > 0 && (mode == kModeIbd || mode == kModeDump || mode == kModeSums || mode == kModePerPair);
 }
 
-// Member of the wave-group kernel for a model of K states: {waves per group, states per wave}.  Up to 320 states four
-// waves (48, 64: two workgroups per CU; 80: one, with the whole register file); beyond, six to eight waves of 64 states;
-// beyond 512 states eight waves of 80 / 96 / 128 states, which have no landing zones for the beta row (they would not
-// fit the CU's LDS) and hold part of their vectors in scratch memory (round 5: K = 600 0.03 -> 0.28 of the roofline).
-// (Three / four waves of 128 states for 321 ... 512 states were measured too: 1.5 x slower than six / eight of 64,
-// profiles/r05_w2_wide_members_of_128.txt.)
-// (Measured on the 600 x 3000 list, profiles/r04_wide_members_ab.txt: five waves of 64 are 6 % slower than four of 80
-// at 300 / 320 states; four waves of 96 / 112 states -- round 4's first members for 321 ... 448 states, which keep part
-// of their vectors in scratch memory -- 10 - 13 % slower than six / seven waves of 64.)
-struct W2Member {
-  int NW, KH;
-};
-W2Member w2Member(int K)
+// The members of the wave-group kernel the library is built with: {waves per group, states per wave}.  plan::w2Member
+// picks a model's; the diagnostic override may name any of these.
+const std::vector<plan::W2Member>& builtW2Members()
 {
-  // (diagnostic: FSMC_DIAG_W2_MEMBER="<waves>x<states per wave>" picks another member that holds the model -- A/B runs)
-  if (const char* v = std::getenv("FSMC_DIAG_W2_MEMBER")) {
-    int nw = 0, kh = 0;
-    // (a member whose waves the model fills all but the last of, or the 48-state one: where the kernel masks ghosts)
-    if (std::sscanf(v, "%dx%d", &nw, &kh) == 2 && nw * kh >= K &&
-        ((nw - 1) * kh < K || (kh == 48 && 2 * kh < K) || (nw * kh > 512 && (nw - 2) * kh < K))) {
-#define FSMC_IS_W2(KHX, NWX)                                                                                            \
-  if (kh == KHX && nw == NWX) {                                                                                        \
-    return {nw, kh};                                                                                                   \
-  }
-      FSMC_ALL_W2(FSMC_IS_W2)
-#undef FSMC_IS_W2
-    }
-  }
-  if (K <= 192) return {4, 48};
-  if (K <= 256) return {4, 64};
-  if (K <= 320) return {4, 80};
-  if (K <= 384) return {6, 64};
-  if (K <= 448) return {7, 64};
-  if (K <= 512) return {8, 64};
-  // beyond 512 states: eight waves without landing zones (fsmc_kernels_w2.h, LAND)
-  if (K <= 640) return {8, 80};
-  if (K <= 768) return {8, 96};
-  return {8, 128};
+#define FSMC_LIST_W2(KHX, NWX) {NWX, KHX},
+  static const std::vector<plan::W2Member> built = {FSMC_ALL_W2(FSMC_LIST_W2)};
+#undef FSMC_LIST_W2
+  return built;
 }
 
 template <int KH, int NW, bool SEQ> KernelFn pickWaveGroupKernelOf(int mode, bool track)
@@ -585,12 +550,66 @@ template <typename Params, typename Pick> SweepKernel<Params> chooseSweepKernel(
   return s;
 }
 
-// A diagnostic switch that lowers a count: NAME=<n> gives n / divisor where that is at least 1 and below `value`.
-size_t loweredByEnv(const char* name, size_t value, int divisor = 1)
+// An environment variable as a count, 0 where it is not set.
+long envCount(const char* name)
 {
   const char* s = std::getenv(name);
-  const long v = s ? std::atol(s) / divisor : 0;
-  return v >= 1 && (size_t)v < value ? (size_t)v : value;
+  return s ? std::atol(s) : 0;
+}
+
+// A diagnostic switch that lowers a count: NAME=<n> gives n where that is at least 1 and below `value`.
+size_t loweredByEnv(const char* name, size_t value)
+{
+  return plan::lowered(value, envCount(name));
+}
+
+// The planner's inputs (fsmc_plan.h decides, this file does): the diagnostic switches as the environment has them at
+// this call -- the tests change them between contexts --, the context's settings, and what the card has free.
+plan::Diag readDiag()
+{
+  plan::Diag d;
+  d.maxSlots = envCount("FSMC_DIAG_MAX_SLOTS");
+  d.wavesPerCU = envCount("FSMC_DIAG_WAVES_PER_CU");
+  d.sumsSlots = envCount("FSMC_DIAG_SUMS_SLOTS");
+  if (const char* v = std::getenv("FSMC_DIAG_WS_FREE")) {
+    d.wsFree = std::strtoull(v, nullptr, 10);
+  }
+  if (const char* v = std::getenv("FSMC_DIAG_WS_EARN_SCALE")) {
+    d.earnScale = std::atof(v);
+  }
+  if (const char* v = std::getenv("FSMC_DIAG_TWO_WAVE_WINDOWS")) {
+    d.twoWavesNever = std::strcmp(v, "never") == 0;
+  }
+  if (const char* v = std::getenv("FSMC_DIAG_W2_MEMBER")) {
+    int nw = 0, kh = 0;
+    if (std::sscanf(v, "%dx%d", &nw, &kh) == 2) {
+      d.w2NW = nw;
+      d.w2KH = kh;
+    }
+  }
+  return d;
+}
+
+plan::Settings settingsOf(const fsmc_ctx* ctx)
+{
+  plan::Settings s;
+  s.nCU = ctx->nCU;
+  s.hbmBytes = ctx->hbmBytes;
+  s.wsLimit = ctx->wsLimit;
+  s.chunkSites = ctx->chunkSites;
+  s.residentChunks = ctx->residentChunks;
+  s.chunkPool = ctx->chunkPool;
+  s.chunkPoolPhi = ctx->chunkPoolPhi;
+  return s;
+}
+
+plan::MemInfo memInfo()
+{
+  size_t freeB = 0, totalB = 0;
+  plan::MemInfo mem;
+  mem.known = hipMemGetInfo(&freeB, &totalB) == hipSuccess;
+  mem.freeBytes = (uint64_t)freeB;
+  return mem;
 }
 
 // Workgroups of a kernel that a CU holds at once, as the runtime counts them, `most` at the most.  `capDivisor` > 0:
@@ -604,138 +623,50 @@ hipError_t workgroupsPerCU(const KernelChoice& k, int most, int capDivisor, int&
     (void)hipGetLastError();
     return e;
   }
-  perCU = std::min(perCU, most);
-  if (capDivisor > 0) {
-    perCU = (int)loweredByEnv("FSMC_DIAG_WAVES_PER_CU", (size_t)std::max(perCU, 0), capDivisor);
-  }
+  perCU = plan::capWorkgroups(perCU, most, capDivisor, readDiag());
   return hipSuccess;
 }
 
-// A launch, self-describing: its kernel (chunkRows is computed for its beta stride), a slot's layout, slots, bytes.
-struct LaunchPlan {
+static_assert(plan::kWave == kWave && plan::kFloat4Bytes == sizeof(float4), "fsmc_plan.h lays rows out for the kernels' wave");
+
+// A launch: its plan (fsmc_plan.h) and the kernel it was planned for.
+struct LaunchPlan : plan::LaunchPlan {
   KernelChoice k;
-  int chunk = 0;
-  int chunkRows = 0; // rows of the chunk buffer (chunk, or half of it with beta stride 2)
-  int maxChunks = 0;
-  int residentChunks = 0; // chunk buffers beyond the first: chunks whose rows pass B keeps (no rebuild)
-  size_t wsSlot = 0; // float4 per slot
-  int slots = 0;
-  int wavesPerWindow = 1; // 2: the two-waves-per-window kernel, a workgroup per slot
-  size_t bytes = 0;       // of workspace: wsSlot float4 for every slot, and the pool behind them
-  // The resident chunk buffers as a pool behind the slots (poolBuffers == 0: each slot holds its own, the static layout)
-  size_t poolOff = 0;       // float4 from the workspace's start to the pool: wsSlot x the slots planned
-  uint32_t poolBuffers = 0; // slots x residentChunks buffers of chunkRows rows
-  int poolCap = 0;          // the chunks of a window below this index ask for a buffer
 };
 
-// What a decode may spend on its workspace.
-// The most it can have (`hard`): the caller's limit if one is set (fsmc_ctx_set_workspace_limit); otherwise 80 % of the
-// card where that much is free (the card has 288 GB; the model, the haplotypes and the records are small), at least 40 %.
-// What its plan may be UPGRADED with (`soft`) -- a window kept whole instead of chunked, resident chunks, longer windows
-// in the paired kernel: the same when the caller set a limit (the caller knows the job).  Otherwise memory has to be
-// earned: hipMalloc costs ~40 ms per GB on this driver (230 GB: 4.4-9 s; tools/malloc_cost.py), a rebuilt chunk costs a
-// few per cent of a launch, so a run of a few seconds must not start by allocating the card.  Every launch adds what
-// it is expected to save -- kEarnFraction of its estimated kernel time -- at the allocation rate; the buffer is kept
-// between launches, so a long job reaches the full card and a short one stays small.
-// A bigger buffer is a NEW allocation of its whole size (free + hipMalloc), so growth is amortised and every byte is
-// paid for once: an upgrade is considered only when the credit covers twice the buffer held (or the whole hard
-// budget), and an allocation is debited from the credit.  Creeping up a resident chunk per flush -- 16 allocations of
-// 27 ... 230 GB, 80 s of hipMalloc on a 390-s job -- is what this replaces.  A caller that knows its job announces it
-// (fsmc_ctx_expect_work: HMM::decodeAll knows its pair count, HMM.cpp:310-321): the credit of the whole job is there
-// at the first launch, and a job long enough to pay for the card allocates it once, at the start.
-// `cur`: the buffer about to be re-used (what it holds is paid for).
-constexpr double kAllocBytesPerSecond = 25e9; // measured: hipMalloc of 64 / 128 GB takes 2.4 / 5.2 s
-constexpr double kEarnFraction = 0.06;        // what resident chunks save of a chunked launch (C2: 1974 -> 1854 ms)
-constexpr uint64_t kFreeWorkspace = 24ull << 30; // never argued about (at most a second; only what a plan uses is allocated)
-
-struct WsBudget {
-  uint64_t hard, soft;
-};
-
-uint64_t freeWorkspace()
+// What a plan reads of kernel `k` of a model and mode; `perCU`: its workgroups a CU (workgroupsPerCU).
+plan::KernelTraits traitsOf(const fsmc_model* m, int mode, const KernelChoice& k, int perCU)
 {
-  if (const char* v = std::getenv("FSMC_DIAG_WS_FREE")) { // tests: make the policy visible on a small problem
-    return std::strtoull(v, nullptr, 10);
-  }
-  return kFreeWorkspace;
+  const bool w2 = waveGroups(mode, m); // a workgroup of four waves takes a group, lane = pair
+  const bool any = anyStates(m);
+  plan::KernelTraits t;
+  t.member = k.member;
+  t.stride = k.stride;
+  t.rowFloat4 = w2 ? (size_t)m->KP / 4 : (size_t)((k.member > 0 ? k.member : m->K) + 3) / 4 + (any ? 1 : 0);
+  t.sideRows = any ? (size_t)kAnyExtraRows + 2 : 4;
+  t.chunkFloor = w2 ? 2048 : 512;
+  t.resident = (mode == kModeIbd || mode == kModeSums) && !m->sequence && !any && (!w2 || w2ResidentBuilt(m->w2NW, false));
+  t.pool = !w2 && k.poolFn != nullptr;
+  t.perCU = perCU;
+  return t;
 }
 
-WsBudget workspaceBudget(const fsmc_ctx* ctx, const DevBuf& cur)
+// plan::workspaceBudget of the context as it is now.  `cur`: the buffer about to be re-used.
+plan::WsBudget workspaceBudget(const fsmc_ctx* ctx, const DevBuf& cur)
 {
-  size_t freeB = 0, totalB = 0;
-  const bool known = hipMemGetInfo(&freeB, &totalB) == hipSuccess;
-  const uint64_t reachable = (uint64_t)freeB + cur.bytes;
-  const uint64_t margin = (uint64_t)(0.04 * (double)ctx->hbmBytes);
-  if (ctx->wsLimit) {
-    // (a limit above what the card has free right now -- another process on it -- is cut to that, if it is at least
-    //  a quarter of the limit: below, the caller is told by the allocation failing)
-    uint64_t lim = ctx->wsLimit;
-    if (known && reachable > margin && reachable - margin < lim && reachable - margin >= lim / 4) {
-      lim = reachable - margin;
-    }
-    return {lim, lim};
-  }
-  const uint64_t floor40 = (uint64_t)(0.40 * (double)ctx->hbmBytes);
-  uint64_t hard = floor40;
-  if (known) {
-    const uint64_t want = (uint64_t)(0.80 * (double)ctx->hbmBytes);
-    hard = std::max<uint64_t>(floor40, std::min<uint64_t>(want, reachable > margin ? reachable - margin : 0));
-  }
-  uint64_t earned = (uint64_t)std::min(std::max(ctx->wsEarned, 0.0), 1e15);
-  if (earned < hard && earned < 2 * (uint64_t)cur.bytes) {
-    earned = 0; // (not yet worth a re-allocation: growth is geometric)
-  }
-  const uint64_t freeBytes = freeWorkspace();
-  const uint64_t soft = std::min<uint64_t>(hard, std::max<uint64_t>({(uint64_t)cur.bytes, earned, freeBytes}));
-  return {hard, soft};
+  return plan::workspaceBudget(settingsOf(ctx), ctx->credit, memInfo(), cur.bytes, readDiag());
 }
 
-// An allocation of the workspace under the earned policy is debited from the credit (beyond the free allowance).
-void payForWorkspace(fsmc_ctx* ctx, uint64_t allocatedBytes)
-{
-  if (ctx->wsLimit) {
-    return;
-  }
-  const uint64_t freeBytes = freeWorkspace();
-  if (allocatedBytes > freeBytes) {
-    ctx->wsEarned = std::max(0.0, ctx->wsEarned - (double)(allocatedBytes - freeBytes));
-  }
-}
-
-double earnScale()
-{
-  if (const char* v = std::getenv("FSMC_DIAG_WS_EARN_SCALE")) { // tests: a small problem that earns like a long job
-    return std::atof(v);
-  }
-  return 1.0;
-}
-
-// A launch over the uploaded work list earns workspace for this and the following launches: estimated kernel time =
-// algorithmic bytes at 80 % of the roofline.
+// A launch over the uploaded work list earns workspace for this and the following launches.
 void earnWorkspace(fsmc_ctx* ctx, const fsmc_model* m, int mode)
 {
-  double pairSites = 0;
-  for (const fsmc_group& g : ctx->hGroups) {
-    const uint32_t aEnd = (mode == kModeIbd) ? g.scan_to : g.to;
-    pairSites += (double)g.n_pairs * (double)(aEnd > g.from ? aEnd - g.from : 0);
-  }
-  double seconds = pairSites * (8.0 * m->K + 0.25) / (0.8 * 8e12);
-  // (work that was announced has earned already: fsmc_ctx_expect_work)
-  const double announced = std::min(ctx->wsAnnounced, seconds);
-  if (ctx->wsAnnounced > 0) {
-    ctx->wsAnnouncedCredit *= (ctx->wsAnnounced - announced) / ctx->wsAnnounced; // (that part is spent: it was launched)
-  }
-  ctx->wsAnnounced -= announced;
-  seconds -= announced;
-  ctx->wsEarned += earnScale() * kEarnFraction * seconds * kAllocBytesPerSecond;
+  plan::earnWorkspace(ctx->credit, ctx->hGroups, mode == kModeIbd, m->K, readDiag());
 }
 
-// Decide chunking of the beta stream and the number of resident waves of kernel `k` over `list`, the
-// groups its waves pull from.  `paired`: two half-groups per wave, `list` holding the union of each pair's windows.
-// `share`: the launch runs beside another one and may take 1/share of the budget.  Computes only: allocates nothing,
-// leaves the context as it is (holdWorkspace, recordLaunch).  `why`: the message of a status other than FSMC_OK.
+// plan::planOneWave for kernel `k` over `list`.  Computes only: allocates nothing, leaves the context as it is
+// (holdWorkspace, recordLaunch).  `why`: the message of a status other than FSMC_OK.
 int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const KernelChoice& k,
-                const std::vector<fsmc_group>& list, bool paired, const WsBudget& budget, unsigned share,
+                const std::vector<fsmc_group>& list, bool paired, const plan::WsBudget& budget, unsigned share,
                 LaunchPlan& plan, std::string& why)
 {
   if (!k.fn) {
@@ -750,124 +681,14 @@ int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const Kernel
     why = std::string("occupancy query of the decode kernel: ") + hipGetErrorString(e);
     return FSMC_EHIP;
   }
-  const bool w2 = waveGroups(mode, m); // a workgroup of four waves takes a group, lane = pair
-  // (diagnostic: FSMC_DIAG_MAX_SLOTS=<n> caps the resident waves -- tests: a short list that runs several rounds)
-  const size_t slots = loweredByEnv(
-      "FSMC_DIAG_MAX_SLOTS", std::max<size_t>(1, std::min((size_t)ctx->nCU * std::max(perCU, 1), list.size())));
-  size_t L = 1;
-  for (const fsmc_group& g : list) {
-    const size_t aEnd = (mode == kModeIbd) ? g.scan_to : g.to;
-    L = std::max<size_t>(L, aEnd - g.from);
-  }
-  // float4 per lane of a stored K-vector: a padded family member (and the wave-group kernel) stores its ghosts too
-  // (the any-K kernel, member 0, stores K states; its rows carry their scale in one more float4)
-  const size_t K4 = w2 ? (size_t)m->KP / 4 : (size_t)((k.member > 0 ? k.member : m->K) + 3) / 4 + (anyStates(m) ? 1 : 0);
-  const size_t vecBytes = K4 * kWave * sizeof(float4);
-  const uint64_t limit = budget.hard / share;
-  // Rows a chunk of C sites needs in the chunk buffer: with beta stride 2 only every second site's row is stored.
-  const bool half = k.stride == 2;
-  auto chunkRows = [&](size_t c) { return half ? (c + 1) / 2 : c; };
-  const size_t rowsAvail = (size_t)(limit / (vecBytes * slots)); // rows one resident wave may hold
-  const size_t rowsSoft = (size_t)(budget.soft / share / (vecBytes * slots)); // ... and may have earned so far
-  // rows beside the chunk buffer and the checkpoints: parking / segment sums; the any-K kernel keeps every vector there
-  const size_t sideRows = anyStates(m) ? (size_t)kAnyExtraRows + 2 : 4;
-  const size_t defaultChunk = std::max<size_t>((size_t)std::ceil(std::sqrt((double)L)), w2 ? 2048 : 512);
-  size_t C, maxChunks;
-  // A window stays whole if that fits what the launches have earned (or is no longer than a chunk would be anyway).
-  // An explicit chunk length (fsmc_ctx_set_chunk_sites) is kept -- by the paired kernel too, which has the chunked
-  // layout since round 3.
-  if (chunkRows(L) + sideRows + 1 <= rowsAvail && (chunkRows(L) + sideRows + 1 <= rowsSoft || L <= defaultChunk) &&
-      !(ctx->chunkSites && ctx->chunkSites < L)) {
-    C = L;
-    maxChunks = 1;
-  } else {
-    // The chunk length of a window that does not fit the workspace whole: 512 sites, or sqrt(window) if that is larger
-    // (memory is chunk + window / chunk rows), shrunk to what the workspace limit allows.  Short chunks cost a
-    // checkpoint row and a pipeline restart each and let the resident chunks (below) fill the memory that is left to
-    // the last row: C2 at 2048 / 1024 / 512 sites a chunk runs 1886 / 1881 / 1870 ms.
-    C = ctx->chunkSites ? (size_t)ctx->chunkSites : defaultChunk;
-    // (the wave-group kernel pays more per restart: 2048)
-    C = std::min((C + 15) / 16 * 16, (L + 15) / 16 * 16);
-    auto fits = [&](size_t c) { return chunkRows(c) + (L + c - 1) / c + sideRows + 1 <= rowsAvail; };
-    if (!ctx->chunkSites) {
-      while (C > 16 && !fits(C)) {
-        C = std::max<size_t>(16, (C / 2 + 15) / 16 * 16);
-      }
-    }
-    maxChunks = (L + C - 1) / C;
-    if (!fits(C)) {
-      why = "workspace limit too small for the decode window";
-      return FSMC_ENOMEM;
-    }
-  }
-  // Resident chunks (fsmc_kernels.h): a chunked window rebuilds every chunk's rows from a checkpoint -- one of its 3.5
-  // sweeps -- except for the chunks whose rows pass B can leave in the workspace.  Whatever the limit leaves after the
-  // one chunk buffer, the checkpoints and the parking rows goes to such chunks (array-mode IBD decode and sums of the
-  // lane-per-pair family, one group per wave -- the paired kernel is not built with them -- and of the wave-group kernel's
-  // four-wave members).
-  size_t resident = 0;
-  const size_t rowsBudget = rowsSoft;
-  // (exactly the rows of plan.wsSlot below: a plan must qualify again for the buffer it was given -- with a row of
-  //  slack here a context whose soft budget is the buffer it holds lost one resident chunk at its next launch)
-  const size_t fixed = chunkRows(C) + maxChunks + sideRows;
-  const bool residentBuilt = maxChunks > 1 && (mode == kModeIbd || mode == kModeSums) && !m->sequence && !paired &&
-                             !anyStates(m) && (!w2 || w2ResidentBuilt(m->w2NW, false));
-  if (residentBuilt && ctx->residentChunks != 0 && rowsBudget > fixed) {
-    resident = std::min<size_t>((rowsBudget - fixed) / chunkRows(C), maxChunks);
-    if (ctx->residentChunks > 0) {
-      resident = std::min<size_t>(resident, (size_t)ctx->residentChunks);
-    }
-  }
-  // The pool (the kernels built with it: KernelChoice::poolFn): the same buffers, slots x resident of them, behind
-  // the slots instead of inside them, claimed by whichever wave has rows to keep.  A wave holds rows from the end of its pass B to the start of its
-  // pass A only, so a launch whose waves are spread over their groups -- one that runs several rounds -- keeps more
-  // chunks in the same memory.  Taken when the count is left to the library and is neither nothing nor everything, and
-  // the launch is an IBD decode of more than two rounds of groups -- what was measured (C2: 3.8 rounds).  One round has
-  // nobody to share with (a sums launch is always one: its batches run side by side, whatever the list holds), and in a
-  // launch of two rounds every wave's first group runs in phase with all the others; both keep the static layout, and
-  // so do the sums, until a measurement says otherwise.  A slot gains one row, the table of its window's chunks (a
-  // 32-bit entry each): where that row costs the last buffer, the plan has one buffer less a wave; it never exceeds the
-  // budget the static plan was given.  A window asks for a buffer for its first poolCap chunks: phi x its share.
-  size_t poolResident = 0;
-  if (residentBuilt && !w2 && k.poolFn && ctx->chunkPool != 0 && ctx->residentChunks < 0 &&
-      resident > 0 && resident < maxChunks && (ctx->chunkPool == 1 || (mode == kModeIbd && list.size() > 2 * slots)) &&
-      maxChunks * sizeof(int32_t) <= vecBytes && rowsBudget > fixed + 1) {
-    poolResident = std::min((rowsBudget - fixed - 1) / chunkRows(C), resident);
-  }
-  plan.chunk = (int)C;
-  plan.chunkRows = (int)chunkRows(C);
-  plan.maxChunks = (int)maxChunks;
-  plan.slots = (int)slots;
   plan.k = k;
-  plan.wavesPerWindow = 1;
-  if (poolResident > 0 && slots * poolResident < (1u << 30)) {
-    const size_t want = ((size_t)ctx->chunkPoolPhi * poolResident + 99) / 100;
-    plan.residentChunks = (int)poolResident;
-    plan.wsSlot = (chunkRows(C) + maxChunks + 2 + (sideRows - 2) + 1) * K4 * kWave;
-    plan.poolOff = plan.wsSlot * slots;
-    plan.poolBuffers = (uint32_t)(slots * poolResident);
-    plan.poolCap = (int)std::min(maxChunks, std::max<size_t>(want, 1));
-    plan.bytes = (plan.poolOff + (size_t)plan.poolBuffers * chunkRows(C) * K4 * kWave) * sizeof(float4);
-    return FSMC_OK;
-  }
-  plan.residentChunks = (int)resident;
-  plan.wsSlot = (chunkRows(C) * (1 + resident) + maxChunks + 2 + (sideRows - 2)) * K4 * kWave;
-  plan.poolOff = 0;
-  plan.poolBuffers = 0;
-  plan.poolCap = 0;
-  plan.bytes = plan.wsSlot * sizeof(float4) * slots;
-  return FSMC_OK;
+  return plan::planOneWave(settingsOf(ctx), traitsOf(m, mode, k, perCU), mode == kModeIbd, list, paired, budget, share,
+                           readDiag(), plan, why);
 }
 
-// The launch of the Viterbi kernel (fsmc_pair_viterbi.h) over slices of at most `nGroups` whole-sequence groups.  A wave's
-// workspace is `chunk` rows of back-pointers (KT4 x 64 dwords a site) and a checkpoint (KT4 x 64 float4) a chunk; without
-// state rows (`wantStates` false) one row of back-pointers that nobody reads.  The waves: what is resident, the groups,
-// and what the hard budget holds of the smallest slot any chunk length gives (about 2 sqrt(S) sites a chunk: memory is
-// chunk + 4 x S / chunk rows).  The chunk: the caller's (fsmc_ctx_set_chunk_sites), otherwise the whole sequence -- one
-// sweep instead of two -- halved until the waves' slots fit what the context may spend (the soft budget; the hard one
-// for sequences of at most 512 sites, as planOneWave keeps short windows whole).  Computes only, like planOneWave.
+// plan::planViterbi for the Viterbi kernel `k`.  Computes only, like planOneWave.
 int planViterbi(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups, bool wantStates,
-                const WsBudget& budget, LaunchPlan& plan, std::string& why)
+                const plan::WsBudget& budget, LaunchPlan& plan, std::string& why)
 {
   int perCU = 0;
   const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
@@ -875,81 +696,24 @@ int planViterbi(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k,
     why = std::string("occupancy query of the Viterbi kernel: ") + hipGetErrorString(e);
     return FSMC_EHIP;
   }
-  size_t slots = std::max<size_t>(1, std::min((size_t)ctx->nCU * (size_t)std::max(perCU, 1), nGroups));
-  const size_t L = (size_t)m->S;
-  const size_t K4 = (size_t)(k.member + 3) / 4;
-  const size_t psiRow = K4 * kWave * sizeof(uint32_t), ckptRow = K4 * kWave * sizeof(float4);
-  auto slotBytes = [&](size_t c) { return c * psiRow + (L + c - 1) / c * ckptRow; };
-  size_t C = L, bytes = psiRow;
-  if (wantStates) {
-    size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(2.0 * std::sqrt((double)L))));
-    if (ctx->chunkSites) {
-      cMin = std::min<size_t>(ctx->chunkSites, L);
-    }
-    slots = std::min<size_t>(slots, (size_t)(budget.hard / slotBytes(cMin)));
-    if (slots == 0) {
-      why = "workspace limit too small for the back-pointers of one wave";
-      return FSMC_ENOMEM;
-    }
-    if (ctx->chunkSites) {
-      C = cMin;
-    } else {
-      const uint64_t room = L <= 512 ? budget.hard : budget.soft;
-      while (C > cMin && (uint64_t)slots * slotBytes(C) > room) {
-        C = std::max(cMin, (C + 1) / 2);
-      }
-    }
-    bytes = slotBytes(C);
-  }
-  plan = LaunchPlan();
   plan.k = k;
-  plan.chunk = (int)C;
-  plan.chunkRows = (int)C;
-  plan.maxChunks = (int)((L + C - 1) / C);
-  plan.wsSlot = bytes / sizeof(float4);
-  plan.slots = (int)slots;
-  plan.wavesPerWindow = 1;
-  plan.bytes = bytes * slots;
-  return FSMC_OK;
+  return plan::planViterbi(settingsOf(ctx), m->S, k.member, perCU, nGroups, wantStates, budget, plan, why);
 }
 
-// A launch of the two-waves-per-window kernel, if this one qualifies: `nItems` workgroups (groups; batches of the sums)
-// that are ALL resident at once -- so the launch has at most half as many items as the chip holds waves of this member,
-// the case in which the one-wave kernel leaves every wave alone on a SIMD (or SIMDs idle) -- and whose whole windows fit
-// the workspace (to - from rows a workgroup; the same rule as planOneWave's whole windows: inside the hard budget, and
-// inside what the context has earned unless the window is no longer than a chunk would be).
-// twoWavesWanted: what can be said before the budget is read; planTwoWaves: the plan, false if it does not fit.
+// Two waves per window (plan::planTwoWaves).  twoWavesWanted: what can be said before the budget is read.
 bool twoWavesWanted(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems)
 {
-  if (ctx->twoWaves == 1 || nItems == 0 || !k2.fn) {
+  if (ctx->twoWaves == 1 || nItems == 0 || !k2.fn || readDiag().twoWavesNever) {
     return false;
   }
-  if (const char* v = std::getenv("FSMC_DIAG_TWO_WAVE_WINDOWS")) { // tests: the whole suite on the one-wave kernels
-    if (std::strcmp(v, "never") == 0) {
-      return false;
-    }
-  }
   int perCU = 0;
-  return workgroupsPerCU(k2, 4, 2, perCU) == hipSuccess && perCU >= 1 && nItems <= (size_t)ctx->nCU * perCU;
+  return workgroupsPerCU(k2, 4, 2, perCU) == hipSuccess && plan::allResident(settingsOf(ctx), perCU, nItems);
 }
 
-bool planTwoWaves(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems, const WsBudget& budget, LaunchPlan& plan)
+bool planTwoWaves(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems, const plan::WsBudget& budget, LaunchPlan& plan)
 {
-  size_t L = 1;
-  for (const fsmc_group& g : ctx->hGroups) {
-    L = std::max<size_t>(L, g.to - g.from);
-  }
-  const size_t K4 = (size_t)(k2.member + 3) / 4;
-  plan = LaunchPlan();
   plan.k = k2;
-  plan.chunk = (int)L;
-  plan.chunkRows = (int)L;
-  plan.maxChunks = 1;
-  plan.wsSlot = L * K4 * kWave;
-  plan.slots = (int)nItems;
-  plan.wavesPerWindow = 2;
-  plan.bytes = plan.wsSlot * sizeof(float4) * nItems;
-  return plan.bytes <= budget.hard && (plan.bytes <= budget.soft || L <= 512);
+  return plan::planTwoWaves(ctx->hGroups, k2.member, nItems, budget, plan);
 }
 
 // The one place the decode's workspace is allocated: `buf` holds at least `bytes` afterwards, or nothing.  A buffer
@@ -971,7 +735,7 @@ int holdWorkspace(fsmc_ctx* ctx, DevBuf& buf, size_t bytes)
   if (rc != FSMC_OK) {
     (void)hipGetLastError(); // (the failed hipMalloc's: a later launch's check must not find it)
   } else if (buf.bytes != held) {
-    payForWorkspace(ctx, buf.bytes);
+    plan::payForWorkspace(settingsOf(ctx), ctx->credit, buf.bytes, readDiag());
   }
   return rc;
 }
@@ -1195,19 +959,10 @@ int launchBeside(fsmc_ctx* ctx, const KernelChoice& kSide, KParams& pSide, int s
   return FSMC_OK;
 }
 
-// What output staging beside the workspace may take (the sums' planes, the pair posteriors' slices): the caller's
-// workspace limit or a quarter of the card, and no more than 1/`parts` of what the card has free -- `held`, the staging
-// this context holds already, counted as free -- beside a reserve of 2 GiB.
+// plan::stagingLimit of what the card has free right now.
 uint64_t stagingLimit(const fsmc_ctx* ctx, uint64_t held, unsigned parts)
 {
-  uint64_t limit = ctx->wsLimit ? ctx->wsLimit : (uint64_t)(0.25 * (double)ctx->hbmBytes);
-  size_t freeB = 0, totalB = 0;
-  if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-    const uint64_t room = (uint64_t)freeB + held;
-    const uint64_t reserve = 2ull << 30;
-    limit = std::min<uint64_t>(limit, room > reserve ? (room - reserve) / parts : 0);
-  }
-  return limit;
+  return plan::stagingLimit(settingsOf(ctx), memInfo(), held, parts);
 }
 
 // The way out for rows a slice leaves on the device (the posterior tables, the tail / quantile rows): two pinned buffers
@@ -1260,8 +1015,7 @@ int prepareDecode(fsmc_ctx* ctx, const fsmc_model* m, int mode, uint32_t wantStr
   }
   size_t staged = nItems;
   if (stagingPerItem) {
-    staged = std::max<size_t>(1, (size_t)(stagingLimit(ctx, ctx->out.bytes, 1) / stagingPerItem));
-    staged = loweredByEnv("FSMC_DIAG_SUMS_SLOTS", staged);
+    staged = plan::stagedItems(stagingLimit(ctx, ctx->out.bytes, 1), stagingPerItem, readDiag());
     plan.slots = (int)std::min({(size_t)plan.slots, nItems, staged});
   }
   const KernelChoice k2 = chooseTwoWaveKernel(m, mode);
@@ -1300,13 +1054,10 @@ int lastPairSlices(const fsmc_ctx* ctx, PairSlicing kind, int32_t* slices)
   return FSMC_OK;
 }
 
-// The work list in slices of groups, as the fsmc_decode_pair_* entry points send it through the device: the launch of a
-// slice sees the slice as its whole group list (p.groups points at the slice's first group of the resident list).
-struct WorkSlices {
-  const fsmc_ctx* ctx = nullptr;
-  size_t slice = 0;         // groups a slice (the last one may have fewer)
-  size_t nSlices = 0;
-  size_t slicePairsMax = 0; // pairs of the largest slice
+// The work list in slices of groups (plan::Slices), as the fsmc_decode_pair_* entry points send it through the device:
+// the launch of a slice sees the slice as its whole group list (p.groups points at the slice's first group of the
+// resident list).
+struct WorkSlices : plan::Slices {
   LaunchPlan plan;
   // per-pair mode (perPairSetup): the slice's mean / MAP rows in ppStage
   float* stageMean = nullptr;
@@ -1314,15 +1065,6 @@ struct WorkSlices {
   // what the setups upload from: alive until the entry point synchronises the stream
   std::vector<size_t> hOffsets;
   std::vector<float> hCoal;
-
-  size_t firstGroup(size_t sl) const { return sl * slice; }
-  size_t groups(size_t sl) const { return std::min(slice, ctx->nGroups - sl * slice); }
-  size_t firstPair(size_t sl) const { return ctx->hGroups[firstGroup(sl)].first_pair; }
-  size_t pairs(size_t sl) const
-  {
-    const fsmc_group& last = ctx->hGroups[firstGroup(sl) + groups(sl) - 1];
-    return (size_t)last.first_pair + last.n_pairs - firstPair(sl);
-  }
 };
 
 // The sliced entry points decode whole sequences only.  (A check of its own: each entry point keeps it where it
@@ -1349,20 +1091,11 @@ int planSlices(fsmc_ctx* ctx, const fsmc_model* m, int mode, PairSlicing kind, u
                WorkSlices& ws, size_t sliceMost = SIZE_MAX)
 {
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
-  size_t slice = ctx->pairSlices[kind].groups;
-  if (slice == 0) {
-    slice = (size_t)(stagingLimit(ctx, held, 2) / groupBytes);
-  }
-  ws.ctx = ctx;
-  ws.slice = std::max<size_t>(1, std::min({slice, ctx->nGroups, sliceMost}));
-  ws.nSlices = (ctx->nGroups + ws.slice - 1) / ws.slice;
+  const size_t setting = ctx->pairSlices[kind].groups;
+  plan::planSlices(ctx->hGroups, setting, setting ? 0 : stagingLimit(ctx, held, 2), groupBytes, sliceMost, ws);
   if (mode != kNoDecode) {
     const std::vector<fsmc_group> first(ctx->hGroups.begin(), ctx->hGroups.begin() + (ptrdiff_t)ws.slice);
     FSMC_TRY(prepareDecode(ctx, m, mode, ctx->betaStride, first, ws.slice, 0, ws.plan));
-  }
-  ws.slicePairsMax = 0;
-  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
-    ws.slicePairsMax = std::max(ws.slicePairsMax, ws.pairs(sl));
   }
   return FSMC_OK;
 }
@@ -1731,24 +1464,7 @@ int fsmc_ctx_expect_work(fsmc_ctx* ctx, double pair_sites, int32_t states)
   if (!(pair_sites >= 0) || states < 1) {
     return fail(ctx, FSMC_EINVAL, "expected work: pair-sites >= 0 and states >= 1");
   }
-  if (pair_sites == 0) {
-    // the announced job is over (HMM::finishDecoding / finishFromHashing): what is left of the announcement -- an
-    // estimate that was too high, pairs that were filtered, a job that threw -- is forgotten and its unspent credit
-    // taken back, so that a later job on this context earns from its own launches again
-    ctx->wsEarned = std::max(0.0, ctx->wsEarned - ctx->wsAnnouncedCredit);
-    ctx->wsAnnounced = 0;
-    ctx->wsAnnouncedCredit = 0;
-    return FSMC_OK;
-  }
-  // the job's launches will save what workspace upgrades save of its estimated kernel time: its credit is there at the
-  // first launch (workspaceBudget); the launches themselves then earn nothing until the announced work is used up.
-  // No announcement is worth more than the card: the credit is capped at the device's memory.
-  const double seconds = pair_sites * (8.0 * states + 0.25) / (0.8 * 8e12);
-  const double credit = std::min(earnScale() * kEarnFraction * seconds * kAllocBytesPerSecond,
-                                 std::max(0.0, (double)ctx->hbmBytes - ctx->wsAnnouncedCredit));
-  ctx->wsAnnounced += seconds;
-  ctx->wsAnnouncedCredit += credit;
-  ctx->wsEarned += credit;
+  plan::expectWork(settingsOf(ctx), ctx->credit, pair_sites, states, readDiag());
   return FSMC_OK;
 }
 
@@ -1916,7 +1632,7 @@ int fsmc_model_create(fsmc_ctx* ctx, const fsmc_model_desc* d, fsmc_model** out)
   m->KP = (d->K + kKPad - 1) / kKPad * kKPad; // rows zero padded to whole operand blocks of any tunable width
   if (d->K > 128 && d->K <= kMaxStatesW2) {
     // wide models: NW waves per group hold KP / NW states each (fsmc_kernels_w2.h); the padding states are ghosts
-    const W2Member w = w2Member(d->K);
+    const plan::W2Member w = plan::w2Member(d->K, readDiag(), builtW2Members());
     m->w2NW = w.NW;
     m->KP = w.NW * w.KH;
   }
@@ -2102,116 +1818,6 @@ int fsmc_worklist_upload(fsmc_ctx* ctx, const fsmc_pair* pairs, size_t n_pairs, 
   return FSMC_OK;
 }
 
-namespace
-{
-// Two half-groups per wavefront.  A group of at most 32 pairs (a hashing-mode batch) fills half a wave; two of them can
-// share one if the wave walks the union of their windows (decode_kernel<..., DUAL>).  Worth it when the union is not
-// much longer than the longer window: groups are sorted by (window length, from) and neighbours are paired while the
-// union stays within 1.25 x the longer one.  Returns false when the
-// list does not call for it (no half-full groups, or all of them were packed by the caller already).
-bool buildDualItems(const std::vector<fsmc_group>& groups, uint32_t maxLen, std::vector<fsmc_group>& items,
-                    std::vector<fsmc_group>& unions, std::vector<fsmc_group>& rest)
-{
-  // half-full groups whose window (and so the union with a neighbour of the same length class) is within `maxLen`
-  // are candidates (the paired kernel decodes in chunks too, so the callers pass no real bound any more); everything
-  // else -- full groups -- runs as uploaded, in a second kernel
-  std::vector<uint32_t> small;
-  for (size_t g = 0; g < groups.size(); ++g) {
-    if (groups[g].n_pairs <= 32 && (uint64_t)(groups[g].to - groups[g].from) * 5 <= (uint64_t)maxLen * 4) {
-      small.push_back((uint32_t)g);
-    }
-  }
-  if (small.size() < 2) {
-    return false;
-  }
-  // neighbours after this sort have windows of (nearly) the same length that start close to each other: the union a
-  // pair walks is then little longer than either window (lengths are compared in 64-site steps, the hashing word)
-  std::sort(small.begin(), small.end(), [&](uint32_t x, uint32_t y) {
-    const fsmc_group &a = groups[x], &b = groups[y];
-    const uint32_t la = (a.to - a.from + 63) / 64, lb = (b.to - b.from + 63) / 64;
-    return la != lb ? la < lb : a.from != b.from ? a.from < b.from : x < y;
-  });
-  items.clear();
-  unions.clear();
-  rest.clear();
-  std::vector<char> taken(groups.size(), 0);
-  for (size_t i = 0; i + 1 < small.size();) {
-    const fsmc_group &a = groups[small[i]], &b = groups[small[i + 1]];
-    const uint32_t lenA = a.to - a.from, lenB = b.to - b.from;
-    const uint32_t lenU = std::max(a.to, b.to) - std::min(a.from, b.from);
-    if ((uint64_t)lenU * 4 <= (uint64_t)std::max(lenA, lenB) * 5 && lenU <= maxLen) {
-      items.push_back(a);
-      items.push_back(b);
-      fsmc_group u = a;
-      u.from = std::min(a.from, b.from);
-      u.to = std::max(a.to, b.to);
-      u.scan_from = std::min(a.scan_from, b.scan_from);
-      u.scan_to = std::max(a.scan_to, b.scan_to);
-      unions.push_back(u);
-      taken[small[i]] = taken[small[i + 1]] = 1;
-      i += 2;
-    } else {
-      i += 1;
-    }
-  }
-  if (unions.empty()) {
-    return false;
-  }
-  // A half-full group that found no partner but fits the layout rides in the same kernel as an item of its own (B
-  // empty): one queue, longest window first, instead of a second kernel whose long windows finish whenever the
-  // hardware got round to starting them.  What does not fit (more than 32 pairs, a window beyond the budget) is `rest`.
-  for (size_t g = 0; g < groups.size(); ++g) {
-    if (taken[g]) {
-      continue;
-    }
-    const fsmc_group& a = groups[g];
-    if (a.n_pairs <= 32 && a.to - a.from <= maxLen) {
-      fsmc_group none = a;
-      none.n_pairs = 0;
-      items.push_back(a);
-      items.push_back(none);
-      unions.push_back(a);
-    } else {
-      rest.push_back(a);
-    }
-  }
-  // the waves pull the items longest first
-  std::vector<uint32_t> order(unions.size());
-  for (size_t i = 0; i < order.size(); ++i) {
-    order[i] = (uint32_t)i;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-    return unions[x].scan_to - unions[x].from > unions[y].scan_to - unions[y].from;
-  });
-  std::vector<fsmc_group> items2(items.size()), unions2(unions.size());
-  for (size_t i = 0; i < order.size(); ++i) {
-    unions2[i] = unions[order[i]];
-    items2[2 * i] = items[2 * order[i]];
-    items2[2 * i + 1] = items[2 * order[i] + 1];
-  }
-  items.swap(items2);
-  unions.swap(unions2);
-  return true;
-}
-
-// Longest window first: the decode ends when the last wave does, and a wave that pulls a long window late in the
-// queue runs on alone.  (The order of the queue is free: records are keyed by pair and sorted at fetch.)
-// Returns false when the list already is in that order (every window the same length, as in the all-pairs modes).
-bool longestFirst(std::vector<fsmc_group>& list)
-{
-  auto len = [](const fsmc_group& g) { return g.scan_to - g.from; };
-  bool ordered = true;
-  for (size_t i = 1; i < list.size() && ordered; ++i) {
-    ordered = len(list[i]) <= len(list[i - 1]);
-  }
-  if (ordered) {
-    return false;
-  }
-  std::stable_sort(list.begin(), list.end(), [&](const fsmc_group& a, const fsmc_group& b) { return len(a) > len(b); });
-  return true;
-}
-} // namespace
-
 int fsmc_ctx_set_pairing(fsmc_ctx* ctx, uint32_t mode)
 {
   if (!ctx || mode > 1) {
@@ -2270,34 +1876,25 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   // (decode_kernel<..., DUAL>, with beta stride 2 where that is built); the other groups one per wave, in a kernel that
   // runs beside it.
   KernelChoice kDual;
-  uint64_t maxLen = 0, maxLenAlone = 0; // pairing budgets: beside a second kernel (half the workspace) / on its own
-  if (ctx->pairing != 0 && !m->sequence && familyMember(m) > 0) {
+  const bool pairing = ctx->pairing != 0 && !m->sequence && familyMember(m) > 0;
+  if (pairing) {
     kDual = chooseKernel(m, kModeIbd, track, true, ctx->betaStride);
-    // (the paired kernel has the chunked layout too: how long a window may be is no longer a question of memory)
-    maxLen = maxLenAlone = 1u << 30;
   }
   fsmc_ctx::IbdQueues& q = ctx->q;
-  if (!q.valid || q.serial != ctx->worklistSerial || q.maxLen != maxLen || q.maxLenAlone != maxLenAlone ||
-      q.pairing != ctx->pairing) {
+  if (!q.valid || q.serial != ctx->worklistSerial || q.pairing != pairing) {
     q.valid = false;
     q.items.clear();
     q.unions.clear();
     q.rest.clear();
-    // first with the whole workspace: if every group then rides in the paired kernel there is no second kernel to share with
-    q.dual = maxLenAlone > 0 && buildDualItems(ctx->hGroups, (uint32_t)maxLenAlone, q.items, q.unions, q.rest);
+    q.dual = pairing && plan::buildDualItems(ctx->hGroups, q.items, q.unions, q.rest);
+    // (if every group rides in the paired kernel there is no second kernel to share the workspace with)
     q.alone = q.dual && q.rest.empty();
-    if (q.dual && !q.alone) {
-      q.items.clear();
-      q.unions.clear();
-      q.rest.clear();
-      q.dual = maxLen > 0 && buildDualItems(ctx->hGroups, (uint32_t)maxLen, q.items, q.unions, q.rest);
-    }
     if (!q.dual) {
       q.items.clear();
       q.unions.clear();
       q.rest = ctx->hGroups;
     }
-    q.reordered = longestFirst(q.rest) || q.dual;
+    q.reordered = plan::longestFirst(q.rest) || q.dual;
     if (q.dual) {
       rc = upload(ctx, &ctx->dItems, q.items.data(), q.items.size());
       if (rc != FSMC_OK) {
@@ -2311,9 +1908,7 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
       }
     }
     q.serial = ctx->worklistSerial;
-    q.maxLen = maxLen;
-    q.maxLenAlone = maxLenAlone;
-    q.pairing = ctx->pairing;
+    q.pairing = pairing;
     q.valid = true;
   }
   const bool haveRest = !q.rest.empty();
@@ -3485,14 +3080,11 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   uint32_t wantStride = ctx->betaStride;
-  if (wantStride == 0) {
-    // Beta stride 2 pays where the launch fills the chip (C2: 2762 -> 2454 ms: the rows' traffic was the bound); a wave
-    // alone on its SIMD only gets the recomputed half sweep on top (C1 shape: 41.2 -> 43.3 ms).  Left to itself
-    // (fsmc_ctx_set_beta_stride 0) a launch of fewer batches than the chip holds waves keeps stride 1.
+  if (wantStride == 0) { // left to the library: plan::sumsKeepStrideOne
     const KernelChoice k2 = chooseKernel(m, kModeSums, false, false, 0);
     int perCU = 0;
-    if (k2.fn && k2.stride == 2 && workgroupsPerCU(k2, 8, 0, perCU) == hipSuccess && perCU >= 1 &&
-        n_batches < (size_t)ctx->nCU * (size_t)perCU) {
+    if (k2.fn && k2.stride == 2 && workgroupsPerCU(k2, 8, 0, perCU) == hipSuccess &&
+        plan::sumsKeepStrideOne(settingsOf(ctx), perCU, n_batches)) {
       wantStride = 1;
     }
   }

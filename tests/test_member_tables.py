@@ -1,5 +1,5 @@
 """The tests' picture of which kernel serves which model (conftest.expected_member / wave_group_member) against the
-library's own table (csrc/fsmc_capi.hip, w2Member; csrc/fsmc_instances.h, FSMC_ALL_W2) and the build's member list --
+library's own table (csrc/fsmc_plan.h, w2Member; csrc/fsmc_instances.h, FSMC_ALL_W2) and the build's member list --
 read from the sources, no GPU."""
 import os
 import re
@@ -11,8 +11,8 @@ CSRC = os.path.join(ROOT, "fastsmc_amd", "csrc")
 
 
 def _w2_member_table():
-    src = open(os.path.join(CSRC, "fsmc_capi.hip")).read()
-    body = src[src.index("W2Member w2Member(int K)"):]
+    src = open(os.path.join(CSRC, "fsmc_plan.h")).read()
+    body = src[src.index("W2Member w2Member(int K,"):]
     body = body[:body.index("\n}\n")]
     steps = [(int(k), int(nw), int(kh)) for k, nw, kh in re.findall(r"if \(K <= (\d+)\) return \{(\d+), (\d+)\};", body)]
     last = re.search(r"\n  return \{(\d+), (\d+)\};", body)
