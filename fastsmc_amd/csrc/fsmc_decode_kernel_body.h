@@ -20,6 +20,10 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
   static_assert(!DUAL || (MODE == kModeIbd && !SEQ), "two half-groups per wave: array-mode IBD");
   // array mode: the backward loops are rotated (operand-free step tails overlap the next step's first operand requests)
   constexpr bool kRotate = !SEQ;
+  // Beta stride 2, a row with a spare float (K no multiple of four): a stored row carries, in float K, the scaling
+  // reciprocal of the row ABOVE it -- the row the alpha sweep recomputes, which then needs neither its sum nor a division.
+  // Every other instantiation passes 0.f pads and keeps its sums.
+  constexpr bool kCarryScale = HALF && !SEQ && !DUAL && (KT % 4 != 0);
   constexpr int KA = KT;
   constexpr int K4A = (KA + 3) / 4;
   constexpr int E4A = ((KA + kKPad - 1) / kKPad) * (kKPad / 4); // float4 per emission row (rows padded to kKPad)
@@ -335,11 +339,20 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
         enterChunk(ckJ); // (a sweep that stops short of the window enters its last chunk at the checkpoint of aEnd)
       }
 #endif
-      auto afterBeta = [&](const int pos) -> bool { // true if a row went out
+      // kCarryScale: c(s) = 1.0f / bsum(s) is the reciprocal that scaled the row of site s.  cUp = c(pos + 1) rides in
+      // the spare float of a chunk row: the alpha sweep reads the row of odd offset r one site before it recomputes the
+      // row of r + 1 (pass B walks down, so c(r + 1) is known when row r goes out; the pad of a chunk's last row is
+      // never read).  cOwn = c(pos) rides in a checkpoint: the first site of a chunk has no stored row below it, and
+      // checkpoint j IS beta of that site -- for chunk 0 and a one-chunk window, which have none, the row of `from`
+      // goes to checkpoint slot 0 (the area has maxChunks + 2 slots, of which 1 .. nChunks are in use).
+      // Bit-exact: the reader would compute c(pos) as 1.0f / bsum from beta_core_pk on the landed bits of pos + 1 with the
+      // same operand rows; the writer fed the same function the same bits and divided by the same instruction sequence.
+      // So the stored float is the float the reader would have produced.
+      auto afterBeta = [&](const int pos, const float cUp = 0.f, const float cOwn = 0.f) -> bool { // true if a row went out
         if (single) {
           const int rel = pos - from;
           if (pos < aEnd && (!HALF || (rel & 1) || pos == aEnd - 1)) {
-            store_vec<KT, KA>(K, chunkbuf + slotOf(rel) * vecF4, laneOff, b);
+            store_vec<KT, KA>(K, chunkbuf + slotOf(rel) * vecF4, laneOff, b, cUp);
             return true;
           }
         } else {
@@ -357,15 +370,15 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
             const int hiJ = ckPos + C < aEnd ? ckPos + C : aEnd;
             if (!HALF || (relc & 1) || pos == hiJ - 1) {
 #if FSMC_DECODE_POOL
-              store_vec<KT, KA>(K, keep + slotOf(relc) * vecF4, laneOff, b);
+              store_vec<KT, KA>(K, keep + slotOf(relc) * vecF4, laneOff, b, cUp);
 #else
-              store_vec<KT, KA>(K, resBase + ((size_t)ckJ * p.chunkRows + slotOf(relc)) * vecF4, laneOff, b);
+              store_vec<KT, KA>(K, resBase + ((size_t)ckJ * p.chunkRows + slotOf(relc)) * vecF4, laneOff, b, cUp);
 #endif
               out = true;
             }
           }
           if (__builtin_expect(pos == ckPos && ckJ >= 1, 0)) { // once per chunk
-            store_vec<KT, KA>(K, ckpt + (size_t)ckJ * vecF4, laneOff, b);
+            store_vec<KT, KA>(K, ckpt + (size_t)ckJ * vecF4, laneOff, b, cOwn);
             ckJ -= 1;
             ckPos = from + ckJ * C;
 #if FSMC_DECODE_POOL
@@ -418,6 +431,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
               }
             }
           };
+          float cPrev = 1.0f; // kCarryScale: the reciprocal of the iteration before, c(q + 1)
           bool stored = false;
           for (int pos = to - 2; pos >= from; --pos) {
             const int q = pos + 1;
@@ -434,14 +448,26 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
             BetaOps<KT> ops;
             beta_issue_pk<KT>(ops, rs, e);
             FSMC_END(cycW, 0);
-            scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
-            stored = afterBeta(q);
+            if constexpr (kCarryScale) {
+              const float cq = scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
+              stored = afterBeta(q, cPrev, cq);
+              cPrev = cq;
+            } else {
+              scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
+              stored = afterBeta(q);
+            }
             FSMC_END(cycW, 1);
             bsum = beta_core_pk<KT, KA, kGhost<KT>>(b, w, ops, rs, e, tabs.ghostMask, cycW);
           }
           openBeta(from);
-          scale_pk<KT, KA>(b, w, bsum);
-          afterBeta(from);
+          if constexpr (kCarryScale) {
+            const float cq = scale_pk<KT, KA>(b, w, bsum);
+            afterBeta(from, cPrev, cq);
+            store_vec<KT, KA>(K, ckpt, laneOff, b, cq); // checkpoint slot 0: beta of the window's first site and its c
+          } else {
+            scale_pk<KT, KA>(b, w, bsum);
+            afterBeta(from);
+          }
         } else {
           for (int pos = to - 2; pos >= from; --pos) {
             const int q = pos + 1;
@@ -523,10 +549,11 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
         if (j > 0) {
           store_vec<KT, KA>(K, saveA, laneOff, a);
         }
-        auto storeRow = [&](const int site, const float (&row)[KA]) -> bool { // true if the row went out
+        // (cUp: as in pass B's afterBeta -- the reciprocal that scaled the row of site + 1, kCarryScale)
+        auto storeRow = [&](const int site, const float (&row)[KA], const float cUp = 0.f) -> bool { // true if the row went out
           const int rel = site - lo;
           if (!HALF || (rel & 1) || site == hi - 1) {
-            store_vec<KT, KA>(K, chunkbuf + slotOf(rel) * vecF4, laneOff, row);
+            store_vec<KT, KA>(K, chunkbuf + slotOf(rel) * vecF4, laneOff, row, cUp);
             return true;
           }
           return false;
@@ -568,6 +595,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
               }
             }
           };
+          float cPrev = 1.0f; // kCarryScale: the reciprocal of the iteration before, c(q + 1)
           bool stored = false;
           for (; pos >= lo; --pos) {
             const int q = pos + 1;
@@ -584,15 +612,21 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
             BetaOps<KT> ops;
             beta_issue_pk<KT>(ops, rs, e);
             FSMC_END(cycW, 0);
-            scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
-            stored = q < hi && storeRow(q, b);
+            if constexpr (kCarryScale) {
+              const float cq = scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
+              stored = q < hi && storeRow(q, b, cPrev);
+              cPrev = cq;
+            } else {
+              scale_pk<KT, KA>(b, w, bsum); // beta of site q, final
+              stored = q < hi && storeRow(q, b);
+            }
             FSMC_END(cycW, 1);
             bsum = beta_core_pk<KT, KA, kGhost<KT>>(b, w, ops, rs, e, tabs.ghostMask, cycW);
           }
           reopenBeta(pos + 1);
           scale_pk<KT, KA>(b, w, bsum);
           if (pos + 1 < hi) {
-            storeRow(pos + 1, b);
+            storeRow(pos + 1, b, kCarryScale ? cPrev : 0.f);
           }
         } else {
           float b[KA];
@@ -663,6 +697,12 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
       // costs the wave a round trip to L2 at every site)
       // every request so far (the first beta row, the first sites' emission rows) has landed: inside the loop the
       // emission registers are then only ever read behind one of its own vmcnt(0) waits, and the compiler adds none
+      // kCarryScale: c of the site whose row the sweep recomputes next -- at a chunk's first site the pad of checkpoint j
+      // (pass B put it there for kept and rebuilt chunks alike), afterwards the pad of the stored row one site below
+      float cUp = 0.f;
+      if constexpr (kCarryScale) {
+        cUp = load_pad<KT>(ckpt + (size_t)j * vecF4, laneOff);
+      }
       waitVm0();
       for (int pos = lo; pos < hi; ++pos) {
         // HALF: this site's beta row was not stored -- it is recomputed below from the row of site pos+1
@@ -732,8 +772,14 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
             beta_issue_pk<KT>(ops, rs, eq); // in flight while the landed row moves from LDS to registers
             readLanded();
             FSMC_END(cycW, 9);
-            const float bsum = beta_core_pk<KT, KA, kGhost<KT>>(b, w, ops, rs, eq, tabs.ghostMask, cycW);
-            scale_pk<KT, KA>(b, w, bsum);
+            if constexpr (kCarryScale) {
+              // c of this site came with the row below it (or the chunk's checkpoint): no sum, no division
+              beta_core_pk<KT, KA, kGhost<KT>, false, false>(b, w, ops, rs, eq, tabs.ghostMask, cycW);
+              scale_by_pk<KT, KA>(b, w, cUp);
+            } else {
+              const float bsum = beta_core_pk<KT, KA, kGhost<KT>>(b, w, ops, rs, eq, tabs.ghostMask, cycW);
+              scale_pk<KT, KA>(b, w, bsum);
+            }
             if constexpr (DUAL) {
               // the lanes whose own window ends at this site start from beta = 1 here (HMM.cpp:887-897), exactly what
               // pass B gave them (and did not store: the row of an even offset): 1.0f * (1.0f / sum of K ones)
@@ -812,6 +858,11 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void decode_kernel(cons
                     sumq = sumq + w[kk];
                   }
                 }
+              }
+            }
+            if constexpr (kCarryScale) {
+              if (blk == NB - 1) {
+                cUp = pick(c0, c1, K - blk * kCB); // float K of the landed row: c of the site above
               }
             }
             __builtin_amdgcn_sched_barrier(0);

@@ -468,7 +468,9 @@ __device__ __forceinline__ void beta_issue_pk(BetaOps<KT>& o, cfloat_p rowSet, c
 
 // The recurrences of one backward step: on entry b = beta of site pos+1 (scaled), on exit w = the un-normalised
 // beta of site pos and the return value its sum over the states (k ascending from 0.f); b is used up.
-template <int KT, int KA, bool GHOST, bool SY = false>
+// SUM = false: the caller has the reciprocal of that sum already (a recomputed row of beta stride 2 whose neighbour
+// carries it, fsmc_decode_kernel_body.h: kCarryScale) -- the same w, no sum, the return value is 0.f.
+template <int KT, int KA, bool GHOST, bool SY = false, bool SUM = true>
 __device__ __forceinline__ float beta_core_pk(float (&b)[KA], float (&w)[KA], BetaOps<KT>& ops, cfloat_p rowSet,
                                               const float4* e, cfloat_p ghostMask, Diag& dg)
 {
@@ -616,12 +618,21 @@ __device__ __forceinline__ float beta_core_pk(float (&b)[KA], float (&w)[KA], Be
         }
         w[k] = x.x;
         w[k + 1] = x.y;
-        sum = sum + x.x;
-        sum = sum + x.y;
-        BL = (k + 1 < K - 1) ? bl.y + bv.y : bl.y;
+        if constexpr (SUM) {
+          sum = sum + x.x;
+          sum = sum + x.y;
+        } else {
+          // No instruction: the pair is final HERE.  The sum chain is what kept every state's adds in the block of their
+          // operands; without it instruction selection parks the first states' adds behind the last block and the
+          // operand registers they read (two blocks of sixteen SGPRs) are spilled and reloaded at every step.
+          FSMC_GCN_ASM("" ::"v"(x.x), "v"(x.y));
+        }
+        BL =(k + 1 < K - 1) ? bl.y + bv.y : bl.y;
       } else if (k < K) {
         w[k] = (BL + d[i] * b[k]) + w[k];
-        sum = sum + w[k];
+        if constexpr (SUM) {
+          sum = sum + w[k];
+        }
         if (k < K - 1) {
           BL = BL + bt[i] * b[k];
         }
@@ -634,10 +645,11 @@ __device__ __forceinline__ float beta_core_pk(float (&b)[KA], float (&w)[KA], Be
 
 // The operand-free tail of a step (HmmUtils.cpp:102-151: scal = 1.0f/sum, vec *= scal): v = w * (1.0f / sum).
 // With sum = 1.0f it is an exact copy (a loaded checkpoint, the un-normalised half-steps of sequence mode).
-template <int KT, int KA> __device__ __forceinline__ void scale_pk(float (&v)[KA], const float (&w)[KA], const float sum)
+// Two forms: scale_by_pk takes the reciprocal c itself, scale_pk the sum -- and returns the reciprocal it used, for a
+// caller that hands it on (kCarryScale, fsmc_decode_kernel_body.h).
+template <int KT, int KA> __device__ __forceinline__ void scale_by_pk(float (&v)[KA], const float (&w)[KA], const float c)
 {
   constexpr int K = KT;
-  const float c = 1.0f / sum;
   const f32x2 cc = {c, c};
 #pragma unroll
   for (int k = 0; k < K; k += 2) {
@@ -650,6 +662,12 @@ template <int KT, int KA> __device__ __forceinline__ void scale_pk(float (&v)[KA
       v[k] = w[k] * c;
     }
   }
+}
+template <int KT, int KA> __device__ __forceinline__ float scale_pk(float (&v)[KA], const float (&w)[KA], const float sum)
+{
+  const float c = 1.0f / sum;
+  scale_by_pk<KT, KA>(v, w, c);
+  return c;
 }
 
 // A whole backward step in one piece (the sequence-mode passes and the recomputed rows of beta stride 2).
@@ -910,8 +928,12 @@ __device__ __forceinline__ void dmaToLds(const gf32x4_p src, const void* ldsDst)
 #pragma clang diagnostic pop
 #endif
 
+// `pad`: the value of float K of the row, the first spare float of the last float4 when K is no multiple of four (the
+// other spare floats are 0.f) -- a row of beta stride 2 carries a scaling reciprocal there (kCarryScale,
+// fsmc_decode_kernel_body.h).
 template <int KT, int KA>
-__device__ __forceinline__ void store_vec(const int K, float4* row, const unsigned laneOff, const float (&v)[KA])
+__device__ __forceinline__ void store_vec(const int K, float4* row, const unsigned laneOff, const float (&v)[KA],
+                                          const float pad = 0.f)
 {
   const gchar_p base = uniformPtr(row);
   const int K4 = (K + 3) >> 2;
@@ -919,9 +941,9 @@ __device__ __forceinline__ void store_vec(const int K, float4* row, const unsign
   for (int k4 = 0; k4 < K4; ++k4) {
     float4 o;
     o.x = v[4 * k4];
-    o.y = (4 * k4 + 1 < K) ? v[4 * k4 + 1] : 0.f;
-    o.z = (4 * k4 + 2 < K) ? v[4 * k4 + 2] : 0.f;
-    o.w = (4 * k4 + 3 < K) ? v[4 * k4 + 3] : 0.f;
+    o.y = (4 * k4 + 1 < K) ? v[4 * k4 + 1] : (4 * k4 + 1 == K) ? pad : 0.f;
+    o.z = (4 * k4 + 2 < K) ? v[4 * k4 + 2] : (4 * k4 + 2 == K) ? pad : 0.f;
+    o.w = (4 * k4 + 3 < K) ? v[4 * k4 + 3] : (4 * k4 + 3 == K) ? pad : 0.f;
     // streamed once, read back once: keep it from evicting the model tables out of L2
     const f32x4 ov = {o.x, o.y, o.z, o.w};
     __builtin_nontemporal_store(ov, rowSlot(base, k4, laneOff));
@@ -942,6 +964,14 @@ __device__ __forceinline__ void load_vec(const int K, const float4* row, const u
     if (4 * k4 + 2 < K) v[4 * k4 + 2] = o.z;
     if (4 * k4 + 3 < K) v[4 * k4 + 3] = o.w;
   }
+}
+
+// Float KT of this lane's column of a stored row: what store_vec wrote as `pad` (KT no multiple of four).
+template <int KT> __device__ __forceinline__ float load_pad(const float4* row, const unsigned laneOff)
+{
+  static_assert(KT % 4 != 0, "a row of 4n states has no spare float");
+  const f32x4 ov = __builtin_nontemporal_load(rowSlot(uniformPtr(row), KT >> 2, laneOff));
+  return ov[KT & 3];
 }
 
 // Segment age estimates from the per-state posterior sums of a segment
