@@ -20,8 +20,10 @@
 
 #include "fsmc_identify.h"
 #include "fsmc_instances.h"
+#include "fsmc_model_tables.h"
 #include "fsmc_pair_bins.h"
 #include "fsmc_pair_cdf.h"
+#include "fsmc_pair_layout.h"
 #include "fsmc_pair_tail.h"
 #include "fsmc_pair_minima.h"
 #include "fsmc_pair_posteriors.h"
@@ -294,14 +296,10 @@ template <typename T> int upload(fsmc_ctx* ctx, T** dst, const T* src, size_t n)
   return FSMC_OK;
 }
 
-// rows padded to KP floats so that every table row starts 16-byte aligned
-std::vector<float> padRows(const float* src, size_t rows, int K, int KP)
+// A host table on its way to the device.
+template <typename T> int upload(fsmc_ctx* ctx, T** dst, const std::vector<T>& table)
 {
-  std::vector<float> out(rows * (size_t)KP, 0.f);
-  for (size_t r = 0; r < rows; ++r) {
-    std::memcpy(&out[r * KP], src + r * K, sizeof(float) * (size_t)K);
-  }
-  return out;
+  return upload(ctx, dst, table.data(), table.size());
 }
 
 using KernelFn = void (*)(const KParams);
@@ -571,6 +569,7 @@ plan::Diag readDiag()
   d.maxSlots = envCount("FSMC_DIAG_MAX_SLOTS");
   d.wavesPerCU = envCount("FSMC_DIAG_WAVES_PER_CU");
   d.sumsSlots = envCount("FSMC_DIAG_SUMS_SLOTS");
+  d.minimaRange = envCount("FSMC_DIAG_MINIMA_RANGE");
   if (const char* v = std::getenv("FSMC_DIAG_WS_FREE")) {
     d.wsFree = std::strtoull(v, nullptr, 10);
   }
@@ -628,6 +627,7 @@ hipError_t workgroupsPerCU(const KernelChoice& k, int most, int capDivisor, int&
 }
 
 static_assert(plan::kWave == kWave && plan::kFloat4Bytes == sizeof(float4), "fsmc_plan.h lays rows out for the kernels' wave");
+static_assert(layout::kSpecBytes == sizeof(PairCdfSpec), "fsmc_pair_layout.h sizes pcSpec for the kernels' PairCdfSpec");
 
 // A launch: its plan (fsmc_plan.h) and the kernel it was planned for.
 struct LaunchPlan : plan::LaunchPlan {
@@ -1594,139 +1594,50 @@ int fsmc_model_create(fsmc_ctx* ctx, const fsmc_model_desc* d, fsmc_model** out)
     return fail(ctx, FSMC_EINVAL, "null argument");
   }
   *out = nullptr;
-  if (d->K < 2 || d->S < 1 || d->n_rows < 1) {
-    return fail(ctx, FSMC_EINVAL, "need K >= 2, S >= 1, n_rows >= 1");
-  }
-  if (d->K > kMaxStatesAny) {
-    return fail(ctx, FSMC_EUNSUPPORTED, "more than " + std::to_string(kMaxStatesAny) + " states");
-  }
-  if (!d->pi || !d->col_ratios || !d->exp_times || !d->D || !d->B || !d->U || !d->RR || !d->step_row || !d->e1 ||
-      !d->e0m1 || !d->e2m0) {
-    return fail(ctx, FSMC_EINVAL, "null table pointer in model description");
-  }
-  if (d->state_threshold > (uint32_t)d->K || d->age_threshold > (uint32_t)d->K) {
-    return fail(ctx, FSMC_EINVAL, "state/age threshold larger than K");
-  }
-  const bool seq = d->sequence != 0;
-  if (seq && (!d->gap_row_f || !d->site_row_f || !d->gap_row_b || !d->site_row_b || !d->hom)) {
-    return fail(ctx, FSMC_EINVAL, "sequence mode needs gap_row_f, site_row_f, gap_row_b, site_row_b and hom");
-  }
-  const int32_t* rowArrays[5] = {d->step_row, seq ? d->gap_row_f : nullptr, seq ? d->site_row_f : nullptr,
-                                 seq ? d->gap_row_b : nullptr, seq ? d->site_row_b : nullptr};
-  static const char* const rowNames[5] = {"step_row", "gap_row_f", "site_row_f", "gap_row_b", "site_row_b"};
-  for (int a = 0; a < 5; ++a) {
-    for (int32_t s = 1; rowArrays[a] && s < d->S; ++s) {
-      if (rowArrays[a][s] < 0 || rowArrays[a][s] >= d->n_rows) {
-        return fail(ctx, FSMC_EINVAL,
-                    std::string(rowNames[a]) + "[" + std::to_string(s) + "] outside the transition tables");
-      }
-    }
+  std::string why;
+  const int checked = model::checkDesc(*d, why);
+  if (checked != FSMC_OK) {
+    return fail(ctx, checked, why);
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   fsmc_model* m = new (std::nothrow) fsmc_model();
   if (!m) {
     return fail(ctx, FSMC_ENOMEM, "host allocation failed");
   }
+  const model::Shape shape = model::shapeOf(d->K, readDiag(), builtW2Members());
   m->ctx = ctx;
   m->K = d->K;
-  m->KP = (d->K + kKPad - 1) / kKPad * kKPad; // rows zero padded to whole operand blocks of any tunable width
-  if (d->K > 128 && d->K <= kMaxStatesW2) {
-    // wide models: NW waves per group hold KP / NW states each (fsmc_kernels_w2.h); the padding states are ghosts
-    const plan::W2Member w = plan::w2Member(d->K, readDiag(), builtW2Members());
-    m->w2NW = w.NW;
-    m->KP = w.NW * w.KH;
-  }
+  m->KP = shape.KP;
+  m->w2NW = shape.w2NW;
   m->S = d->S;
   m->nRows = d->n_rows;
   m->stateThr = d->state_threshold;
   m->ageThr = d->age_threshold;
   m->probThr = d->probability_threshold;
-  const int K = m->K, KP = m->KP;
-  int rc = FSMC_OK;
-  auto up = [&](float** dst, const float* src, size_t rows) {
-    if (rc == FSMC_OK) {
-      std::vector<float> padded = padRows(src, rows, K, KP);
-      rc = upload(ctx, dst, padded.data(), padded.size());
+  m->sequence = d->sequence != 0;
+  // fsmc_model_tables.h builds, this uploads: one table at a time, each gone from the host before the next is built
+  auto uploadTables = [&]() -> int {
+    const int K = m->K, KP = m->KP;
+    const size_t rows = (size_t)d->n_rows;
+    FSMC_TRY(upload(ctx, &m->pi, model::padRows(d->pi, 1, K, KP)));
+    FSMC_TRY(upload(ctx, &m->cR, model::padRows(d->col_ratios, 1, K, KP)));
+    FSMC_TRY(upload(ctx, &m->expT, model::padRows(d->exp_times, 1, K, KP)));
+    FSMC_TRY(upload(ctx, &m->D, model::padRows(d->D, rows, K, KP)));
+    FSMC_TRY(upload(ctx, &m->B, model::padRows(d->B, rows, K, KP)));
+    FSMC_TRY(upload(ctx, &m->U, model::padRows(d->U, rows, K, KP)));
+    FSMC_TRY(upload(ctx, &m->RR, model::padRows(d->RR, rows, K, KP)));
+    FSMC_TRY(upload(ctx, &m->rowSets, model::rowSets(d->D, d->B, d->U, d->RR, rows, K, KP)));
+    FSMC_TRY(upload(ctx, &m->ghostMask, model::ghostMask(K, KP)));
+    // the kernel's "stepRow" is the (forward) site step: step_row in array mode, site_row_f in sequence mode
+    FSMC_TRY(upload(ctx, &m->stepRow, model::stepRows(m->sequence ? d->site_row_f : d->step_row, d->S)));
+    if (m->sequence) {
+      FSMC_TRY(upload(ctx, &m->rowGapF, model::stepRows(d->gap_row_f, d->S)));
+      FSMC_TRY(upload(ctx, &m->rowSiteB, model::stepRows(d->site_row_b, d->S)));
+      FSMC_TRY(upload(ctx, &m->rowGapB, model::stepRows(d->gap_row_b, d->S)));
     }
+    return upload(ctx, (float**)&m->emis3, model::emissions(*d, KP));
   };
-  up(&m->pi, d->pi, 1);
-  up(&m->cR, d->col_ratios, 1);
-  up(&m->expT, d->exp_times, 1);
-  up(&m->D, d->D, (size_t)d->n_rows);
-  up(&m->B, d->B, (size_t)d->n_rows);
-  up(&m->U, d->U, (size_t)d->n_rows);
-  up(&m->RR, d->RR, (size_t)d->n_rows);
-  if (rc == FSMC_OK) {
-    // RowSet copy for the packed steps: the rows of one key side by side so that one base register and
-    // immediate offsets address all of them.  Ush is U moved up one state: the packed beta step multiplies
-    // vec[k] = beta[k]*e[k] by U[k-1] (the term U[k-1]*vec[k] of BU[k-1], HMM.cpp:986-1005).
-    const size_t n = (size_t)d->n_rows;
-    std::vector<float> rs(n * kRowSetParts * (size_t)KP, 0.f);
-    for (size_t r = 0; r < n; ++r) {
-      float* q = &rs[r * kRowSetParts * KP];
-      for (int k = 0; k < K; ++k) {
-        q[kRowD * KP + k] = d->D[r * K + k];
-        q[kRowB * KP + k] = d->B[r * K + k];
-        q[kRowU * KP + k] = d->U[r * K + k];
-        q[kRowRR * KP + k] = d->RR[r * K + k];
-        if (k >= 1) {
-          q[kRowUsh * KP + k] = d->U[r * K + (k - 1)];
-        }
-      }
-    }
-    rc = upload(ctx, &m->rowSets, rs.data(), rs.size());
-  }
-  if (rc == FSMC_OK) {
-    std::vector<float> mask((size_t)KP, 0.f);
-    std::fill(mask.begin(), mask.begin() + K, 1.0f);
-    rc = upload(ctx, &m->ghostMask, mask.data(), mask.size());
-  }
-  m->sequence = seq;
-  auto upRows = [&](int** dst, const int32_t* src) {
-    if (rc == FSMC_OK) {
-      std::vector<int> rows(src, src + d->S);
-      rows[0] = 0;
-      rc = upload(ctx, dst, rows.data(), rows.size());
-    }
-  };
-  // the kernel's "stepRow" is the (forward) site step: step_row in array mode, site_row_f in sequence mode
-  upRows(&m->stepRow, seq ? d->site_row_f : d->step_row);
-  if (seq) {
-    upRows(&m->rowGapF, d->gap_row_f);
-    upRows(&m->rowSiteB, d->site_row_b);
-    upRows(&m->rowGapB, d->gap_row_b);
-  }
-  if (rc == FSMC_OK) {
-    // The reference evaluates e = (e1 + e0m1*isZero) + e2m0*isTwo with isZero/isTwo in {0,1}
-    // (HMM.cpp:827-828, 959-961).  The three reachable (isZero,isTwo) combinations are tabulated
-    // here with the same fp32 expression, so the kernel's row select is bit-identical.
-    // Sequence mode adds a fourth row per site: the homozygous emission of the gap before it, which the reference
-    // passes as all three emission vectors with all-zero observations (HMM.cpp:764-766): (h + h*0) + h*0.
-    const int NC = seq ? 4 : 3;
-    std::vector<float> emis((size_t)d->S * NC * KP, 0.f);
-    static const float zs[3] = {0.f, 1.f, 1.f};
-    static const float ts[3] = {0.f, 0.f, 1.f};
-    for (int32_t s = 0; s < d->S; ++s) {
-      for (int c = 0; c < 3; ++c) {
-        float* dst = &emis[((size_t)s * NC + c) * KP];
-        const volatile float z = zs[c];
-        const volatile float t = ts[c];
-        for (int k = 0; k < K; ++k) {
-          const size_t i = (size_t)s * K + k;
-          dst[k] = d->e1[i] + d->e0m1[i] * z + d->e2m0[i] * t;
-        }
-      }
-      if (seq) {
-        float* dst = &emis[((size_t)s * NC + 3) * KP];
-        const volatile float zero = 0.f;
-        for (int k = 0; k < K; ++k) {
-          const float h = d->hom[(size_t)s * K + k];
-          dst[k] = h + h * zero + h * zero;
-        }
-      }
-    }
-    rc = upload(ctx, (float**)&m->emis3, emis.data(), emis.size());
-  }
+  const int rc = uploadTables();
   if (rc != FSMC_OK) {
     fsmc_model_destroy(m);
     return rc;
@@ -1780,26 +1691,10 @@ int fsmc_worklist_upload(fsmc_ctx* ctx, const fsmc_pair* pairs, size_t n_pairs, 
   if (!ctx || !pairs || !groups || n_pairs == 0 || n_groups == 0) {
     return fail(ctx, FSMC_EINVAL, "null or empty work list");
   }
-  if (n_pairs > 0xFFFFFFF0ull) {
-    return fail(ctx, FSMC_EINVAL, "too many pairs for one work list");
-  }
-  size_t covered = 0;
-  for (size_t g = 0; g < n_groups; ++g) {
-    const fsmc_group& G = groups[g];
-    if (G.n_pairs < 1 || G.n_pairs > (uint32_t)kWave) {
-      return fail(ctx, FSMC_EINVAL, "group " + std::to_string(g) + ": n_pairs must be 1..64");
-    }
-    if (G.first_pair != covered) {
-      return fail(ctx, FSMC_EINVAL, "group " + std::to_string(g) + ": groups must partition the pair list in order");
-    }
-    if (!(G.from < G.to) || !(G.from <= G.scan_from && G.scan_from < G.scan_to && G.scan_to <= G.to)) {
-      return fail(ctx, FSMC_EINVAL, "group " + std::to_string(g) + ": need from <= scan_from < scan_to <= to");
-    }
-    covered += G.n_pairs;
-  }
-  if (covered != n_pairs) {
-    return fail(ctx, FSMC_EINVAL, "groups cover " + std::to_string(covered) + " pairs, list has " +
-                                      std::to_string(n_pairs));
+  std::string why;
+  const int checked = model::checkWorklist(n_pairs, groups, n_groups, why);
+  if (checked != FSMC_OK) {
+    return fail(ctx, checked, why);
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   int rc = upload(ctx, &ctx->dPairs, pairs, n_pairs);
@@ -2387,31 +2282,32 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
   }
   const size_t K = (size_t)m->K, S = (size_t)m->S;
   const size_t plane = K * S;                      // floats of one pair's table, and of the sum
-  const size_t groupBytes = (size_t)kWave * plane * sizeof(float); // a group in the staging buffer; its rows at most
   const bool wantRows = post_rows != nullptr;
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kModeDump, kSlicePosteriors, ctx->ppStage.bytes + ctx->ppRows.bytes,
-                      groupBytes * (wantRows ? 2 : 1), ws));
+                      layout::posteriorsGroupBytes(K, S, wantRows), ws));
+  const layout::Posteriors L = layout::posteriors(K, S, wantRows, ws.slice, ws.slicePairsMax);
   FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
-  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * groupBytes));
-  FSMC_TRY(ensure(ctx, ctx->ppAcc, (K + plane) * sizeof(float)));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, L.stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppAcc, L.accBytes));
   if (wantRows) {
-    FSMC_TRY(ensure(ctx, ctx->ppRows, ws.slicePairsMax * plane * sizeof(float)));
+    FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
   }
   // The way out for the rows: whole pairs a copy -- what a pinned buffer holds, one pair's table at least.
-  const size_t rowBytes = plane * sizeof(float);
+  const size_t rowBytes = L.rowBytes;
   const size_t pairsPerCopy = std::max<size_t>(1, std::min<size_t>(rowCopyBytes() / rowBytes, ws.slicePairsMax));
   if (wantRows) {
     FSMC_TRY(ensureRowCopies(ctx, pairsPerCopy * rowBytes));
   }
 
-  float* const dCoal = (float*)ctx->ppAcc.p;
-  float* const dSum = dCoal + K;
+  char* const acc = (char*)ctx->ppAcc.p;
+  float* const dCoal = (float*)(acc + L.offCoal);
+  float* const dSum = (float*)(acc + L.offSum);
   KParams p;
   FSMC_TRY(dumpSetup(ctx, m, ws, p));
   FSMC_HIP(ctx, hipMemcpyAsync(dCoal, exp_coal_times, K * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (sum) {
-    FSMC_HIP(ctx, hipMemcpyAsync(dSum, sum, plane * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FSMC_HIP(ctx, hipMemcpyAsync(dSum, sum, rowBytes, hipMemcpyHostToDevice, ctx->stream)); // (the sum is one table)
   }
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
@@ -2447,7 +2343,7 @@ int fsmc_decode_pair_posteriors(fsmc_ctx* ctx, const fsmc_model* m, const float*
   FSMC_TRY(decodeSlicesDrained(ctx, ws, p, wantRows, reduce, drain));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (sum) {
-    FSMC_HIP(ctx, hipMemcpy(sum, dSum, plane * sizeof(float), hipMemcpyDeviceToHost));
+    FSMC_HIP(ctx, hipMemcpy(sum, dSum, rowBytes, hipMemcpyDeviceToHost));
   }
   ctx->pairSlices[kSlicePosteriors].last = (int)ws.nSlices;
   return FSMC_OK;
@@ -2473,30 +2369,22 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
   }
   const size_t S = (size_t)m->S;
   const int nOut = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
-  const size_t groupBytes = (size_t)kWave * S * sizeof(float) * (size_t)nOut; // a full group's rows in the staging buffer
   WorkSlices ws;
-  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceMinima, ctx->ppStage.bytes, groupBytes, ws));
-  // The ranges: a wave owns 64 sites of one range.  A large slice is cut so that every SIMD of the chip gets a few waves
-  // (4 x 4 x CUs of them over the site blocks), a range no shorter than 16 pairs: the partials stay a small fraction of
-  // the rows.  FSMC_DIAG_MINIMA_RANGE=<pairs> -- tests: several ranges on a small problem.
-  const size_t siteBlocks = (S + kWave - 1) / kWave;
-  const size_t wavesWanted = (size_t)16 * (size_t)ctx->nCU;
-  const size_t rangesWanted = std::max<size_t>(1, (wavesWanted + siteBlocks - 1) / siteBlocks);
-  size_t rangeLen = std::max<size_t>(16, (ws.slicePairsMax + rangesWanted - 1) / rangesWanted);
-  rangeLen = loweredByEnv("FSMC_DIAG_MINIMA_RANGE", rangeLen);
-  const size_t rangesMax = (ws.slicePairsMax + rangeLen - 1) / rangeLen;
-  if (rangesMax * siteBlocks > (size_t)INT32_MAX) {
+  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceMinima, ctx->ppStage.bytes, layout::minimaGroupBytes(S, (size_t)nOut),
+                      ws));
+  // the buffers and the ranges a slice is reduced in (a wave owns 64 sites of one range)
+  const layout::Minima L = layout::minima(ctx->nCU, S, (size_t)m->KP, (size_t)nOut, ws.slicePairsMax, readDiag());
+  if (L.tooManyRanges) {
     return fail(ctx, FSMC_EINVAL, "too many ranges for one launch (FSMC_DIAG_MINIMA_RANGE)");
   }
+  const size_t siteBlocks = L.siteBlocks, rangeLen = L.rangeLen, vec = L.vec;
 
-  const size_t coalBytes = (size_t)m->KP * sizeof(float);
-  const size_t vec = S * sizeof(float); // one [S] vector of floats or int32s
-  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slicePairsMax * S * sizeof(float) * (size_t)nOut));
-  FSMC_TRY(ensure(ctx, ctx->pmAcc, coalBytes + 4 * vec + 4 * rangesMax * vec));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, L.stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->pmAcc, L.accBytes));
   char* const acc = (char*)ctx->pmAcc.p;
   KParams p;
-  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc, wantMean, wantMap, ws, p));
-  void* const dState[4] = {acc + coalBytes, acc + coalBytes + vec, acc + coalBytes + 2 * vec, acc + coalBytes + 3 * vec};
+  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc + L.offCoal, wantMean, wantMap, ws, p));
+  void* const dState[4] = {acc + L.offState[0], acc + L.offState[1], acc + L.offState[2], acc + L.offState[3]};
   void* const hState[4] = {min_mean, argmin_mean, min_map, argmin_map};
   if (pair_base > 0) { // the chain continues: the caller's arrays are its state
     for (int i = 0; i < 4; ++i) {
@@ -2507,16 +2395,15 @@ int fsmc_decode_pair_minima(fsmc_ctx* ctx, const fsmc_model* m, const float* exp
   }
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  char* const parts = acc + coalBytes + 4 * vec;
   PairMinimaParams q;
   q.mean = ws.stageMean;
   q.map = ws.stageMap;
   q.S = m->S;
   q.rangeLen = (int)rangeLen;
-  q.partMinMean = (float*)parts;
-  q.partArgMean = (int*)(parts + rangesMax * vec);
-  q.partMinMap = (int*)(parts + 2 * rangesMax * vec);
-  q.partArgMap = (int*)(parts + 3 * rangesMax * vec);
+  q.partMinMean = (float*)(acc + L.offParts[0]);
+  q.partArgMean = (int*)(acc + L.offParts[1]);
+  q.partMinMap = (int*)(acc + L.offParts[2]);
+  q.partArgMap = (int*)(acc + L.offParts[3]);
   q.minMean = (float*)dState[0];
   q.argMean = (int*)dState[1];
   q.minMap = (int*)dState[2];
@@ -2567,41 +2454,36 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   const size_t S = (size_t)m->S, B = n_bins;
   const int nRows = (wantMean ? 1 : 0) + (wantMap ? 1 : 0);
   void* const hOut[5] = {bin_mean, bin_min_mean, bin_argmin_mean, bin_min_map, bin_argmin_map};
+  bool want[5];
   size_t nOut = 0;
-  for (void* o : hOut) {
-    nOut += o ? 1 : 0;
+  for (int i = 0; i < 5; ++i) {
+    want[i] = hOut[i] != nullptr;
+    nOut += want[i] ? 1 : 0;
   }
-  // a full group's rows in the staging buffer and its cells in the output buffer
-  const size_t groupBytes = (size_t)kWave * sizeof(float) * (S * (size_t)nRows + B * nOut);
   WorkSlices ws;
-  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceBins, ctx->ppStage.bytes + ctx->pbAcc.bytes, groupBytes, ws));
+  FSMC_TRY(planSlices(ctx, m, kModePerPair, kSliceBins, ctx->ppStage.bytes + ctx->pbAcc.bytes,
+                      layout::binsGroupBytes(S, B, (size_t)nRows, nOut), ws));
   if (ws.slicePairsMax > (size_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_bins_slice)");
   }
 
-  const size_t coalBytes = (size_t)m->KP * sizeof(float);
-  const size_t edgeBytes = (B + 1) * sizeof(int32_t);
-  const size_t outBytes = ws.slicePairsMax * B * sizeof(float); // one output of the largest slice
-  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slicePairsMax * S * sizeof(float) * (size_t)nRows));
-  FSMC_TRY(ensure(ctx, ctx->pbAcc, coalBytes + edgeBytes + nOut * outBytes));
+  const layout::Bins L = layout::bins(S, (size_t)m->KP, B, (size_t)nRows, want, ws.slicePairsMax);
+  FSMC_TRY(ensure(ctx, ctx->ppStage, L.stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->pbAcc, L.accBytes));
   char* const acc = (char*)ctx->pbAcc.p;
   KParams p;
-  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc, wantMean, wantMap, ws, p));
-  FSMC_HIP(ctx, hipMemcpyAsync(acc + coalBytes, bin_edges, edgeBytes, hipMemcpyHostToDevice, ctx->stream));
+  FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc + L.offCoal, wantMean, wantMap, ws, p));
+  FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, L.edgeBytes, hipMemcpyHostToDevice, ctx->stream));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
   void* dOut[5];
-  {
-    char* next = acc + coalBytes + edgeBytes;
-    for (int i = 0; i < 5; ++i) {
-      dOut[i] = hOut[i] ? next : nullptr;
-      next += hOut[i] ? outBytes : 0;
-    }
+  for (int i = 0; i < 5; ++i) {
+    dOut[i] = want[i] ? acc + L.offOut[i] : nullptr;
   }
   PairBinsParams q;
   q.mean = ws.stageMean;
   q.map = ws.stageMap;
-  q.edges = (const int*)(acc + coalBytes);
+  q.edges = (const int*)(acc + L.offEdges);
   q.S = m->S;
   q.B = (int)B;
   q.binMean = (float*)dOut[0];
@@ -2660,9 +2542,8 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
                                       std::to_string(m->K) + ")");
   }
   const size_t B = bin_mant ? n_bins : 0;
-  const size_t groupBytes = (size_t)kWave * (sizeof(double) + sizeof(int32_t)) * (1 + B);
   WorkSlices ws;
-  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceLoglik, ctx->plAcc.bytes, groupBytes, ws));
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceLoglik, ctx->plAcc.bytes, layout::loglikGroupBytes(B), ws));
   int perCU = 0;
   const hipError_t eo = workgroupsPerCU(kern.k, 8, 1, perCU);
   if (eo != hipSuccess) {
@@ -2673,14 +2554,11 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
   plan.slots = (int)std::max<size_t>(1, std::min((size_t)ctx->nCU * (size_t)std::max(perCU, 1), ws.slice));
 
   // [mant][bin mant] doubles, [expo][bin expo] ints of the largest slice, then the edges
-  const size_t n = ws.slicePairsMax;
-  const size_t offBinMant = n * sizeof(double), offExpo = offBinMant + n * B * sizeof(double),
-               offBinExpo = offExpo + n * sizeof(int32_t), offEdges = offBinExpo + n * B * sizeof(int32_t);
-  FSMC_TRY(ensure(ctx, ctx->plAcc, offEdges + (B + 1) * sizeof(int32_t)));
+  const layout::Loglik L = layout::loglik(B, ws.slicePairsMax);
+  FSMC_TRY(ensure(ctx, ctx->plAcc, L.accBytes));
   char* const acc = (char*)ctx->plAcc.p;
   if (B) {
-    FSMC_HIP(ctx, hipMemcpyAsync(acc + offEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 ctx->stream));
+    FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, L.edgeBytes, hipMemcpyHostToDevice, ctx->stream));
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   FwdParams p;
@@ -2688,21 +2566,21 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
   fillSweepParams(ctx, m, p);
   p.B = (int)B;
   p.rowGapF = m->rowGapF;
-  p.edges = B ? (const int*)(acc + offEdges) : nullptr;
-  p.mant = mant ? (double*)acc : nullptr;
-  p.expo = mant ? (int*)(acc + offExpo) : nullptr;
-  p.binMant = B ? (double*)(acc + offBinMant) : nullptr;
-  p.binExpo = B ? (int*)(acc + offBinExpo) : nullptr;
+  p.edges = B ? (const int*)(acc + L.offEdges) : nullptr;
+  p.mant = mant ? (double*)(acc + L.offMant) : nullptr;
+  p.expo = mant ? (int*)(acc + L.offExpo) : nullptr;
+  p.binMant = B ? (double*)(acc + L.offBinMant) : nullptr;
+  p.binExpo = B ? (int*)(acc + L.offBinExpo) : nullptr;
   recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     // the slice's values go to the caller before the next slice overwrites them (12 bytes a pair and output)
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc, sizeof(double)));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + offExpo, sizeof(int32_t)));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_mant, acc + offBinMant, B * sizeof(double)));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_expo, acc + offBinExpo, B * sizeof(int32_t)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc + L.offMant, sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + L.offExpo, sizeof(int32_t)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_mant, acc + L.offBinMant, B * sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, bin_expo, acc + L.offBinExpo, B * sizeof(int32_t)));
   }
   ctx->pairSlices[kSliceLoglik].last = (int)ws.nSlices;
   return FSMC_OK;
@@ -2735,17 +2613,16 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
     return fail(ctx, FSMC_EUNSUPPORTED, "per-pair Viterbi paths: no kernel for this model");
   }
   const size_t S = (size_t)m->S;
-  const size_t pairBytes = (states ? S : 0) + (mant ? sizeof(double) + sizeof(int32_t) : 0);
   WorkSlices ws;
-  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceViterbi, ctx->ppRows.bytes + ctx->pvAcc.bytes, (size_t)kWave * pairBytes,
-                      ws));
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceViterbi, ctx->ppRows.bytes + ctx->pvAcc.bytes,
+                      layout::viterbiGroupBytes(S, states != nullptr, mant != nullptr), ws));
   const size_t n = ws.slicePairsMax;
-  const size_t offExpo = n * sizeof(double);
+  const layout::Viterbi L = layout::viterbi(S, states != nullptr, mant != nullptr, n);
   if (states) {
-    FSMC_TRY(ensure(ctx, ctx->ppRows, (n * S + 3) / 4 * 4));
+    FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
   }
   if (mant) {
-    FSMC_TRY(ensure(ctx, ctx->pvAcc, offExpo + n * sizeof(int32_t)));
+    FSMC_TRY(ensure(ctx, ctx->pvAcc, L.accBytes));
   }
   const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), n * S));
   if (states) {
@@ -2770,8 +2647,8 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
   p.ws = (char*)ctx->ws.p;
   p.slotBytes = plan.wsSlot * sizeof(float4);
   p.states = states ? (unsigned char*)ctx->ppRows.p : nullptr;
-  p.mant = mant ? (double*)acc : nullptr;
-  p.expo = mant ? (int*)(acc + offExpo) : nullptr;
+  p.mant = mant ? (double*)(acc + L.offMant) : nullptr;
+  p.expo = mant ? (int*)(acc + L.offExpo) : nullptr;
   recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
@@ -2789,8 +2666,8 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
     }
     // the slice's values go to the caller before the next slice overwrites them
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc, sizeof(double)));
-    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + offExpo, sizeof(int32_t)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, mant, acc + L.offMant, sizeof(double)));
+    FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + L.offExpo, sizeof(int32_t)));
   }
   ctx->pairSlices[kSliceViterbi].last = (int)ws.nSlices;
   return FSMC_OK;
@@ -2837,25 +2714,23 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "per-pair tails and quantiles"));
   const size_t K = (size_t)m->K, S = (size_t)m->S, nOut = spec.size();
-  const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
-  const size_t groupBytes = stageBytes + (size_t)kWave * S * sizeof(float) * nOut; // ... and its rows, at most
-  const size_t siteBlocks = (S + kWave - 1) / kWave;
+  const size_t siteBlocks = layout::siteBlocks(S);
   WorkSlices ws;
-  FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceCdf, ctx->ppStage.bytes + ctx->ppRows.bytes, groupBytes, ws,
-                      (size_t)INT32_MAX / siteBlocks));
-  const size_t outCells = ws.slicePairsMax * S; // cells of one output of the largest slice
+  FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceCdf, ctx->ppStage.bytes + ctx->ppRows.bytes,
+                      layout::cdfGroupBytes(K, S, nOut), ws, layout::sliceMostBySiteBlocks(S)));
+  const layout::Cdf L = layout::cdf(K, S, nOut, ws.slice, ws.slicePairsMax);
+  const size_t outCells = L.outCells; // cells of one output of the largest slice
   FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
-  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * stageBytes));
-  FSMC_TRY(ensure(ctx, ctx->ppRows, nOut * outCells * sizeof(float)));
-  FSMC_TRY(ensure(ctx, ctx->pcSpec, nOut * sizeof(PairCdfSpec)));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, L.stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
+  FSMC_TRY(ensure(ctx, ctx->pcSpec, L.specBytes));
   // the way out: cells a copy -- what a pinned buffer holds, or one output of the largest slice if that is smaller
   const size_t cellsPerCopy = std::min(std::max<size_t>(1, rowCopyBytes() / sizeof(float)), outCells);
   FSMC_TRY(ensureRowCopies(ctx, cellsPerCopy * sizeof(float)));
 
   KParams p;
   FSMC_TRY(dumpSetup(ctx, m, ws, p));
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nOut * sizeof(PairCdfSpec), hipMemcpyHostToDevice,
-                               ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), L.specBytes, hipMemcpyHostToDevice, ctx->stream));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
   PairCdfParams q;
@@ -2935,36 +2810,31 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "tail summaries"));
   const size_t K = (size_t)m->K, S = (size_t)m->S, nT = n_tail, B = wantBins ? n_bins : 0;
-  const size_t nBinOut = (bin_tail_mean ? 1 : 0) + (bin_tail_length ? 1 : 0);
-  const size_t stageBytes = (size_t)kWave * K * S * sizeof(float); // a group in the staging buffer
-  // ... and its rows and its cells in the output buffer
-  const size_t groupBytes = stageBytes + (size_t)kWave * sizeof(float) * nT * (S + B * nBinOut);
-  const size_t siteBlocks = (S + kWave - 1) / kWave;
+  const bool wantMean = bin_tail_mean != nullptr, wantLength = bin_tail_length != nullptr;
+  const size_t siteBlocks = layout::siteBlocks(S);
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceTail, ctx->ppStage.bytes + ctx->ppRows.bytes + ctx->ptAcc.bytes,
-                      groupBytes, ws, (size_t)INT32_MAX / siteBlocks));
+                      layout::tailGroupBytes(K, S, nT, B, wantMean, wantLength), ws, layout::sliceMostBySiteBlocks(S)));
   if (ws.slicePairsMax > (size_t)INT32_MAX) {
     return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_tail_slice)");
   }
-  const size_t sumBytes = nT * S * sizeof(double);
-  const size_t edgeBytes = wantBins ? ((B + 1) * sizeof(int32_t) + 7) / 8 * 8 : 0;
-  const size_t weightBytes = bin_tail_length ? (S * sizeof(float) + 7) / 8 * 8 : 0;
-  const size_t outBytes = nT * ws.slicePairsMax * B * sizeof(float); // one output of the largest slice, every cut
+  const layout::Tail L = layout::tail(K, S, nT, B, wantMean, wantLength, ws.slice, ws.slicePairsMax);
   FSMC_TRY(ensure(ctx, ctx->aux, ws.slice * sizeof(size_t)));
-  FSMC_TRY(ensure(ctx, ctx->ppStage, ws.slice * stageBytes));
-  FSMC_TRY(ensure(ctx, ctx->ppRows, nT * ws.slicePairsMax * S * sizeof(float)));
-  FSMC_TRY(ensure(ctx, ctx->pcSpec, nT * sizeof(PairCdfSpec)));
-  FSMC_TRY(ensure(ctx, ctx->ptAcc, sumBytes + edgeBytes + weightBytes + nBinOut * outBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppStage, L.stageBytes));
+  FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
+  FSMC_TRY(ensure(ctx, ctx->pcSpec, L.specBytes));
+  FSMC_TRY(ensure(ctx, ctx->ptAcc, L.accBytes));
 
   char* const acc = (char*)ctx->ptAcc.p;
-  double* const dSum = (double*)acc;
-  char* const dEdges = acc + sumBytes;
-  char* const dWeights = dEdges + edgeBytes;
-  float* const dMean = bin_tail_mean ? (float*)(dWeights + weightBytes) : nullptr;
-  float* const dLength = bin_tail_length ? (float*)(dWeights + weightBytes + (bin_tail_mean ? outBytes : 0)) : nullptr;
+  double* const dSum = (double*)(acc + L.offSum);
+  char* const dEdges = acc + L.offEdges;
+  char* const dWeights = acc + L.offWeights;
+  float* const dMean = wantMean ? (float*)(acc + L.offMean) : nullptr;
+  float* const dLength = wantLength ? (float*)(acc + L.offLength) : nullptr;
+  const size_t sumBytes = L.sumBytes;
   KParams p;
   FSMC_TRY(dumpSetup(ctx, m, ws, p));
-  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), nT * sizeof(PairCdfSpec), hipMemcpyHostToDevice, ctx->stream));
+  FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), L.specBytes, hipMemcpyHostToDevice, ctx->stream));
   if (tail_sum) { // the chain continues what the caller passes in
     FSMC_HIP(ctx, hipMemcpyAsync(dSum, tail_sum, sumBytes, hipMemcpyHostToDevice, ctx->stream));
   }

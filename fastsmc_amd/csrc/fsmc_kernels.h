@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "../../include/fastsmc_hip.h"
+#include "fsmc_constants.h"
 
 namespace fsmc
 {
@@ -39,10 +40,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kMaxStates = 256; // the widest model a lane-per-pair or two-workgroups-per-CU member decodes (fsmc_instances.h)
-constexpr int kMaxStatesW2 = 1024; // ... and the wave-group kernel with one workgroup per CU (four waves of 80 states, six to eight of 64;
-                                    // beyond 512 states eight waves of 80 / 96 / 128 without landing zones)
-constexpr int kMaxStatesAny = 4096; // ... and the any-K kernel (fsmc_kernels_any.h: K-vectors in the workspace)
+// (kMaxStates, kMaxStatesW2, kMaxStatesAny -- how wide a model each kernel family takes: fsmc_constants.h)
 
 enum Mode : int { kModeIbd = 0, kModeDump = 1, kModePerPair = 2, kModeSums = 3 };
 
@@ -230,9 +228,7 @@ __device__ __forceinline__ void swait(f32x4& a, f32x4& b, f32x4& c, f32x4& d)
 #endif
 constexpr int kKB = FSMC_KB;   // states per operand block of the beta passes (two tables at a time)
 constexpr int kKBF = FSMC_KBF; // states per operand block of the alpha pass (four tables at a time)
-constexpr int kKPad = 16;      // table / emission rows are zero padded to a multiple of this many floats
-// RowSet: the transition-table rows of one key side by side, [key][5][KP] floats (packed steps)
-enum RowSetPart : int { kRowD = 0, kRowB = 1, kRowU = 2, kRowUsh = 3, kRowRR = 4, kRowSetParts = 5 };
+// (kKPad, the padding of table / emission rows, and RowSetPart, the parts of a RowSet [key][5][KP]: fsmc_constants.h)
 
 __device__ __forceinline__ float pick(const float4& e0, const float4& e1, const int i)
 {

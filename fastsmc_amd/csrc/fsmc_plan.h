@@ -103,6 +103,7 @@ struct Diag {
   double earnScale = 1.0; // FSMC_DIAG_WS_EARN_SCALE -- tests: a small problem that earns like a long job
   bool twoWavesNever = false; // FSMC_DIAG_TWO_WAVE_WINDOWS=never -- tests: the whole suite on the one-wave kernels
   int w2NW = 0, w2KH = 0;     // FSMC_DIAG_W2_MEMBER="<waves>x<states per wave>", parsed (0 x 0: not set or not a pair)
+  long minimaRange = 0; // FSMC_DIAG_MINIMA_RANGE=<pairs> (fsmc_pair_layout.h) -- tests: several ranges on a small problem
 };
 
 // A diagnostic switch that lowers a count: n / divisor where that is at least 1 and below `value`.

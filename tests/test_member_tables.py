@@ -22,8 +22,8 @@ def _w2_member_table():
 def test_wave_group_members_agree_with_the_library_and_the_build():
     steps, last = _w2_member_table()
     assert steps and steps == sorted(steps)
-    kernels = open(os.path.join(CSRC, "fsmc_kernels.h")).read()
-    k_max = int(re.search(r"constexpr int kMaxStatesW2 = (\d+);", kernels).group(1))
+    constants = open(os.path.join(CSRC, "fsmc_constants.h")).read()
+    k_max = int(re.search(r"constexpr int kMaxStatesW2 = (\d+);", constants).group(1))
     built = set((int(nw), int(kh)) for kh, nw in
                 re.findall(r"Y\((\d+), (\d+)\)", re.search(r"#define FSMC_ALL_W2\(Y\)(.*)", open(
                     os.path.join(CSRC, "fsmc_instances.h")).read()).group(1)))
