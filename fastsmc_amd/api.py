@@ -79,7 +79,8 @@ def tail_states(discretization, times) -> np.ndarray:
 
 
 def state_runs(row):
-    """The run-length form of one row of ``per_pair_viterbi_states`` (or of any row of states): ``(starts, ends, states)``,
+    """The run-length form of one row of ``per_pair_viterbi_states`` or of ``per_pair_sampled_states`` (``ASMC.samplePairs``; or
+    of any row of states): ``(starts, ends, states)``,
     three arrays of one entry a run; run ``r`` is sites ``[starts[r], ends[r])``, all in state ``states[r]``, and
     neighbouring runs differ in state.  ``starts[0] = 0`` and ``ends[-1] = len(row)``; an empty row gives three empty
     arrays.  The piecewise-constant TMRCA track of a pair is ``expectedTimes[states]`` over these segments."""

@@ -8,6 +8,7 @@ raise ``FsmcError``.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 
 import numpy as np
@@ -41,6 +42,7 @@ SYMBOLS = [
     "fsmc_decode_pair_tail_summaries", "fsmc_ctx_set_pair_tail_slice", "fsmc_ctx_last_pair_tail_slices",
     "fsmc_decode_pair_loglik", "fsmc_ctx_set_pair_loglik_slice", "fsmc_ctx_last_pair_loglik_slices",
     "fsmc_decode_pair_viterbi", "fsmc_ctx_set_pair_viterbi_slice", "fsmc_ctx_last_pair_viterbi_slices",
+    "fsmc_decode_pair_samples", "fsmc_ctx_set_pair_samples_slice", "fsmc_ctx_last_pair_samples_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -156,6 +158,9 @@ def load():
         L.fsmc_decode_pair_viterbi.argtypes = [vp, vp, vp, vp, vp]
         L.fsmc_ctx_set_pair_viterbi_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_viterbi_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_samples.argtypes = [vp, vp, i32, C.c_uint64, vp]
+        L.fsmc_ctx_set_pair_samples_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_samples_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -570,6 +575,36 @@ class Context:
     def last_pair_viterbi_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_viterbi_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_samples(self, model: "Model", n_samples, seed=0, out=None):
+        """Per pair of the resident work list, ``n_samples`` (1 ... 64) state sequences drawn from the joint posterior over
+        state sequences (fsmc_decode_pair_samples): uint8 [n_pairs][n_samples][S].  A sample depends on (seed, the pair's
+        two haplotypes, the sample's index, the site) and the data only.  ``seed``: 0 ... 2**64 - 1.  ``out``: such an
+        array (at least n_pairs rows), written in place and returned as it is."""
+        n, S = self._n_pairs, model.S
+        n_samples, seed = operator.index(n_samples), operator.index(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed: 0 ... 2**64 - 1")
+        if not -(1 << 31) <= n_samples < 1 << 31:
+            raise ValueError("n_samples: 1 ... 64")
+        rows = min(max(n_samples, 1), 64)  # (outside 1 ... 64 the library refuses the call)
+        if out is None:
+            out = np.zeros((n, rows, S), np.uint8)
+        if (not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous
+                or not out.flags.writeable or out.ndim != 3 or out.shape[1:] != (rows, S) or out.shape[0] < n):
+            raise ValueError("out: a writable C-contiguous uint8 array [>= n_pairs][n_samples][S]")
+        self._check(self._L.fsmc_decode_pair_samples(self._h, model._h, n_samples, seed, _p(out)))
+        return out
+
+    def set_pair_samples_slice(self, groups: int):
+        """Groups fsmc_decode_pair_samples puts through the device at a time; 0 = automatic.  Results do not depend on
+        it."""
+        self._check(self._L.fsmc_ctx_set_pair_samples_slice(self._h, groups))
+
+    def last_pair_samples_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_samples_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):

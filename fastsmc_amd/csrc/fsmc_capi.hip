@@ -81,6 +81,7 @@ enum PairSlicing {
   kSliceTail,
   kSliceLoglik,
   kSliceViterbi,
+  kSliceSamples,
   kPairSlicings
 };
 } // namespace
@@ -698,6 +699,20 @@ int planViterbi(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k,
   }
   plan.k = k;
   return plan::planViterbi(settingsOf(ctx), m->S, k.member, perCU, nGroups, wantStates, budget, plan, why);
+}
+
+// plan::planSamples for the sampling kernel `k`.  Computes only, like planViterbi.
+int planSamples(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups,
+                const plan::WsBudget& budget, LaunchPlan& plan, std::string& why)
+{
+  int perCU = 0;
+  const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
+  if (e != hipSuccess) {
+    why = std::string("occupancy query of the sampling kernel: ") + hipGetErrorString(e);
+    return FSMC_EHIP;
+  }
+  plan.k = k;
+  return plan::planSamples(settingsOf(ctx), m->S, k.member, perCU, nGroups, budget, plan, why);
 }
 
 // Two waves per window (plan::planTwoWaves).  twoWavesWanted: what can be said before the budget is read.
@@ -1578,6 +1593,8 @@ int fsmc_ctx_set_pair_loglik_slice(fsmc_ctx* ctx, uint32_t groups) { return setP
 int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceLoglik, slices); }
 int fsmc_ctx_set_pair_viterbi_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceViterbi, groups); }
 int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceViterbi, slices); }
+int fsmc_ctx_set_pair_samples_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceSamples, groups); }
+int fsmc_ctx_last_pair_samples_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceSamples, slices); }
 
 int fsmc_ctx_last_kernel(const fsmc_ctx* ctx, int32_t* member)
 {
@@ -2670,6 +2687,82 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
     FSMC_TRY(sliceToCaller(ctx, ws, sl, expo, acc + L.offExpo, sizeof(int32_t)));
   }
   ctx->pairSlices[kSliceViterbi].last = (int)ws.nSlices;
+  return FSMC_OK;
+}
+
+// Per pair, n_samples state sequences drawn from the joint posterior (fsmc_pair_samples.h): one launch of sample_kernel
+// a slice, planned by planSamples into the decode's workspace.  A slice's state rows, [pair][sample][S] bytes in ppRows,
+// are one span of the caller's array and leave through drainRows in copies that need not end with a row.  Slices are
+// independent; a slice's rows have left before the next launch.
+int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_samples, uint64_t seed, uint8_t* states)
+{
+  FSMC_TRY(checkReady(ctx, m));
+  if (n_samples < 1 || n_samples > kMaxSamples) {
+    return fail(ctx, FSMC_EINVAL, "sampled paths: n_samples must be 1 ... 64 (" + std::to_string(n_samples) + ")");
+  }
+  if (!states) {
+    return fail(ctx, FSMC_EINVAL, "sampled paths: states is null");
+  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "sampled paths"));
+  if (m->K > 128) {
+    return fail(ctx, FSMC_EINVAL, "sampled paths: no sampling kernel for a model of more than 128 states (" +
+                                      std::to_string(m->K) + ")");
+  }
+  if (m->sequence) {
+    return fail(ctx, FSMC_EINVAL, "sampled paths: no sampling kernel for a sequence-mode model");
+  }
+  const SweepKernel<SmpParams> kern =
+      chooseSweepKernel<SmpParams>(m, [](auto kt) { return sample_kernel<decltype(kt)::value>; });
+  if (!kern.fn) {
+    return fail(ctx, FSMC_EUNSUPPORTED, "sampled paths: no kernel for this model");
+  }
+  const size_t S = (size_t)m->S, nS = (size_t)n_samples;
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceSamples, ctx->ppRows.bytes, layout::samplesGroupBytes(S, nS), ws));
+  const layout::Samples L = layout::samples(S, nS, ws.slicePairsMax);
+  FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
+  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), ws.slicePairsMax * L.pairBytes));
+  FSMC_TRY(ensureRowCopies(ctx, copyBytes));
+  earnWorkspace(ctx, m, kModePerPair);
+  LaunchPlan plan;
+  std::string why;
+  const int rc = planSamples(ctx, m, kern.k, ws.slice, workspaceBudget(ctx, ctx->ws), plan, why);
+  if (rc != FSMC_OK) {
+    return fail(ctx, rc, why);
+  }
+  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+
+  SmpParams p;
+  std::memset(&p, 0, sizeof(p));
+  fillSweepParams(ctx, m, p);
+  p.K = m->K;
+  p.chunk = plan.chunk;
+  p.nChunks = plan.maxChunks;
+  p.nSamples = n_samples;
+  p.seedLo = (unsigned)(seed & 0xffffffffull);
+  p.seedHi = (unsigned)(seed >> 32);
+  p.ws = (char*)ctx->ws.p;
+  p.slotBytes = plan.wsSlot * sizeof(float4);
+  p.states = (unsigned char*)ctx->ppRows.p;
+  recordLaunch(ctx, kern.k, plan);
+
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    const size_t first = ws.firstPair(sl), nP = ws.pairs(sl);
+    FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
+    if (nP > 0) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+      const size_t bytes = nP * L.pairBytes;
+      uint8_t* const dst = states + first * L.pairBytes;
+      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
+      FSMC_TRY(drainRows(
+          ctx, (bytes + copyBytes - 1) / copyBytes,
+          [&](size_t c) { return RowChunk{(const char*)ctx->ppRows.p + c * copyBytes, span(c)}; },
+          [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
+    }
+    // the slice's rows have left before the next slice overwrites them
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  ctx->pairSlices[kSliceSamples].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 

@@ -28,6 +28,8 @@ FSMC_KT_VITERBI_KERNELS(FSMC_DEFINE_KT_VITERBI, FSMC_INSTANCE_KT)
 static_assert(poolBuilt(FSMC_INSTANCE_KT), "the members built with the chunk pool: poolBuilt()");
 FSMC_KT_POOL_KERNELS(FSMC_DEFINE_KT_POOL, FSMC_INSTANCE_KT)
 #endif
+// (behind everything: the sampling kernels; every kernel above keeps its compiled text)
+FSMC_KT_SAMPLE_KERNELS(FSMC_DEFINE_KT_SAMPLE, FSMC_INSTANCE_KT)
 #elif defined(FSMC_INSTANCE_W2)
 #ifndef FSMC_INSTANCE_NW
 #define FSMC_INSTANCE_NW 4

@@ -1,4 +1,4 @@
-// fsmc_pair_layout.h -- where the fsmc_decode_pair_* entry points keep what on the device: for each of the seven, the
+// fsmc_pair_layout.h -- where the fsmc_decode_pair_* entry points keep what on the device: for each of the eight, the
 // bytes a group of the work list takes (what plan::planSlices cuts the list by), and, once the slices are known, the
 // sizes of the staging, row and spec buffers and every region's offset inside the entry point's accumulator buffer.
 //
@@ -169,6 +169,22 @@ inline Viterbi viterbi(size_t S, bool wantStates, bool wantProb, size_t slicePai
   L.offMant = 0;
   L.offExpo = n * sizeof(double);
   L.accBytes = L.offExpo + n * sizeof(int32_t);
+  return L;
+}
+
+// ---- sampled paths: no accumulator; a slice's state rows, [pair][sample][S] bytes, are in ppRows -----------------------
+struct Samples {
+  size_t groupBytes = 0;
+  size_t pairBytes = 0; // one pair's rows
+  size_t rowsBytes = 0; // ppRows: the largest slice's rows, whole dwords
+};
+inline size_t samplesGroupBytes(size_t S, size_t nSamples) { return kLanes * nSamples * S; }
+inline Samples samples(size_t S, size_t nSamples, size_t slicePairsMax)
+{
+  Samples L;
+  L.groupBytes = samplesGroupBytes(S, nSamples);
+  L.pairBytes = nSamples * S;
+  L.rowsBytes = (slicePairsMax * L.pairBytes + 3) / 4 * 4;
   return L;
 }
 

@@ -389,6 +389,51 @@ inline int planViterbi(const Settings& set, int S, int member, int perCU, size_t
   return FSMC_OK;
 }
 
+// The launch of the sampling kernel (fsmc_pair_samples.h) over slices of at most `nGroups` whole-sequence groups of `S`
+// sites.  A wave's workspace is `chunk` rows of forward vectors (KT4 x 64 float4 a site) and a checkpoint of the same
+// size a chunk.  The waves: what is resident, the groups, and what the hard budget holds of the smallest slot any chunk
+// length gives (about sqrt(S) sites a chunk: memory is chunk + S / chunk rows).  The chunk: the caller's
+// (set_chunk_sites), otherwise the whole sequence -- one sweep instead of two -- halved until the waves' slots fit what
+// the context may spend (the soft budget; the hard one for sequences of at most 512 sites, as planViterbi).
+// `member`: the kernel's family member; `perCU`: its workgroups a CU, as queried.
+inline int planSamples(const Settings& set, int S, int member, int perCU, size_t nGroups, const WsBudget& budget,
+                       LaunchPlan& plan, std::string& why)
+{
+  size_t slots = std::max<size_t>(1, std::min((size_t)set.nCU * (size_t)std::max(perCU, 1), nGroups));
+  const size_t L = (size_t)S;
+  const size_t K4 = (size_t)(member + 3) / 4;
+  const size_t row = K4 * kWave * kFloat4Bytes;
+  auto slotBytes = [&](size_t c) { return (c + (L + c - 1) / c) * row; };
+  size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(std::sqrt((double)L))));
+  if (set.chunkSites) {
+    cMin = std::min<size_t>(set.chunkSites, L);
+  }
+  slots = std::min<size_t>(slots, (size_t)(budget.hard / slotBytes(cMin)));
+  if (slots == 0) {
+    why = "workspace limit too small for the forward rows of one wave";
+    return FSMC_ENOMEM;
+  }
+  size_t C = L;
+  if (set.chunkSites) {
+    C = cMin;
+  } else {
+    const uint64_t room = L <= 512 ? budget.hard : budget.soft;
+    while (C > cMin && (uint64_t)slots * slotBytes(C) > room) {
+      C = std::max(cMin, (C + 1) / 2);
+    }
+  }
+  const size_t bytes = slotBytes(C);
+  plan = LaunchPlan();
+  plan.chunk = (int)C;
+  plan.chunkRows = (int)C;
+  plan.maxChunks = (int)((L + C - 1) / C);
+  plan.wsSlot = bytes / kFloat4Bytes;
+  plan.slots = (int)slots;
+  plan.wavesPerWindow = 1;
+  plan.bytes = bytes * slots;
+  return FSMC_OK;
+}
+
 // A launch of the two-waves-per-window kernel, if this one qualifies: `nItems` workgroups (groups; batches of the sums)
 // that are ALL resident at once -- so the launch has at most half as many items as the chip holds waves of this member,
 // the case in which the one-wave kernel leaves every wave alone on a SIMD (or SIMDs idle) -- and whose whole windows fit

@@ -611,6 +611,14 @@ void HMM::setStoreViterbiPaths(bool v)
   setPairOutputs(next);
 }
 
+void HMM::setSampledPaths(int n, unsigned long long seed)
+{
+  PairOutputs next = mOutputs;
+  next.sampledPaths = n;
+  next.sampleSeed = seed;
+  setPairOutputs(next);
+}
+
 // (the rest of the request passed its check when it was set: only the part that changes can be refused)
 void HMM::setSiteBins(const std::vector<int>& edges)
 {
@@ -1015,6 +1023,9 @@ void HMM::flushPairOutputs(size_t nPairs)
   if (o.viterbiPaths) {
     flushPairViterbi(nPairs);
   }
+  if (o.sampledPaths > 0) {
+    flushPairSamples(nPairs);
+  }
   if (o.cdf()) {
     flushPairCdf();
   }
@@ -1120,6 +1131,22 @@ void HMM::flushPairViterbi(size_t nPairs)
     R.perPairViterbiLogProbabilities[i] =
         std::log(R.perPairViterbiMantissas[i]) + static_cast<double>(R.perPairViterbiExponents[i]) * ln2;
   }
+}
+
+// per pair the state sequences drawn from the joint posterior, flush after flush at the pairs written so far: a byte a
+// pair, sample and site crosses the bus.  A sample does not depend on the flush its pair is in.
+void HMM::flushPairSamples(size_t)
+{
+  auto& R = mPairsReturn;
+  const size_t rowBytes = static_cast<size_t>(mOutputs.sampledPaths) * static_cast<size_t>(R.numSites);
+  if (R.request.sampledPaths != mOutputs.sampledPaths ||
+      R.perPairSampledStates.size() != static_cast<size_t>(R.numPairs) * rowBytes) {
+    throw std::runtime_error("the return structure was not initialised for the sampled paths asked for");
+  }
+  check(mCtx,
+        fsmc_decode_pair_samples(mCtx, mModel, mOutputs.sampledPaths, mOutputs.sampleSeed,
+                                 R.perPairSampledStates.data() + R.numWritten * rowBytes),
+        "fsmc_decode_pair_samples");
 }
 
 // per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far: 4 bytes a

@@ -127,6 +127,10 @@ public:
   // per pair the most probable joint state sequence and its probability (mantissa, exponent, logarithm): a max-product
   // sweep and a traceback on the device (fsmc_decode_pair_viterbi); throws for more than 128 states and sequence mode
   void setStoreViterbiPaths(bool v);
+  // per pair n state sequences (1 ... 64; 0 turns this off) drawn from the joint posterior over sequences, forward
+  // filtering with backward sampling on the device (fsmc_decode_pair_samples); a sample depends on the seed, the pair's
+  // two haplotypes, its index and the data only.  Throws for n outside 0 ... 64, more than 128 states and sequence mode
+  void setSampledPaths(int n, unsigned long long seed = 0);
   // per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins of sites
   // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
   // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
@@ -212,6 +216,7 @@ private:
   void flushPairBins();
   void flushPairLogLik(size_t nPairs);
   void flushPairViterbi(size_t nPairs);
+  void flushPairSamples(size_t nPairs);
   void flushPairCdf();
   void flushPairTailSummaries(size_t nPairs);
   void flushPairPosteriors(size_t nPairs);

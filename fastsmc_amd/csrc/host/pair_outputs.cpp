@@ -99,6 +99,16 @@ void PairOutputs::check(long sites, long states, bool sequence) const
   if (viterbiPaths && sequence) {
     throw std::runtime_error("per-pair Viterbi paths: no Viterbi kernel for a sequence-mode model");
   }
+  if (sampledPaths < 0 || sampledPaths > 64) { // (the messages of fsmc_decode_pair_samples)
+    throw std::runtime_error("sampled paths: n_samples must be 1 ... 64 (" + std::to_string(sampledPaths) + ")");
+  }
+  if (sampledPaths && states > 128) {
+    throw std::runtime_error("sampled paths: no sampling kernel for a model of more than 128 states (" +
+                             std::to_string(states) + ")");
+  }
+  if (sampledPaths && sequence) {
+    throw std::runtime_error("sampled paths: no sampling kernel for a sequence-mode model");
+  }
 }
 
 void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs)
@@ -146,6 +156,8 @@ void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states,
   perPairViterbiMantissas.assign(o.viterbiPaths ? nPairs : 0, 0.0);
   perPairViterbiExponents.assign(o.viterbiPaths ? nPairs : 0, 0);
   perPairViterbiLogProbabilities.assign(o.viterbiPaths ? nPairs : 0, 0.0);
+  // the sampled paths: [pairs][samples][sites]
+  perPairSampledStates.assign(o.sampledPaths > 0 ? nPairs * static_cast<size_t>(o.sampledPaths) * S : 0, 0);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()

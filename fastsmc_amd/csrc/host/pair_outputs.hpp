@@ -39,11 +39,16 @@ struct PairOutputs {
   // per pair, the most probable joint state sequence (the Viterbi path) and its probability as mantissa, exponent and
   // logarithm (fsmc_decode_pair_viterbi): models of at most 128 states, array mode
   bool viterbiPaths = false;
+  // per pair, this many state sequences (1 ... 64; 0: none) drawn from the joint posterior over sequences with this seed
+  // (fsmc_decode_pair_samples): models of at most 128 states, array mode
+  int sampledPaths = 0;
+  unsigned long long sampleSeed = 0;
 
   // Throws what the ABI would refuse, with its messages: more than 8 tail states or quantiles, a cut outside [1, states],
   // a quantile outside (0, 1]; then the same for the tail summaries, and weights without cuts, not one a site or not
   // finite; then fewer than two bin edges, edges outside [0, sites] or not strictly ascending; then log-likelihoods of a
-  // model of more than 128 states; then Viterbi paths of a model of more than 128 states or of a sequence-mode model.
+  // model of more than 128 states; then Viterbi paths of a model of more than 128 states or of a sequence-mode model;
+  // then sampled paths outside 0 ... 64, of a model of more than 128 states or of a sequence-mode model.
   void check(long sites, long states, bool sequence = false) const;
 
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
@@ -54,7 +59,8 @@ struct PairOutputs {
   bool any() const
   {
     return means || maps || posteriors || sumOfPosteriors || minMeansOnDevice() || minMapsOnDevice() ||
-           !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods || viterbiPaths;
+           !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods || viterbiPaths ||
+           sampledPaths != 0;
   }
 };
 
@@ -92,6 +98,8 @@ struct DecodePairsReturnStruct {
   std::vector<unsigned char> perPairViterbiStates;
   std::vector<double> perPairViterbiMantissas, perPairViterbiLogProbabilities;
   std::vector<int> perPairViterbiExponents;
+  // state sequences drawn from the joint posterior of each pair, [pairs][samples][sites]
+  std::vector<unsigned char> perPairSampledStates;
   size_t numWritten = 0;
 
   void initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs);

@@ -157,6 +157,31 @@ template <typename Id> void defDecodePairs(py::class_<ASMC>& c, const char* list
       "+ exponent * ln 2.  api.state_runs gives the run-length form of a row.");
 }
 
+// ASMC.samplePairs for one kind of pair list: a decodePairs with the sampled paths as its one output
+template <typename Id> void defSamplePairs(py::class_<ASMC>& c, const char* listA, const char* listB)
+{
+  c.def(
+      "samplePairs",
+      [](ASMC& self, const std::vector<Id>& a, const std::vector<Id>& b, int samples, unsigned long long seed) {
+        PairOutputs o;
+        o.sampledPaths = samples;
+        o.sampleSeed = seed;
+        if (samples == 0) { // (PairOutputs: 0 asks for nothing)
+          throw std::runtime_error("sampled paths: n_samples must be 1 ... 64 (0)");
+        }
+        self.decodePairs(a, b, o);
+      },
+      py::arg(listA), py::arg(listB), "samples"_a = 1, "seed"_a = 0ull,
+      "Decode the listed pairs and draw `samples` (1 ... 64) state sequences per pair from the JOINT posterior over state "
+      "sequences given the pair's observations (forward filtering with backward sampling on the device; models of at "
+      "most 128 states, array mode) into per_pair_sampled_states ([pairs][samples][sites] uint8) of the return "
+      "structure; every other field is empty.  A Viterbi path is one point without spread and the marginals carry no "
+      "dependence between neighbouring sites: these are whole tracks with the right joint law.  A sample depends on "
+      "the seed (0 ... 2**64 - 1), the pair's two haplotypes, the sample's index and the data only: the same call gives "
+      "the same array, whatever the flushes; (a, b) and (b, a) are different streams.  api.state_runs gives the "
+      "run-length form of a row.");
+}
+
 } // namespace
 
 PYBIND11_MODULE(_pyasmc, m)
@@ -235,7 +260,10 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("per_pair_viterbi_states", [](const Pairs& r) { return shaped(r.perPairViterbiStates, r.numPairs, r.numSites); })
       .def_property_readonly("per_pair_viterbi_log_probabilities", [](const Pairs& r) { return shaped(r.perPairViterbiLogProbabilities, r.perPairViterbiLogProbabilities.size()); })
       .def_property_readonly("per_pair_viterbi_mantissas", [](const Pairs& r) { return shaped(r.perPairViterbiMantissas, r.perPairViterbiMantissas.size()); })
-      .def_property_readonly("per_pair_viterbi_exponents", [](const Pairs& r) { return shaped(r.perPairViterbiExponents, r.perPairViterbiExponents.size()); });
+      .def_property_readonly("per_pair_viterbi_exponents", [](const Pairs& r) { return shaped(r.perPairViterbiExponents, r.perPairViterbiExponents.size()); })
+      // state sequences drawn from the joint posterior of each pair (ASMC.samplePairs), [pairs][samples][sites]; empty
+      // where not asked for
+      .def_property_readonly("per_pair_sampled_states", [](const Pairs& r) { return shaped(r.perPairSampledStates, r.numPairs, r.request.sampledPaths, r.numSites); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -499,6 +527,9 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setStoreViterbiPaths", &HMM::setStoreViterbiPaths, "storeViterbiPaths"_a = true,
            "per pair the most probable joint state sequence and its probability (mantissa, exponent, logarithm): a "
            "max-product sweep and a traceback on the device; models of at most 128 states, array mode")
+      .def("setSampledPaths", &HMM::setSampledPaths, "samples"_a, "seed"_a = 0ull,
+           "per pair this many state sequences (1 ... 64; 0 turns it off) drawn from the joint posterior over state "
+           "sequences on the device, forward filtering with backward sampling; models of at most 128 states, array mode")
       .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
            "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
            "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")
@@ -649,6 +680,8 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("decodeAllInJob", &ASMC::decodeAllInJob);
   defDecodePairs<unsigned long>(asmc, "hap_indices_a", "hap_indices_b");
   defDecodePairs<std::string>(asmc, "hap_ids_a", "hap_ids_b");
+  defSamplePairs<unsigned long>(asmc, "hap_indices_a", "hap_indices_b");
+  defSamplePairs<std::string>(asmc, "hap_ids_a", "hap_ids_b");
   asmc.def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

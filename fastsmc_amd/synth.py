@@ -93,14 +93,17 @@ def physical_distance_keys(max_bp: int = 2_000_000) -> np.ndarray:
 
 
 def make_model_tables(K: int = 69, N: float = 15000.0, mu: float = 1.0e-5, csfs_samples: int = 50,
-                      keys: np.ndarray | None = None) -> ModelTables:
+                      keys: np.ndarray | None = None, boundaries: np.ndarray | None = None) -> ModelTables:
     """Constant-size SMC tables (SURVEY.md App. B closed forms), computed in float64 and stored fp32.
+    ``boundaries``: the K + 1 interval boundaries (first 0, last inf) in place of ``discretization(K, N)``.
 
     With h_j = P(coalesce in interval j), s_i the expected time in interval i and r the genetic
     distance: T[i][j>i] = g(s_i) h_j, T[i][j<i] = B[j], T[i][i] = D[i] (rows sum to 1), hence
     U[i] = g(s_i) h_{i+1}, columnRatios[j] = h_{j+1}/h_j, RR[i] = g(s_i)/g(s_{i+1}).
     """
-    d = discretization(K, N)
+    d = discretization(K, N) if boundaries is None else np.asarray(boundaries, dtype=np.float64)
+    if d.shape != (K + 1,) or d[0] != 0.0 or not np.isinf(d[-1]) or np.any(np.diff(d) <= 0):
+        raise ValueError("boundaries: K + 1 ascending values from 0 to inf")
     lo, hi = d[:-1], d[1:]
     ea, eb = np.exp(-lo / N), np.exp(-hi / N)  # eb[-1] == 0
     h = ea - eb

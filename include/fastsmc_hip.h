@@ -34,6 +34,8 @@
  *                             uses every sum for 1.0f / sum and drops it
  *   fsmc_decode_pair_viterbi <- none: the reference decodes marginals only.  The forward step of decodeBatch
  *                             (HMM.cpp:787-830) with max in place of +, back-pointers and a traceback
+ *   fsmc_decode_pair_samples <- none: the reference draws nothing.  The forward half of decodeBatch (HMM.cpp:725-784),
+ *                             then backward sampling with the coefficients of the forward step's term (HMM.cpp:799-830)
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -247,6 +249,11 @@ int fsmc_ctx_last_pair_loglik_slices(const fsmc_ctx* ctx, int32_t* slices);
  * it. */
 int fsmc_ctx_set_pair_viterbi_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_samples.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of outputs (64 * n_samples * S bytes a group).  Results do not depend
+ * on it. */
+int fsmc_ctx_set_pair_samples_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_samples_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -473,6 +480,47 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
  * output; a group that is not the whole sequence (from = 0, to = S); a model of more than 128 states; a sequence-mode
  * model (its half-step doubles the trellis). */
 int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states, double* mant, int32_t* expo);
+
+/* Per pair of the resident work list, n_samples state sequences drawn from the JOINT posterior over state sequences
+ * given the pair's observations: forward filtering with backward sampling (fsmc_pair_samples.h; lane-per-pair kernels:
+ * K <= 128, array mode, whole-sequence groups).  The Viterbi path is one point without spread, the marginals have spread
+ * without dependence between neighbouring sites; these are whole tracks with the right joint law.  The transition is
+ * semiseparable, so the weights of the predecessors of a state cost O(K): they are the coefficients of delta_t[i] in the
+ * forward step's term for state j (HMM.cpp:799-830); the emission of t+1 is common to all i and drops out.  The
+ * contract; every operation is one separately rounded IEEE fp32 operation.  delta_t is the scaled forward vector of
+ * site t, exactly what fsmc_decode_pair_loglik's kernel holds after its scaling (the reference's alpha):
+ *     uniform of (seed, pair, sample r, site t):
+ *       Philox4x32-10, key = (seed & 0xffffffff, seed >> 32),
+ *       counter = (t >> 2, r, hap_a, hap_b)          (the pair's two fields of the work list, as stored)
+ *       u = float(out[t & 3] >> 8) * 2^-24           (exact, in [0, 1))
+ *     pick(w[0..K-1], u):
+ *       c[-1] = 0.f;  c[i] = c[i-1] + w[i]   for i ascending
+ *       x = u * c[K-1]
+ *       state = min(K-1, #{ i in [0, K) : c[i] <= x })   (exactly this comparison; K the model's states)
+ *     site S-1:  w[i] = delta_{S-1}[i];   x[S-1] = pick(w, u(S-1))
+ *     site t = S-2 .. 0, with j = x[t+1] and D, B, U the table row step_row[t+1], cR the column ratios:
+ *       i > j:   w[i] = B[j] * delta_t[i]
+ *       i = j:   w[j] = D[j] * delta_t[j]
+ *       i < j:   g = 1.f at i = j-1;   for i = j-2 .. 0:  g = g * cR[i+1]
+ *                w[i] = (U[i] * delta_t[i]) * g
+ *       x[t] = pick(w, u(t))
+ *   states[(i * n_samples + r) * S + t] = x[t] of sample r (uint8, in [0, K)), i in work-list order.
+ *   A chosen state always has w > 0 (c[i] > x >= c[i-1]): every sampled path is one the model allows.  Ghost states of a
+ *     padded kernel member (delta = 0, zero table entries) have w = +0 and are never counted and never chosen.
+ *   A sample depends on (seed, hap_a, hap_b, r, t) and the data only: not on list order, groups, slices, flushes, chunk
+ *     length, workspace or shard.  A pair listed twice gets the same rows; (a, b) and (b, a) are different streams.
+ *   A pair with a zero scaling sum somewhere (NaN vectors) only has states in [0, K).  The other pairs of its group are
+ *     exact.
+ * A wave keeps 4 K bytes of forward vector a pair and site in the decode's workspace; a sequence whose vectors do not fit
+ * is swept in chunks: a first sweep leaves a checkpoint a chunk, then chunk by chunk from the end a second sweep rebuilds
+ * the chunk's vectors and the sampler walks it down (fsmc_ctx_set_chunk_sites and fsmc_ctx_set_workspace_limit are
+ * honoured, fsmc_ctx_last_plan and fsmc_ctx_last_kernel report; results do not depend on them).  The work list goes
+ * through the device in slices of groups (fsmc_ctx_set_pair_samples_slice), which are independent; the state rows leave
+ * through pinned buffers.  fsmc_last_kernel_ms spans the call's launches (with several slices also the copies in
+ * between).  FSMC_EINVAL, nothing touched: n_samples outside 1 ... 64; states NULL; a group that is not the whole
+ * sequence (from = 0, to = S); a model of more than 128 states; a sequence-mode model (its half-step doubles the
+ * trellis). */
+int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_samples, uint64_t seed, uint8_t* states);
 
 /* Per pair of the resident work list and site, where the posterior mass lies, without the [K][S] tables leaving the
  * device.  post[k] is the pair's normalised fp32 posterior at the site over the model's K states (not multiplied by any
