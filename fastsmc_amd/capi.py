@@ -43,6 +43,7 @@ SYMBOLS = [
     "fsmc_decode_pair_loglik", "fsmc_ctx_set_pair_loglik_slice", "fsmc_ctx_last_pair_loglik_slices",
     "fsmc_decode_pair_viterbi", "fsmc_ctx_set_pair_viterbi_slice", "fsmc_ctx_last_pair_viterbi_slices",
     "fsmc_decode_pair_samples", "fsmc_ctx_set_pair_samples_slice", "fsmc_ctx_last_pair_samples_slices",
+    "fsmc_decode_pair_transitions", "fsmc_ctx_set_pair_transitions_slice", "fsmc_ctx_last_pair_transitions_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
 
@@ -161,6 +162,9 @@ def load():
         L.fsmc_decode_pair_samples.argtypes = [vp, vp, i32, C.c_uint64, vp]
         L.fsmc_ctx_set_pair_samples_slice.argtypes = [vp, u32]
         L.fsmc_ctx_last_pair_samples_slices.argtypes = [vp, C.POINTER(i32)]
+        L.fsmc_decode_pair_transitions.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
+        L.fsmc_ctx_set_pair_transitions_slice.argtypes = [vp, u32]
+        L.fsmc_ctx_last_pair_transitions_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -605,6 +609,50 @@ class Context:
     def last_pair_samples_slices(self) -> int:
         v = C.c_int32(0)
         self._check(self._L.fsmc_ctx_last_pair_samples_slices(self._h, C.byref(v)))
+        return v.value
+
+    def decode_pair_transitions(self, model: "Model", bin_edges=None, want_rows=True, out=None):
+        """Per pair of the resident work list and site t, the posterior probability that the state at t is lower / higher
+        than at t - 1 (fsmc_decode_pair_transitions): (down f32 [n_pairs][S], up f32 [n_pairs][S], bin_down f32
+        [n_pairs][B], bin_up f32 [n_pairs][B]); 1 - down - up is the probability of no change, site 0 holds 0.  The bin
+        outputs -- the expected number of downward / upward changes over the sites [bin_edges[b], bin_edges[b + 1]) --
+        come with ``bin_edges``, the rows with ``want_rows``; None for what was not asked for.  ``out``: four such arrays
+        (None where not wanted, at least n_pairs rows), written in place and returned as they are -- ``want_rows`` is
+        ignored then."""
+        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
+        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
+        if edges is not None and edges.size == 0:
+            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        n, S = self._n_pairs, model.S
+        if out is None:
+            out = (np.zeros((n, S), np.float32) if want_rows else None, np.zeros((n, S), np.float32) if want_rows else None,
+                   np.zeros((n, n_bins), np.float32) if edges is not None else None,
+                   np.zeros((n, n_bins), np.float32) if edges is not None else None)
+        out = tuple(out)
+        if len(out) != 4:
+            raise ValueError("out: (down, up, bin_down, bin_up)")
+        if all(a is None for a in out):
+            raise ValueError("need at least one output: rows (want_rows) or bins (bin_edges)")
+        for i, a in enumerate(out):
+            if a is None:
+                continue
+            if i >= 2 and edges is None:
+                raise ValueError("out: the bin outputs need bin_edges")
+            if (not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or not a.flags.writeable
+                    or a.ndim != 2 or a.shape[1] != (S if i < 2 else n_bins) or a.shape[0] < n):
+                raise ValueError("out: writable C-contiguous float32 arrays, [>= n_pairs][S] rows and [>= n_pairs][B] bins")
+        self._check(self._L.fsmc_decode_pair_transitions(self._h, model._h, _p(out[0]), _p(out[1]), _p(edges), n_bins,
+                                                         _p(out[2]), _p(out[3])))
+        return out
+
+    def set_pair_transitions_slice(self, groups: int):
+        """Groups fsmc_decode_pair_transitions puts through the device at a time; 0 = automatic.  Results do not depend
+        on it."""
+        self._check(self._L.fsmc_ctx_set_pair_transitions_slice(self._h, groups))
+
+    def last_pair_transitions_slices(self) -> int:
+        v = C.c_int32(0)
+        self._check(self._L.fsmc_ctx_last_pair_transitions_slices(self._h, C.byref(v)))
         return v.value
 
     def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):

@@ -82,6 +82,7 @@ enum PairSlicing {
   kSliceLoglik,
   kSliceViterbi,
   kSliceSamples,
+  kSliceTransitions,
   kPairSlicings
 };
 } // namespace
@@ -168,6 +169,7 @@ struct fsmc_ctx {
   DevBuf pcSpec;            // cdf, tail summaries: the call's outputs, PairCdfSpec each
   DevBuf plAcc;             // log-likelihoods: a slice's [mant][bin mant][expo][bin expo], then the edges, B + 1
   DevBuf pvAcc;             // Viterbi paths: a slice's [mant][expo]; its state rows, [pair][S] bytes, are in ppRows
+  DevBuf pxAcc;             // change probabilities: [edges, B + 1][weights, S ones][a slice's bin outputs, 2 x pairs x B]
   DevBuf ptAcc;             // tail summaries: [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
@@ -1440,6 +1442,7 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx)
   if (ctx->pmAcc.p) (void)hipFree(ctx->pmAcc.p);
   if (ctx->pbAcc.p) (void)hipFree(ctx->pbAcc.p);
   if (ctx->plAcc.p) (void)hipFree(ctx->plAcc.p);
+  if (ctx->pxAcc.p) (void)hipFree(ctx->pxAcc.p);
   if (ctx->pvAcc.p) (void)hipFree(ctx->pvAcc.p);
   for (int i = 0; i < 2; ++i) {
     if (ctx->ppPinned[i]) (void)hipHostFree(ctx->ppPinned[i]);
@@ -1595,6 +1598,8 @@ int fsmc_ctx_set_pair_viterbi_slice(fsmc_ctx* ctx, uint32_t groups) { return set
 int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceViterbi, slices); }
 int fsmc_ctx_set_pair_samples_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceSamples, groups); }
 int fsmc_ctx_last_pair_samples_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceSamples, slices); }
+int fsmc_ctx_set_pair_transitions_slice(fsmc_ctx* ctx, uint32_t groups) { return setPairSlice(ctx, kSliceTransitions, groups); }
+int fsmc_ctx_last_pair_transitions_slices(const fsmc_ctx* ctx, int32_t* slices) { return lastPairSlices(ctx, kSliceTransitions, slices); }
 
 int fsmc_ctx_last_kernel(const fsmc_ctx* ctx, int32_t* member)
 {
@@ -2763,6 +2768,143 @@ int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_sampl
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   ctx->pairSlices[kSliceSamples].last = (int)ws.nSlices;
+  return FSMC_OK;
+}
+
+// Per pair and site, the posterior probability that the state is lower / higher than at the site before
+// (fsmc_pair_transitions.h): one launch of transition_kernel a slice, planned by planSamples into the decode's workspace
+// (the workspace is the sampling kernel's).  A slice's rows, [down | up][pair][S] floats in ppRows, are two spans of the
+// caller's arrays and leave through drainRows; its bin sums are pair_tail_bins_kernel's bin_tail_length over weights of
+// 1.f -- (double)p * 1.0 is p -- and leave by a blocking copy.  Slices are independent; a slice's rows have left before
+// the next launch.
+int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down_rows, float* up_rows,
+                                 const int32_t* bin_edges, int32_t n_bins, float* bin_down, float* bin_up)
+{
+  FSMC_TRY(checkReady(ctx, m));
+  if (!down_rows && !up_rows && !bin_down && !bin_up) {
+    return fail(ctx, FSMC_EINVAL, "change probabilities: need at least one output (down_rows, up_rows, bin_down, bin_up)");
+  }
+  const bool wantBins = bin_down || bin_up;
+  if (wantBins) {
+    if (!bin_edges) {
+      return fail(ctx, FSMC_EINVAL, "change probabilities: the bin outputs need bin edges");
+    }
+    if (n_bins < 0) {
+      return fail(ctx, FSMC_EINVAL, "change probabilities: n_bins is negative");
+    }
+    FSMC_TRY(checkBinEdges(ctx, m, bin_edges, (size_t)n_bins));
+  }
+  FSMC_TRY(checkWholeSequence(ctx, m, "change probabilities"));
+  if (m->K > 128) {
+    return fail(ctx, FSMC_EINVAL, "change probabilities: no transition kernel for a model of more than 128 states (" +
+                                      std::to_string(m->K) + ")");
+  }
+  if (m->sequence) {
+    return fail(ctx, FSMC_EINVAL, "change probabilities: no transition kernel for a sequence-mode model");
+  }
+  const SweepKernel<TrnParams> kern =
+      chooseSweepKernel<TrnParams>(m, [](auto kt) { return transition_kernel<decltype(kt)::value>; });
+  if (!kern.fn) {
+    return fail(ctx, FSMC_EUNSUPPORTED, "change probabilities: no kernel for this model");
+  }
+  const size_t S = (size_t)m->S, B = wantBins ? (size_t)n_bins : 0;
+  WorkSlices ws;
+  FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceTransitions, ctx->ppRows.bytes + ctx->pxAcc.bytes,
+                      layout::transitionsGroupBytes(S, B), ws));
+  if (ws.slicePairsMax > (size_t)INT32_MAX) {
+    return fail(ctx, FSMC_EINVAL, "too many pairs in one slice (fsmc_ctx_set_pair_transitions_slice)");
+  }
+  const layout::Transitions L = layout::transitions(S, B, ws.slicePairsMax);
+  FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
+  if (wantBins) {
+    FSMC_TRY(ensure(ctx, ctx->pxAcc, L.accBytes));
+  }
+  const bool wantRows = down_rows || up_rows;
+  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), ws.slicePairsMax * S * sizeof(float)));
+  if (wantRows) {
+    FSMC_TRY(ensureRowCopies(ctx, copyBytes));
+  }
+  earnWorkspace(ctx, m, kModePerPair);
+  LaunchPlan plan;
+  std::string why;
+  const int rc = planSamples(ctx, m, kern.k, ws.slice, workspaceBudget(ctx, ctx->ws), plan, why);
+  if (rc != FSMC_OK) {
+    return fail(ctx, rc, why);
+  }
+  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+
+  float* const dRows[2] = {(float*)ctx->ppRows.p, (float*)ctx->ppRows.p + L.rowsPerOut * S};
+  char* const acc = (char*)ctx->pxAcc.p;
+  std::vector<float> ones;
+  if (wantBins) {
+    ones.assign(S, 1.f);
+    FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 ctx->stream));
+    FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offWeights, ones.data(), S * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  TrnParams p;
+  std::memset(&p, 0, sizeof(p));
+  fillSweepParams(ctx, m, p);
+  p.K = m->K;
+  p.ghostMask = m->ghostMask;
+  p.chunk = plan.chunk;
+  p.nChunks = plan.maxChunks;
+  p.ws = (char*)ctx->ws.p;
+  p.slotBytes = plan.wsSlot * sizeof(float4);
+  p.down = dRows[0];
+  p.up = dRows[1];
+  recordLaunch(ctx, kern.k, plan);
+
+  PairTailParams r;
+  std::memset(&r, 0, sizeof(r));
+  float* const dBins = wantBins ? (float*)(acc + L.offBins) : nullptr;
+  r.rows = dRows[0];
+  r.rowsPerOut = L.rowsPerOut;
+  r.S = m->S;
+  r.nTail = 2;
+  r.edges = wantBins ? (const int*)(acc + L.offEdges) : nullptr;
+  r.weights = wantBins ? (const float*)(acc + L.offWeights) : nullptr;
+  r.B = (int)B;
+  r.binLength = dBins;
+  const size_t wavesPerBlock = kPairBinsThreads / kWave;
+  const size_t blocksMax = std::max<size_t>(1, (size_t)4 * (size_t)std::max(ctx->nCU, 1));
+  float* const hRows[2] = {down_rows, up_rows};
+  float* const hBins[2] = {bin_down, bin_up};
+
+  for (size_t sl = 0; sl < ws.nSlices; ++sl) {
+    const size_t first = ws.firstPair(sl), nP = ws.pairs(sl);
+    FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
+    if (wantBins && nP > 0) {
+      r.n = (int)nP;
+      const size_t blocks = std::min(blocksMax, (nP * B + wavesPerBlock - 1) / wavesPerBlock);
+      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3((unsigned)blocks, 2u), dim3(kPairBinsThreads), 0, ctx->stream, r);
+      FSMC_HIP(ctx, hipGetLastError());
+      FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every sweep and every reduction)
+    }
+    if (wantRows && nP > 0) {
+      FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
+      const size_t bytes = nP * S * sizeof(float);
+      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
+      for (int o = 0; o < 2; ++o) {
+        if (!hRows[o]) {
+          continue;
+        }
+        char* const dst = (char*)(hRows[o] + first * S);
+        const char* const src = (const char*)dRows[o];
+        FSMC_TRY(drainRows(
+            ctx, (bytes + copyBytes - 1) / copyBytes, [&](size_t c) { return RowChunk{src + c * copyBytes, span(c)}; },
+            [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
+      }
+    }
+    // the slice's rows and cells have left before the next slice overwrites them
+    FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int o = 0; o < 2; ++o) {
+      FSMC_TRY(sliceToCaller(ctx, ws, sl, hBins[o], dBins ? dBins + (size_t)o * L.rowsPerOut * B : nullptr,
+                             B * sizeof(float)));
+    }
+  }
+  ctx->pairSlices[kSliceTransitions].last = (int)ws.nSlices;
   return FSMC_OK;
 }
 

@@ -30,6 +30,8 @@ FSMC_KT_POOL_KERNELS(FSMC_DEFINE_KT_POOL, FSMC_INSTANCE_KT)
 #endif
 // (behind everything: the sampling kernels; every kernel above keeps its compiled text)
 FSMC_KT_SAMPLE_KERNELS(FSMC_DEFINE_KT_SAMPLE, FSMC_INSTANCE_KT)
+// (and behind those the transition kernels, likewise)
+FSMC_KT_TRANSITION_KERNELS(FSMC_DEFINE_KT_TRANSITION, FSMC_INSTANCE_KT)
 #elif defined(FSMC_INSTANCE_W2)
 #ifndef FSMC_INSTANCE_NW
 #define FSMC_INSTANCE_NW 4

@@ -26,6 +26,9 @@
 //   member, array mode; the wave-group and any-K families have none.
 // Sampling kernel (sample_kernel<KT>, fsmc_pair_samples.h): state paths drawn from the joint posterior, every
 //   lane-per-pair member, array mode; the wave-group and any-K families have none.
+// Transition kernel (transition_kernel<KT>, fsmc_pair_transitions.h): per site, the posterior probability of a change of
+//   state from the site before, downwards and upwards; every lane-per-pair member, array mode; the wave-group and any-K
+//   families have none.
 // What the families share is defined once: fsmc_lane_scaffold.h (a lane's pair and haplotype rows, the next group of a
 //   sums batch, the row-index block),
 //   fsmc_site_consumers.h (the per-pair mean / MAP consumer, the IBD record writer), both included by fsmc_kernels.h;
@@ -41,6 +44,7 @@
 #include "fsmc_pair_loglik.h"
 #include "fsmc_pair_viterbi.h"
 #include "fsmc_pair_samples.h"
+#include "fsmc_pair_transitions.h"
 
 namespace fsmc
 {
@@ -135,6 +139,10 @@ constexpr bool poolBuilt(const int KT)
 #define FSMC_KT_SAMPLE_KERNELS(X, KT) X(KT)
 #define FSMC_DECLARE_KT_SAMPLE(KT) extern template __global__ void sample_kernel<KT>(const SmpParams);
 #define FSMC_DEFINE_KT_SAMPLE(KT) template __global__ void sample_kernel<KT>(const SmpParams);
+// the two-slice change probabilities (fsmc_pair_transitions.h): array mode
+#define FSMC_KT_TRANSITION_KERNELS(X, KT) X(KT)
+#define FSMC_DECLARE_KT_TRANSITION(KT) extern template __global__ void transition_kernel<KT>(const TrnParams);
+#define FSMC_DEFINE_KT_TRANSITION(KT) template __global__ void transition_kernel<KT>(const TrnParams);
 // NW waves per group of KH states each, lane = pair (fsmc_kernels_w2.h): 128 < K <= 512
 #define FSMC_W2_MODE_KERNELS(X, KH, NW, SEQ)                                                                           \
   X(KH, kModeIbd, true, SEQ, NW)                                                                                       \
@@ -157,7 +165,8 @@ constexpr bool poolBuilt(const int KT)
 #define FSMC_DECLARE_MEMBER(KT)                                                                                         \
   FSMC_KT_KERNELS(FSMC_DECLARE_KT, KT)                                                                                  \
   FSMC_KT_BIDIR_KERNELS(FSMC_DECLARE_KT_BIDIR, KT) FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)                        \
-  FSMC_KT_VITERBI_KERNELS(FSMC_DECLARE_KT_VITERBI, KT) FSMC_KT_SAMPLE_KERNELS(FSMC_DECLARE_KT_SAMPLE, KT)
+  FSMC_KT_VITERBI_KERNELS(FSMC_DECLARE_KT_VITERBI, KT) FSMC_KT_SAMPLE_KERNELS(FSMC_DECLARE_KT_SAMPLE, KT)               \
+  FSMC_KT_TRANSITION_KERNELS(FSMC_DECLARE_KT_TRANSITION, KT)
 FSMC_ALL_KT(FSMC_DECLARE_MEMBER)
 #define FSMC_DECLARE_EXACT_MEMBER(KT)                                                                                   \
   static_assert(KT % 16 != 0 && KT <= 128, "an exact member is not a multiple of 16 states and has at most 128");       \
@@ -166,6 +175,7 @@ FSMC_ALL_KT(FSMC_DECLARE_MEMBER)
   FSMC_KT_FWD_KERNELS(FSMC_DECLARE_KT_FWD, KT)                                                                          \
   FSMC_KT_VITERBI_KERNELS(FSMC_DECLARE_KT_VITERBI, KT)                                                                  \
   FSMC_KT_SAMPLE_KERNELS(FSMC_DECLARE_KT_SAMPLE, KT)                                                                    \
+  FSMC_KT_TRANSITION_KERNELS(FSMC_DECLARE_KT_TRANSITION, KT)                                                            \
   FSMC_KT_HALF_KERNELS(FSMC_DECLARE_KT, KT)                                                                             \
   FSMC_KT_HALF_SUMS_KERNELS(FSMC_DECLARE_KT, KT)                                                                        \
   FSMC_DECLARE_KT_DUAL_HALF(KT)                                                                                         \

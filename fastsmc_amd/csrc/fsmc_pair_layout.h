@@ -188,7 +188,31 @@ inline Samples samples(size_t S, size_t nSamples, size_t slicePairsMax)
   return L;
 }
 
-// ---- tails and quantiles: no accumulator; ppRows = [output][pair of slice][S] ----------------------------------------
+// ---- change probabilities: ppRows = [down | up][pair of slice, a multiple of four][S] floats (both halves start on 16
+// bytes); pxAcc = [edges, B + 1][weights, S ones][a slice's bin outputs, 2 x pairs x B] where bins are wanted ------------
+struct Transitions {
+  size_t groupBytes = 0;
+  size_t rowsPerOut = 0; // rows of one direction in ppRows
+  size_t rowsBytes = 0;  // ppRows
+  size_t outBytes = 0;   // the bin cells of both directions, the largest slice
+  size_t offEdges = 0, offWeights = 0, offBins = 0, accBytes = 0;
+};
+inline size_t transitionsGroupBytes(size_t S, size_t B) { return kLanes * 2 * sizeof(float) * (S + B); }
+inline Transitions transitions(size_t S, size_t B, size_t slicePairsMax)
+{
+  Transitions L;
+  L.groupBytes = transitionsGroupBytes(S, B);
+  L.rowsPerOut = (slicePairsMax + 3) / 4 * 4;
+  L.rowsBytes = 2 * L.rowsPerOut * S * sizeof(float);
+  L.outBytes = 2 * L.rowsPerOut * B * sizeof(float);
+  L.offEdges = 0;
+  L.offWeights = B ? roundUp8((B + 1) * sizeof(int32_t)) : 0;
+  L.offBins = L.offWeights + (B ? roundUp8(S * sizeof(float)) : 0);
+  L.accBytes = L.offBins + L.outBytes;
+  return L;
+}
+
+// ---- tails and quantiles: no accumulator; ppRows =[output][pair of slice][S] ----------------------------------------
 struct Cdf {
   size_t groupBytes = 0; // a group in the staging buffer and its rows, at most
   size_t stageBytes = 0; // ppStage: a slice's dump

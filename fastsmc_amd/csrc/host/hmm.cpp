@@ -619,6 +619,14 @@ void HMM::setSampledPaths(int n, unsigned long long seed)
   setPairOutputs(next);
 }
 
+void HMM::setTransitionProbabilities(bool rows, const std::vector<int>& bins)
+{
+  PairOutputs next = mOutputs;
+  next.transitionRows = rows;
+  next.transitionBins = bins;
+  setPairOutputs(next);
+}
+
 // (the rest of the request passed its check when it was set: only the part that changes can be refused)
 void HMM::setSiteBins(const std::vector<int>& edges)
 {
@@ -1026,6 +1034,9 @@ void HMM::flushPairOutputs(size_t nPairs)
   if (o.sampledPaths > 0) {
     flushPairSamples(nPairs);
   }
+  if (o.transitions()) {
+    flushPairTransitions();
+  }
   if (o.cdf()) {
     flushPairCdf();
   }
@@ -1147,6 +1158,31 @@ void HMM::flushPairSamples(size_t)
         fsmc_decode_pair_samples(mCtx, mModel, mOutputs.sampledPaths, mOutputs.sampleSeed,
                                  R.perPairSampledStates.data() + R.numWritten * rowBytes),
         "fsmc_decode_pair_samples");
+}
+
+// per pair and site the probabilities of a change of state from the site before, and their sums over the bins, flush
+// after flush at the pairs written so far: 8 bytes a pair-site (rows) and a pair-bin cross the bus.  A pair's values do
+// not depend on the flush it is in.
+void HMM::flushPairTransitions()
+{
+  auto& R = mPairsReturn;
+  const size_t S = static_cast<size_t>(R.numSites);
+  const std::vector<int>& edges = mOutputs.transitionBins;
+  const size_t nBins = edges.empty() ? 0 : edges.size() - 1;
+  const bool rows = mOutputs.transitionRows;
+  if (R.request.transitionRows != rows || R.request.transitionBins != edges ||
+      R.perPairDownProbabilities.size() != (rows ? static_cast<size_t>(R.numPairs) * S : 0) ||
+      R.binExpectedDowns.size() != static_cast<size_t>(R.numPairs) * nBins) {
+    throw std::runtime_error("the return structure was not initialised for the change probabilities asked for");
+  }
+  const size_t at = R.numWritten * S, atBin = R.numWritten * nBins;
+  check(mCtx,
+        fsmc_decode_pair_transitions(mCtx, mModel, rows ? R.perPairDownProbabilities.data() + at : nullptr,
+                                     rows ? R.perPairUpProbabilities.data() + at : nullptr,
+                                     nBins ? edges.data() : nullptr, static_cast<int32_t>(nBins),
+                                     nBins ? R.binExpectedDowns.data() + atBin : nullptr,
+                                     nBins ? R.binExpectedUps.data() + atBin : nullptr),
+        "fsmc_decode_pair_transitions");
 }
 
 // per pair and site the tail probabilities and quantile states, flush after flush at the pairs written so far: 4 bytes a

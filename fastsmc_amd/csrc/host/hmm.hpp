@@ -131,6 +131,11 @@ public:
   // filtering with backward sampling on the device (fsmc_decode_pair_samples); a sample depends on the seed, the pair's
   // two haplotypes, its index and the data only.  Throws for n outside 0 ... 64, more than 128 states and sequence mode
   void setSampledPaths(int n, unsigned long long seed = 0);
+  // per pair and site the posterior probability that the state is lower / higher than at the site before, exact, from a
+  // forward sweep joined to a backward walk on the device (fsmc_decode_pair_transitions): the [pairs][sites] rows with
+  // `rows`, their sums over the bins of sites [bins[b], bins[b + 1]) -- the expected number of changes -- with `bins`
+  // (empty: none).  Throws for more than 128 states, sequence mode and edges the ABI would refuse
+  void setTransitionProbabilities(bool rows, const std::vector<int>& bins = {});
   // per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins of sites
   // [edges[b], edges[b + 1]), into the return structure's bin matrices (fsmc_decode_pair_bins); an empty vector turns
   // this off.  Throws for edges the ABI would refuse: fewer than two, not strictly ascending, outside [0, sites].
@@ -217,6 +222,7 @@ private:
   void flushPairLogLik(size_t nPairs);
   void flushPairViterbi(size_t nPairs);
   void flushPairSamples(size_t nPairs);
+  void flushPairTransitions();
   void flushPairCdf();
   void flushPairTailSummaries(size_t nPairs);
   void flushPairPosteriors(size_t nPairs);

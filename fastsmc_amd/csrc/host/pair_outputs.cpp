@@ -109,6 +109,26 @@ void PairOutputs::check(long sites, long states, bool sequence) const
   if (sampledPaths && sequence) {
     throw std::runtime_error("sampled paths: no sampling kernel for a sequence-mode model");
   }
+  if (transitions() && states > 128) { // (the messages of fsmc_decode_pair_transitions)
+    throw std::runtime_error("change probabilities: no transition kernel for a model of more than 128 states (" +
+                             std::to_string(states) + ")");
+  }
+  if (transitions() && sequence) {
+    throw std::runtime_error("change probabilities: no transition kernel for a sequence-mode model");
+  }
+  if (!transitionBins.empty()) {
+    if (transitionBins.size() < 2) {
+      throw std::runtime_error("need one bin at least (n_bins + 1 edges)");
+    }
+    if (transitionBins.front() < 0 || static_cast<long>(transitionBins.back()) > sites) {
+      throw std::runtime_error("bin edges must lie in [0, sites]");
+    }
+    for (size_t b = 0; b + 1 < transitionBins.size(); ++b) {
+      if (transitionBins[b] >= transitionBins[b + 1]) {
+        throw std::runtime_error("bin edges must be strictly ascending");
+      }
+    }
+  }
 }
 
 void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs)
@@ -158,6 +178,12 @@ void DecodePairsReturnStruct::initialise(size_t nPairs, long sites, long states,
   perPairViterbiLogProbabilities.assign(o.viterbiPaths ? nPairs : 0, 0.0);
   // the sampled paths: [pairs][samples][sites]
   perPairSampledStates.assign(o.sampledPaths > 0 ? nPairs * static_cast<size_t>(o.sampledPaths) * S : 0, 0);
+  // the change probabilities: [pairs][sites] and [pairs][bins of their own]
+  const size_t changeCells = o.transitionBins.size() < 2 ? 0 : nPairs * (o.transitionBins.size() - 1);
+  perPairDownProbabilities.assign(o.transitionRows ? nPairs * S : 0, 0.f);
+  perPairUpProbabilities.assign(o.transitionRows ? nPairs * S : 0, 0.f);
+  binExpectedDowns.assign(changeCells, 0.f);
+  binExpectedUps.assign(changeCells, 0.f);
 }
 
 void DecodePairsReturnStruct::finaliseCalculations()

@@ -43,24 +43,31 @@ struct PairOutputs {
   // (fsmc_decode_pair_samples): models of at most 128 states, array mode
   int sampledPaths = 0;
   unsigned long long sampleSeed = 0;
+  // per pair and site, the posterior probability that the state is lower / higher than at the site before
+  // (fsmc_decode_pair_transitions): the [pairs][sites] rows, and / or their sums over bins of sites with edges of their
+  // own (transitionBins[b], transitionBins[b + 1]); models of at most 128 states, array mode
+  bool transitionRows = false;
+  std::vector<int> transitionBins;
 
   // Throws what the ABI would refuse, with its messages: more than 8 tail states or quantiles, a cut outside [1, states],
   // a quantile outside (0, 1]; then the same for the tail summaries, and weights without cuts, not one a site or not
   // finite; then fewer than two bin edges, edges outside [0, sites] or not strictly ascending; then log-likelihoods of a
   // model of more than 128 states; then Viterbi paths of a model of more than 128 states or of a sequence-mode model;
-  // then sampled paths outside 0 ... 64, of a model of more than 128 states or of a sequence-mode model.
+  // then sampled paths outside 0 ... 64, of a model of more than 128 states or of a sequence-mode model; then change
+  // probabilities of a model of more than 128 states or of a sequence-mode model, or with bad bin edges.
   void check(long sites, long states, bool sequence = false) const;
 
   // the minima come from the device where their rows are not stored (stored rows: finaliseCalculations, as ever)
   bool minMeansOnDevice() const { return minMeans && !means; }
   bool minMapsOnDevice() const { return minMaps && !maps; }
   bool cdf() const { return !tailStates.empty() || !quantiles.empty(); }
+  bool transitions() const { return transitionRows || !transitionBins.empty(); }
   // anything at all that goes into the return structure
   bool any() const
   {
     return means || maps || posteriors || sumOfPosteriors || minMeansOnDevice() || minMapsOnDevice() ||
            !siteBins.empty() || cdf() || !tailSummaryStates.empty() || logLikelihoods || viterbiPaths ||
-           sampledPaths != 0;
+           sampledPaths != 0 || transitions();
   }
 };
 
@@ -100,6 +107,10 @@ struct DecodePairsReturnStruct {
   std::vector<int> perPairViterbiExponents;
   // state sequences drawn from the joint posterior of each pair, [pairs][samples][sites]
   std::vector<unsigned char> perPairSampledStates;
+  // the posterior probability that the state at a site is lower / higher than at the site before, [pairs][sites], and
+  // their sums over the bins of request.transitionBins, [pairs][bins]
+  std::vector<float> perPairDownProbabilities, perPairUpProbabilities;
+  std::vector<float> binExpectedDowns, binExpectedUps;
   size_t numWritten = 0;
 
   void initialise(size_t nPairs, long sites, long states, const PairOutputs& outputs);

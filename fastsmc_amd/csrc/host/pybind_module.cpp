@@ -6,6 +6,8 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <optional>
+
 #include "binary_reader.hpp"
 #include "drivers.hpp"
 #include "hashing.hpp"
@@ -92,6 +94,10 @@ using Pairs = DecodePairsReturnStruct;
 size_t numBins(const Pairs& r)
 {
   return r.request.siteBins.empty() ? 0 : r.request.siteBins.size() - 1;
+}
+size_t transitionBinCount(const Pairs& r)
+{
+  return r.request.transitionBins.empty() ? 0 : r.request.transitionBins.size() - 1;
 }
 
 // ASMC.decodePairs for one kind of pair list (haplotype indices / "<ID>#<1|2>" strings): the keywords and the text once
@@ -182,6 +188,39 @@ template <typename Id> void defSamplePairs(py::class_<ASMC>& c, const char* list
       "run-length form of a row.");
 }
 
+// ASMC.decodePairTransitions for one kind of pair list: a decodePairs with the change probabilities as its one output
+template <typename Id> void defDecodePairTransitions(py::class_<ASMC>& c, const char* listA, const char* listB)
+{
+  c.def(
+      "decodePairTransitions",
+      [](ASMC& self, const std::vector<Id>& a, const std::vector<Id>& b, bool rows,
+         const std::optional<std::vector<int>>& siteBins) {
+        PairOutputs o;
+        o.transitionRows = rows;
+        if (siteBins) {
+          if (siteBins->size() < 2) { // (PairOutputs: no edges ask for nothing)
+            throw std::runtime_error("need one bin at least (n_bins + 1 edges)");
+          }
+          o.transitionBins = *siteBins;
+        }
+        if (!o.transitions()) {
+          throw std::runtime_error("change probabilities: need at least one output (rows or site_bins)");
+        }
+        self.decodePairs(a, b, o);
+      },
+      py::arg(listA), py::arg(listB), "rows"_a = true, "site_bins"_a = py::none(),
+      "Decode the listed pairs into the posterior probability, given all of a pair's data, that the state at site t is "
+      "lower / higher than the state at site t - 1 (exact: a forward sweep joined to a backward walk on the device, "
+      "about the cost of one decode; models of at most 128 states, array mode): per_pair_down_probabilities and "
+      "per_pair_up_probabilities ([pairs][sites] float32, 0 at site 0; 1 - down - up is the probability of no change) "
+      "with rows, and with site_bins (edges e[0] < ... < e[B] within [0, sites], reported in bin_edges) "
+      "bin_expected_downs and bin_expected_ups ([pairs][B] float32: the sum over the bin's sites in a defined fp64 "
+      "order, the expected number of changes in the bin; with rows=False the rows never leave the device).  Every other "
+      "field of the return structure is empty.  The marginals carry no dependence between neighbouring sites and a "
+      "Viterbi path no uncertainty; sampled paths give this at 1 / sqrt(samples).  A pair's values depend on the pair "
+      "and the data only, whatever the flushes.");
+}
+
 } // namespace
 
 PYBIND11_MODULE(_pyasmc, m)
@@ -225,7 +264,11 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("min_MAPs", [](const Pairs& r) { return shaped(r.minMAPs, r.minMAPs.size()); })
       .def_property_readonly("argmin_MAPs", [](const Pairs& r) { return shaped(r.argminMAPs, r.argminMAPs.size()); })
       // per pair, summaries over the bins of sites [bin_edges[b], bin_edges[b + 1]): [pairs][bins], empty without bins
-      .def_property_readonly("bin_edges", [](const Pairs& r) { return shaped(r.request.siteBins, r.request.siteBins.size()); })
+      // (the edges of decodePairs' site_bins, or of decodePairTransitions', which asks for nothing else)
+      .def_property_readonly("bin_edges", [](const Pairs& r) {
+        const std::vector<int>& e = r.request.siteBins.empty() ? r.request.transitionBins : r.request.siteBins;
+        return shaped(e, e.size());
+      })
       .def_property_readonly("bin_mean_posterior_means", [](const Pairs& r) { return shaped(r.binMeanPosteriorMeans, r.numPairs, numBins(r)); })
       .def_property_readonly("bin_min_posterior_means", [](const Pairs& r) { return shaped(r.binMinPosteriorMeans, r.numPairs, numBins(r)); })
       .def_property_readonly("bin_argmin_posterior_means", [](const Pairs& r) { return shaped(r.binArgminPosteriorMeans, r.numPairs, numBins(r)); })
@@ -263,7 +306,14 @@ PYBIND11_MODULE(_pyasmc, m)
       .def_property_readonly("per_pair_viterbi_exponents", [](const Pairs& r) { return shaped(r.perPairViterbiExponents, r.perPairViterbiExponents.size()); })
       // state sequences drawn from the joint posterior of each pair (ASMC.samplePairs), [pairs][samples][sites]; empty
       // where not asked for
-      .def_property_readonly("per_pair_sampled_states", [](const Pairs& r) { return shaped(r.perPairSampledStates, r.numPairs, r.request.sampledPaths, r.numSites); });
+      .def_property_readonly("per_pair_sampled_states", [](const Pairs& r) { return shaped(r.perPairSampledStates, r.numPairs, r.request.sampledPaths, r.numSites); })
+      // the posterior probability that the state at a site is lower / higher than at the site before
+      // (ASMC.decodePairTransitions), [pairs][sites], and their sums over the bins of bin_edges, [pairs][bins]; empty
+      // where not asked for
+      .def_property_readonly("per_pair_down_probabilities", [](const Pairs& r) { return shaped(r.perPairDownProbabilities, r.numPairs, r.numSites); })
+      .def_property_readonly("per_pair_up_probabilities", [](const Pairs& r) { return shaped(r.perPairUpProbabilities, r.numPairs, r.numSites); })
+      .def_property_readonly("bin_expected_downs", [](const Pairs& r) { return shaped(r.binExpectedDowns, r.numPairs, transitionBinCount(r)); })
+      .def_property_readonly("bin_expected_ups", [](const Pairs& r) { return shaped(r.binExpectedUps, r.numPairs, transitionBinCount(r)); });
 
   py::class_<PairObservations>(m, "PairObservations")
       .def_readwrite("obsBits", &PairObservations::obsBits)
@@ -530,6 +580,10 @@ PYBIND11_MODULE(_pyasmc, m)
       .def("setSampledPaths", &HMM::setSampledPaths, "samples"_a, "seed"_a = 0ull,
            "per pair this many state sequences (1 ... 64; 0 turns it off) drawn from the joint posterior over state "
            "sequences on the device, forward filtering with backward sampling; models of at most 128 states, array mode")
+      .def("setTransitionProbabilities", &HMM::setTransitionProbabilities, "rows"_a, "bins"_a = std::vector<int>{},
+           "per pair and site the posterior probability that the state is lower / higher than at the site before, "
+           "computed on the device: the [pairs][sites] rows with rows, their sums over the bins of sites [bins[b], "
+           "bins[b+1]) with bins (an empty list: none); models of at most 128 states, array mode")
       .def("setSiteBins", &HMM::setSiteBins, "edges"_a,
            "per pair the mean / min / argmin of the posterior-mean row and the min / argmin of the MAP row over the bins "
            "of sites [edges[b], edges[b+1]), computed on the device; an empty list turns this off")
@@ -682,6 +736,8 @@ PYBIND11_MODULE(_pyasmc, m)
   defDecodePairs<std::string>(asmc, "hap_ids_a", "hap_ids_b");
   defSamplePairs<unsigned long>(asmc, "hap_indices_a", "hap_indices_b");
   defSamplePairs<std::string>(asmc, "hap_ids_a", "hap_ids_b");
+  defDecodePairTransitions<unsigned long>(asmc, "hap_indices_a", "hap_indices_b");
+  defDecodePairTransitions<std::string>(asmc, "hap_ids_a", "hap_ids_b");
   asmc.def("get_copy_of_results", &ASMC::getCopyOfResults, py::return_value_policy::copy)
       .def("get_ref_of_results", &ASMC::getRefOfResults, py::return_value_policy::reference_internal)
       .def("hmm", &ASMC::hmm, py::return_value_policy::reference_internal);

@@ -36,6 +36,8 @@
  *                             (HMM.cpp:787-830) with max in place of +, back-pointers and a traceback
  *   fsmc_decode_pair_samples <- none: the reference draws nothing.  The forward half of decodeBatch (HMM.cpp:725-784),
  *                             then backward sampling with the coefficients of the forward step's term (HMM.cpp:799-830)
+ *   fsmc_decode_pair_transitions <- none: the reference keeps no two-slice quantity.  decodeBatch's forward vectors and
+ *                             the three terms of its backward step (getPreviousBetaBatched, HMM.cpp:986-1014) joined
  *
  * Conventions: plain C types; host buffers are caller-owned, device buffers library-owned;
  * every function returns 0 on success or a negative FSMC_E* code and never exits or throws;
@@ -254,6 +256,11 @@ int fsmc_ctx_last_pair_viterbi_slices(const fsmc_ctx* ctx, int32_t* slices);
  * on it. */
 int fsmc_ctx_set_pair_samples_slice(fsmc_ctx* ctx, uint32_t groups);
 int fsmc_ctx_last_pair_samples_slices(const fsmc_ctx* ctx, int32_t* slices);
+/* The same for fsmc_decode_pair_transitions.  0 (default) = automatic: as many groups as a quarter of the card (or the
+ * workspace limit) and half its free memory hold of outputs (64 * 8 bytes * (S + n_bins) a group).  Results do not
+ * depend on it. */
+int fsmc_ctx_set_pair_transitions_slice(fsmc_ctx* ctx, uint32_t groups);
+int fsmc_ctx_last_pair_transitions_slices(const fsmc_ctx* ctx, int32_t* slices);
 /* Which kernel the last launch ran: 16 ... 128 = the lane-per-pair kernel compiled for that many states (the exact
  * members 69, 50, 100, or the padded members 16, 32, 48, 64, 80, 96, 112, 128); the wave-group kernel (128 < K <= 1024):
  * 1048 / 1064 / 1080 = four waves per group of 48 / 64 / 80 states (K <= 192 / 256 / 320), 6064 / 7064 / 8064 = six /
@@ -521,6 +528,51 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
  * sequence (from = 0, to = S); a model of more than 128 states; a sequence-mode model (its half-step doubles the
  * trellis). */
 int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_samples, uint64_t seed, uint8_t* states);
+
+/* Per pair of the resident work list and site t, the posterior probability, given all of the pair's observations, that
+ * the state at site t is lower (p_down) or higher (p_up) than the state at site t-1: the two-slice posterior summed
+ * below and above the diagonal (fsmc_pair_transitions.h; lane-per-pair kernels: K <= 128, array mode, whole-sequence
+ * groups).  The marginals carry no dependence between neighbouring sites, the Viterbi path no uncertainty, and counting
+ * over sampled paths costs n samples for 1 / sqrt(n); this is exact and costs about one decode.  The transition is
+ * semiseparable: the backward step already forms, per state k of site t-1, the mass moving to lower states (BL[k]),
+ * staying (D[k] * vec[k]) and moving to higher states (BU[k]) (getPreviousBetaBatched, HMM.cpp:986-1014).  The contract;
+ * every operation is one separately rounded IEEE fp32 operation.  delta_t is the scaled forward vector of site t,
+ * exactly what fsmc_decode_pair_loglik's kernel holds after its scaling (the reference's alpha).  b_t is the scaled
+ * backward vector of the reference (backwardBatch, HMM.cpp:882-940): b_{S-1}[k] = 1.f * (1.0f / sum) with sum over the
+ * model's K states; going down, one backward step in the order (BL + D * vec) + BU, then the scaling:
+ *     site t = S-1 .. 1, with D, B, U, RR the table row step_row[t] and e the emission of the pair's class at site t:
+ *       vec[k] = b_t[k] * e[k]
+ *       BU[K-1] = 0.f;  BU[k] = U[k] * vec[k+1] + RR[k] * BU[k+1]       (k descending)
+ *       BL[0]   = 0.f;  BL[k] = BL[k-1] + B[k-1] * vec[k-1]            (k ascending)
+ *       down = up = stay = 0.f;  for k ascending over the model's K states:
+ *         down = down + delta_{t-1}[k] * BL[k]
+ *         stay = stay + delta_{t-1}[k] * (D[k] * vec[k])
+ *         up   = up   + delta_{t-1}[k] * BU[k]
+ *       z = (down + stay) + up;   r = 1.0f / z
+ *       p_down[t] = down * r;     p_up[t] = up * r
+ *     p_down[0] = p_up[0] = 0.f.
+ *   down_rows[i * S + t] = p_down[t], up_rows[i * S + t] = p_up[t] of pair i in work-list order; 1 - p_down - p_up is
+ *     the probability of no change.
+ *   bin_down[i * n_bins + b] = the sum of (double)p_down[t] over the sites t of [bin_edges[b], bin_edges[b+1]), rounded
+ *     once to float, in the fp64 order of bin_tail_length (fsmc_decode_pair_tail_summaries): 64 slots starting at +0.0,
+ *     slot s adds the sites e[b] + s, + 64, ... ascending, then the tree a[s] = a[s] + a[s + stride] for stride = 32 ...
+ *     1.  No weights, no divide: the expected number of downward changes in the bin.  bin_up likewise.
+ *   Ghost states of a padded kernel member (delta = 0, zero table entries) contribute +0.f products and change nothing;
+ *     the first scaling of b uses the model's K.
+ *   A pair with a zero scaling sum somewhere gives whatever IEEE gives (NaN).  The other pairs of its group are exact.
+ *   The results depend on the pair and the data only: not on list order, groups, slices, flushes, chunk length or
+ *     workspace.
+ * Any of the four outputs may be NULL, one at least must be given; with bin outputs only, the rows never leave the
+ * device.  The workspace is fsmc_decode_pair_samples': forward vectors in chunks with checkpoints
+ * (fsmc_ctx_set_chunk_sites and fsmc_ctx_set_workspace_limit are honoured, fsmc_ctx_last_plan and fsmc_ctx_last_kernel
+ * report; results do not depend on them).  The work list goes through the device in slices of groups
+ * (fsmc_ctx_set_pair_transitions_slice), which are independent; the rows leave through pinned buffers.
+ * fsmc_last_kernel_ms spans the call's launches (with several slices also the copies in between).  FSMC_EINVAL, nothing
+ * touched: all four outputs NULL; bin outputs without edges, or edges that are not strictly ascending inside [0, S]; a
+ * group that is not the whole sequence (from = 0, to = S); a model of more than 128 states; a sequence-mode model.
+ * FSMC_ENOMEM, nothing launched: the workspace limit does not hold one wave's rows. */
+int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down_rows, float* up_rows,
+                                 const int32_t* bin_edges, int32_t n_bins, float* bin_down, float* bin_up);
 
 /* Per pair of the resident work list and site, where the posterior mass lies, without the [K][S] tables leaving the
  * device.  post[k] is the pair's normalised fp32 posterior at the site over the model's K states (not multiplied by any

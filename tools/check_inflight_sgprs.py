@@ -125,8 +125,9 @@ def transfer(b: Block, inflight: dict, report, name):
 def check(path: str) -> int:
     txt = open(path).read()
     # (decode_kernel, decode_kernel_bidir, decode_kernel_w2, decode_kernel_any; forward_kernel of fsmc_pair_loglik.h;
-    #  viterbi_kernel of fsmc_pair_viterbi.h; sample_kernel of fsmc_pair_samples.h)
-    parts = re.split(r"\n(_ZN4fsmc\d+(?:decode|forward|viterbi|sample)_kernel\w+):[^\n]*\n", txt)
+    #  viterbi_kernel of fsmc_pair_viterbi.h; sample_kernel of fsmc_pair_samples.h; transition_kernel of
+    #  fsmc_pair_transitions.h)
+    parts = re.split(r"\n(_ZN4fsmc\d+(?:decode|forward|viterbi|sample|transition)_kernel\w+):[^\n]*\n", txt)
     bad = 0
     for i in range(1, len(parts), 2):
         name, body = parts[i], parts[i + 1].split(".Lfunc_end")[0]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of the HIP library as the compiler reports it (-Rpass-analysis=kernel-resource-usage): VGPRs,
 AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, LDS bytes per workgroup, waves per SIMD -- one row per
-instantiation of every family member (the forward-only kernels of fsmc_pair_loglik.h the Viterbi kernels of fsmc_pair_viterbi.h and the sampling kernels of fsmc_pair_samples.h among them) and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
+instantiation of every family member (the forward-only kernels of fsmc_pair_loglik.h the Viterbi kernels of fsmc_pair_viterbi.h, the sampling kernels of fsmc_pair_samples.h and the transition kernels of fsmc_pair_transitions.h among them) and the kernels of fsmc_capi.hip (the sums' plane adder, the per-pair posterior
 transposition, the per-pair minima and their combine step, the per-pair site bins, the per-pair tails and quantile states, the tail summaries), stamped with the hash of the sources they were compiled from.
 Usage: tools/resource_table.py [out.json]   (default profiles/r14_kernel_resources.json; no GPU needed)"""
 import json
@@ -61,7 +61,7 @@ def main():
     doc = {"lib_hash": hip_source_hash(), "flags": " ".join(HIPCC_FLAGS),
            "template_arguments": {"decode_kernel": "<KT, MODE (0 IBD, 1 dump, 2 per pair, 3 sums), TRACK, SEQ, HALF, DUAL>",
                                   "decode_kernel_pool": "<KT, MODE, TRACK, HALF> (array mode, one group per wave, with the chunk pool)",
-                                  "decode_kernel_w2": "<KH, MODE, TRACK, SEQ, NW>", "forward_kernel": "<KT, SEQ>", "viterbi_kernel": "<KT>", "sample_kernel": "<KT>"},
+                                  "decode_kernel_w2": "<KH, MODE, TRACK, SEQ, NW>", "forward_kernel": "<KT, SEQ>", "viterbi_kernel": "<KT>", "sample_kernel": "<KT>", "transition_kernel": "<KT>"},
            "kernels": rows}
     json.dump(doc, open(out, "w"), indent=1)
     print(f"{len(rows)} kernels -> {out}")
