@@ -27,7 +27,7 @@ FSMC_EOVERFLOW = -6
 # every symbol include/fastsmc_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "fsmc_ctx_create", "fsmc_ctx_destroy", "fsmc_last_error", "fsmc_ctx_info", "fsmc_ctx_set_workspace_limit",
-    "fsmc_ctx_expect_work",
+    "fsmc_ctx_expect_work", "fsmc_ctx_scratch_filled",
     "fsmc_ctx_set_chunk_sites", "fsmc_ctx_set_beta_stride", "fsmc_ctx_last_beta_stride", "fsmc_ctx_last_plan",
     "fsmc_ctx_last_kernel", "fsmc_ctx_set_pairing", "fsmc_ctx_last_items", "fsmc_ctx_set_two_wave_windows", "fsmc_ctx_last_waves_per_window", "fsmc_ctx_last_segment_sums_in_lds", "fsmc_ctx_set_resident_chunks",
     "fsmc_ctx_last_resident_chunks", "fsmc_ctx_set_chunk_pool", "fsmc_ctx_last_chunk_pool",
@@ -111,6 +111,8 @@ def load():
         L.fsmc_last_error.argtypes = [vp]
         L.fsmc_last_error.restype = C.c_char_p
         L.fsmc_ctx_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
+        L.fsmc_ctx_scratch_filled.argtypes = [vp]
+        L.fsmc_ctx_scratch_filled.restype = u64
         L.fsmc_ctx_set_workspace_limit.argtypes = [vp, u64]
         L.fsmc_ctx_expect_work.argtypes = [vp, C.c_double, C.c_int32]
         L.fsmc_ctx_set_chunk_sites.argtypes = [vp, u32]
@@ -231,6 +233,11 @@ class Context:
         self._check(self._L.fsmc_ctx_last_plan(self._h, C.byref(chunk), C.byref(chunks), None))
         return {"n_cu": cu.value, "n_slots": slots.value, "hbm_bytes": hbm.value, "chunk_sites": chunk.value,
                 "max_chunks": chunks.value}
+
+    def scratch_filled(self) -> int:
+        """Bytes of scratch memory the diagnostic FSMC_DIAG_SCRATCH_FILL=<0..255> has filled on this context: 0 unless
+        the variable was set during a call."""
+        return int(self._L.fsmc_ctx_scratch_filled(self._h))
 
     def set_chunk_sites(self, sites: int):
         self._check(self._L.fsmc_ctx_set_chunk_sites(self._h, sites))

@@ -172,6 +172,8 @@ struct fsmc_ctx {
   DevBuf pxAcc;             // change probabilities: [edges, B + 1][weights, S ones][a slice's bin outputs, 2 x pairs x B]
   DevBuf ptAcc;             // tail summaries: [sum, n_tail x S doubles][edges, B + 1][weights, S][a slice's outputs, up to 2 x n_tail x pairs x B]
 
+  uint64_t scratchFilled = 0; // bytes FSMC_DIAG_SCRATCH_FILL has filled on this context (fsmc_ctx_scratch_filled)
+
   DevBuf idStash;       // fsmc_identify on overflow: the complete, ordered candidate list, kept for fsmc_identify_fetch
   size_t idStashCount = 0;
 
@@ -253,11 +255,48 @@ int fail(fsmc_ctx* ctx, int code, const std::string& msg)
     }                                                                                                                  \
   } while (0)
 
-int ensure(fsmc_ctx* ctx, DevBuf& b, size_t bytes)
+// FSMC_DIAG_SCRATCH_FILL=<0..255> (tests: every kernel on scratch memory an earlier launch left dirty): the byte every
+// scratch buffer holds, over its whole allocation, when an entry point takes it -- `fill`, -1 where the variable is not
+// set.  Read at every use, never cached: the tests set and unset it inside one process.  A value that is no integer in
+// 0..255 is an error, not "unset": a typo must not turn those tests into no-ops.
+int scratchFill(fsmc_ctx* ctx, int& fill)
 {
-  if (b.bytes >= bytes && b.p) {
+  fill = -1;
+  const char* s = std::getenv("FSMC_DIAG_SCRATCH_FILL");
+  if (!s) {
     return FSMC_OK;
   }
+  char* end = nullptr;
+  const long v = std::strtol(s, &end, 10);
+  if (end == s || *end != '\0' || v < 0 || v > 255 || !(*s >= '0' && *s <= '9')) {
+    return fail(ctx, FSMC_EINVAL, std::string("FSMC_DIAG_SCRATCH_FILL must be an integer in 0..255, not \"") + s + "\"");
+  }
+  fill = (int)v;
+  return FSMC_OK;
+}
+
+int allocate(fsmc_ctx* ctx, DevBuf& b, size_t bytes); // `b` freed, then `bytes` (16 at least) from hipMalloc
+
+// `b` holds at least `bytes` afterwards.  Every entry point calls this for each of its scratch buffers before its first
+// upload into them, so this is where FSMC_DIAG_SCRATCH_FILL dirties them: the whole allocation, new or held, on the
+// context's stream in front of everything the entry point writes there (the call sites, and why no live
+// data precedes any of them).  Unset, the variable adds no call.
+int ensure(fsmc_ctx* ctx, DevBuf& b, size_t bytes)
+{
+  int fill = -1;
+  FSMC_TRY(scratchFill(ctx, fill));
+  if (!(b.bytes >= bytes && b.p)) {
+    FSMC_TRY(allocate(ctx, b, bytes));
+  }
+  if (fill >= 0) {
+    FSMC_HIP(ctx, hipMemsetAsync(b.p, fill, b.bytes, ctx->stream));
+    ctx->scratchFilled += b.bytes;
+  }
+  return FSMC_OK;
+}
+
+int allocate(fsmc_ctx* ctx, DevBuf& b, size_t bytes)
+{
   if (b.p) {
     (void)hipFree(b.p);
     b.p = nullptr;
@@ -986,6 +1025,8 @@ uint64_t stagingLimit(const fsmc_ctx* ctx, uint64_t held, unsigned parts)
 // of `need` bytes each at least, the copy stream and its events.
 int ensureRowCopies(fsmc_ctx* ctx, size_t need)
 {
+  int fill = -1;
+  FSMC_TRY(scratchFill(ctx, fill));
   if (ctx->ppPinnedBytes < need) {
     for (int i = 0; i < 2; ++i) {
       if (ctx->ppPinned[i]) {
@@ -1002,6 +1043,12 @@ int ensureRowCopies(fsmc_ctx* ctx, size_t need)
       }
     }
     ctx->ppPinnedBytes = need;
+  }
+  if (fill >= 0) { // (no copy is in flight: every entry point has emptied both buffers when it returns)
+    for (int i = 0; i < 2; ++i) {
+      std::memset(ctx->ppPinned[i], fill, ctx->ppPinnedBytes);
+      ctx->scratchFilled += ctx->ppPinnedBytes;
+    }
   }
   if (!ctx->copyStream) {
     FSMC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copyStream, hipStreamNonBlocking));
@@ -1463,6 +1510,11 @@ int fsmc_ctx_info(const fsmc_ctx* ctx, int32_t* n_cu, int32_t* n_slots, uint64_t
   if (n_slots) *n_slots = ctx->lastSlots;
   if (hbm_bytes) *hbm_bytes = ctx->hbmBytes;
   return FSMC_OK;
+}
+
+uint64_t fsmc_ctx_scratch_filled(const fsmc_ctx* ctx)
+{
+  return ctx ? ctx->scratchFilled : 0;
 }
 
 int fsmc_ctx_set_workspace_limit(fsmc_ctx* ctx, uint64_t bytes)
@@ -1948,6 +2000,8 @@ int fsmc_identify_ex(fsmc_ctx* ctx, const uint64_t* words, uint32_t n_haps, uint
   if (gap < 0 || cap > 0xFFFFFFFFull) {
     return fail(ctx, FSMC_EINVAL, "fsmc_identify: gap < 0 or cap beyond 2^32");
   }
+  int fill = -1;
+  FSMC_TRY(scratchFill(ctx, fill));
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   const unsigned tiles = (n_haps + kIdTile - 1) / kIdTile;
   const unsigned chunks = (n_words + kIdChunk - 1) / kIdChunk;
@@ -1977,6 +2031,11 @@ int fsmc_identify_ex(fsmc_ctx* ctx, const uint64_t* words, uint32_t n_haps, uint
       b.p[i] = nullptr;
       return fail(ctx, FSMC_ENOMEM, std::string("fsmc_identify: hipMalloc failed: ") + hipGetErrorString(e));
     }
+  }
+  // (FSMC_DIAG_SCRATCH_FILL: buffers 3 to 7 are scratch, 0 to 2 the call's inputs)
+  for (int i = 3; fill >= 0 && i < 8; ++i) {
+    FSMC_HIP(ctx, hipMemsetAsync(b.p[i], fill, bytes[i], ctx->stream));
+    ctx->scratchFilled += bytes[i];
   }
   FSMC_HIP(ctx, hipMemcpyAsync(b.p[0], words, bytes[0], hipMemcpyHostToDevice, ctx->stream));
   FSMC_HIP(ctx, hipMemcpyAsync(b.p[1], global_ids, bytes[1], hipMemcpyHostToDevice, ctx->stream));

@@ -907,6 +907,21 @@ void HMM::flush()
   if (mGroups.empty()) {
     return;
   }
+  try {
+    flushQueued();
+  } catch (...) {
+    // a flush that failed leaves no work behind: the queue (flushPosteriorSums' closing entry of mBatchFirstGroup
+    // included) would otherwise be decoded again, on top of its own pairs, by the next call on this object
+    mPairs.clear();
+    mGroups.clear();
+    mBatchFirstGroup.clear();
+    mBatchBegin = 0;
+    throw;
+  }
+}
+
+void HMM::flushQueued()
+{
   ensureEngine();
   const size_t nPairs = mBatchBegin; // pairs covered by closed batches
   const Clock::time_point t0 = Clock::now();

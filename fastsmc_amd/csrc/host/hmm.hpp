@@ -211,7 +211,8 @@ private:
   void closeBatch(bool last);
   // flush what is queued under the old setting, assign(), updateOutputStructures()
   template <typename Assign> void changeOutputs(Assign&& assign);
-  void flush();
+  void flush();       // flushQueued(); if that throws, the queue is dropped before the exception goes on
+  void flushQueued(); // upload the closed batches' work list, decode every output asked for, keep the open batch's pairs
   // the parts of a flush, in its order (nPairs: the pairs of the closed batches, the flush's work list)
   std::vector<fsmc_ibd_record> fetchIbdRecords(size_t nPairs);
   void emitIbdRecords(const std::vector<fsmc_ibd_record>& recs);

@@ -143,6 +143,15 @@ void fsmc_ctx_destroy(fsmc_ctx* ctx);
 const char* fsmc_last_error(const fsmc_ctx* ctx);
 /* Device properties as seen by the library: CU count, and the number of resident decode waves it launches. */
 int fsmc_ctx_info(const fsmc_ctx* ctx, int32_t* n_cu, int32_t* n_slots, uint64_t* hbm_bytes);
+/* Diagnostic.  The library's scratch memory (the decode's workspace, the staging, row and accumulator buffers of the
+ * entry points, the two pinned row buffers, fsmc_identify's per-call buffers) is allocated once and reused; a kernel
+ * must write every cell of it before any kernel reads it.  FSMC_DIAG_SCRATCH_FILL=<0..255> in the environment makes an
+ * entry point fill every scratch buffer it is about to use with that byte, the whole allocation, before anything it
+ * writes there, so that a read of a cell not written in this call shows in the result (255: NaN / -1; 127: a huge finite
+ * value; 128: a tiny negative float, a very negative integer).  The variable is read at every call; a value that is no
+ * integer in 0..255 makes every such entry point return FSMC_EINVAL, nothing launched.  Results do not depend on it.
+ * Returns the bytes filled on this context since it was created: 0 unless the variable was set. */
+uint64_t fsmc_ctx_scratch_filled(const fsmc_ctx* ctx);
 /* Workspace for the alpha/beta streaming (bytes).  A limit set here is the caller's statement about the job: a plan may
  * use all of it at once -- windows kept whole instead of chunked, resident chunks, long windows in the paired kernel.
  * 0 (default): the library's own policy.  The rows a decode cannot do without may take up to 80 % of the card (at least
