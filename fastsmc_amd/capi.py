@@ -24,6 +24,15 @@ FSMC_WANT_MAJOR_MINOR_SUMS = 8
 
 FSMC_EOVERFLOW = -6
 
+# The sliced per-pair entry points by kind: fsmc_ctx_set_pair_<kind>_slice and fsmc_ctx_last_pair_<kind>_slices are the
+# setting and the getter of the entry point named here (Context.set_pair_<kind>_slice, Context.last_pair_<kind>_slices).
+PAIR_ENTRY_POINTS = {
+    "posterior": "fsmc_decode_pair_posteriors", "minima": "fsmc_decode_pair_minima", "bins": "fsmc_decode_pair_bins",
+    "cdf": "fsmc_decode_pair_cdf", "tail": "fsmc_decode_pair_tail_summaries", "loglik": "fsmc_decode_pair_loglik",
+    "viterbi": "fsmc_decode_pair_viterbi", "samples": "fsmc_decode_pair_samples",
+    "transitions": "fsmc_decode_pair_transitions",
+}
+
 # every symbol include/fastsmc_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
     "fsmc_ctx_create", "fsmc_ctx_destroy", "fsmc_last_error", "fsmc_ctx_info", "fsmc_ctx_set_workspace_limit",
@@ -35,17 +44,10 @@ SYMBOLS = [
     "fsmc_decode_ibd_launch", "fsmc_decode_ibd_fetch", "fsmc_sync", "fsmc_last_kernel_ms", "fsmc_phase_cycles",
     "fsmc_decode_ibd",
     "fsmc_decode_posteriors", "fsmc_decode_per_pair", "fsmc_decode_sums", "fsmc_decode_sums_batches",
-    "fsmc_decode_pair_posteriors", "fsmc_ctx_set_pair_posterior_slice", "fsmc_ctx_last_pair_posterior_slices",
-    "fsmc_decode_pair_minima", "fsmc_ctx_set_pair_minima_slice", "fsmc_ctx_last_pair_minima_slices",
-    "fsmc_decode_pair_bins", "fsmc_ctx_set_pair_bins_slice", "fsmc_ctx_last_pair_bins_slices",
-    "fsmc_decode_pair_cdf", "fsmc_ctx_set_pair_cdf_slice", "fsmc_ctx_last_pair_cdf_slices",
-    "fsmc_decode_pair_tail_summaries", "fsmc_ctx_set_pair_tail_slice", "fsmc_ctx_last_pair_tail_slices",
-    "fsmc_decode_pair_loglik", "fsmc_ctx_set_pair_loglik_slice", "fsmc_ctx_last_pair_loglik_slices",
-    "fsmc_decode_pair_viterbi", "fsmc_ctx_set_pair_viterbi_slice", "fsmc_ctx_last_pair_viterbi_slices",
-    "fsmc_decode_pair_samples", "fsmc_ctx_set_pair_samples_slice", "fsmc_ctx_last_pair_samples_slices",
-    "fsmc_decode_pair_transitions", "fsmc_ctx_set_pair_transitions_slice", "fsmc_ctx_last_pair_transitions_slices",
     "fsmc_identify", "fsmc_identify_ex", "fsmc_identify_fetch",
 ]
+for _kind, _entry in PAIR_ENTRY_POINTS.items():
+    SYMBOLS += [_entry, f"fsmc_ctx_set_pair_{_kind}_slice", f"fsmc_ctx_last_pair_{_kind}_slices"]
 
 PAIR_DTYPE = np.dtype([("hap_a", "<u4"), ("hap_b", "<u4")])
 GROUP_DTYPE = np.dtype([("first_pair", "<u4"), ("n_pairs", "<u4"), ("from", "<u4"), ("to", "<u4"),
@@ -141,32 +143,17 @@ def load():
         L.fsmc_decode_posteriors.argtypes = [vp, vp, vp, sz]
         L.fsmc_decode_per_pair.argtypes = [vp, vp, vp, vp, vp]
         L.fsmc_decode_pair_posteriors.argtypes = [vp, vp, vp, vp, vp]
-        L.fsmc_ctx_set_pair_posterior_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_posterior_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_minima.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
-        L.fsmc_ctx_set_pair_minima_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_minima_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_bins.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
-        L.fsmc_ctx_set_pair_bins_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_bins_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_cdf.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
-        L.fsmc_ctx_set_pair_cdf_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_cdf_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_tail_summaries.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
-        L.fsmc_ctx_set_pair_tail_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_tail_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_loglik.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
-        L.fsmc_ctx_set_pair_loglik_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_loglik_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_viterbi.argtypes = [vp, vp, vp, vp, vp]
-        L.fsmc_ctx_set_pair_viterbi_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_viterbi_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_samples.argtypes = [vp, vp, i32, C.c_uint64, vp]
-        L.fsmc_ctx_set_pair_samples_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_samples_slices.argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_pair_transitions.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
-        L.fsmc_ctx_set_pair_transitions_slice.argtypes = [vp, u32]
-        L.fsmc_ctx_last_pair_transitions_slices.argtypes = [vp, C.POINTER(i32)]
+        for kind in PAIR_ENTRY_POINTS:
+            getattr(L, f"fsmc_ctx_set_pair_{kind}_slice").argtypes = [vp, u32]
+            getattr(L, f"fsmc_ctx_last_pair_{kind}_slices").argtypes = [vp, C.POINTER(i32)]
         L.fsmc_decode_sums.argtypes = [vp, vp, vp, vp, vp, vp]
         L.fsmc_decode_sums_batches.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
         L.fsmc_identify.argtypes = [vp, vp, u32, u32, vp, C.POINTER(_JobWindow), vp, u32, i32, C.c_float, C.c_float, vp,
@@ -180,6 +167,24 @@ def load():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _bin_edges(bin_edges):
+    """(edges, n_bins) as the entry points with bins of sites take them: int32 edges in one dimension, None for None."""
+    if bin_edges is None:
+        return None, 0
+    edges = np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
+    if edges.size == 0:
+        return np.zeros(1, np.int32), 0  # (no edge at all: the library sees n_bins == 0)
+    return edges, int(edges.size) - 1
+
+
+def _writable(a, dtype, shape, at_least=None):
+    """``a`` is a writable C-contiguous array of ``dtype`` and ``shape``; along axis ``at_least`` (the pairs' axis of an
+    array that may hold more rows than the work list has pairs) it may be longer."""
+    return (a.dtype == dtype and a.flags.c_contiguous and a.flags.writeable and a.ndim == len(shape)
+            and all(have >= want if ax == at_least else have == want
+                    for ax, (have, want) in enumerate(zip(a.shape, shape))))
 
 
 def whole_sequence_groups(n_pairs: int, S: int, batch: int = 64) -> np.ndarray:
@@ -212,6 +217,12 @@ class Context:
     def _check(self, rc: int):
         if rc != 0:
             raise FsmcError(rc, (self._L.fsmc_last_error(self._h) or b"").decode())
+
+    def _last_i32(self, getter: str) -> int:
+        """What the library's ``getter``(ctx, int32_t*) reports."""
+        v = C.c_int32(0)
+        self._check(getattr(self._L, getter)(self._h, C.byref(v)))
+        return v.value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -247,9 +258,7 @@ class Context:
         self._check(self._L.fsmc_ctx_set_resident_chunks(self._h, chunks))
 
     def last_resident_chunks(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_resident_chunks(self._h, C.byref(v)))
-        return v.value
+        return self._last_i32("fsmc_ctx_last_resident_chunks")
 
     def set_chunk_pool(self, mode: int, phi_percent: int = 0):
         """The resident chunk buffers of a launch as one pool its waves claim from: -1 = in IBD launches of more than two
@@ -268,40 +277,30 @@ class Context:
         self._check(self._L.fsmc_ctx_set_beta_stride(self._h, stride))
 
     def last_beta_stride(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_beta_stride(self._h, C.byref(v)))
-        return v.value
+        return self._last_i32("fsmc_ctx_last_beta_stride")
 
     def last_kernel(self) -> int:
         """Kernel of the last launch: KT (16 ... 128) = the lane-per-pair family member, 1000 + KH (1048, 1064) = the
         four-waves-per-group kernel with KH states per wave."""
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_kernel(self._h, C.byref(v)))
-        return v.value
+        return self._last_i32("fsmc_ctx_last_kernel")
 
     def set_two_wave_windows(self, mode: int):
         """0 = automatic (small launches of the dump / per-pair / sums consumers give a window two waves), 1 = never."""
         self._check(self._L.fsmc_ctx_set_two_wave_windows(self._h, mode))
 
     def last_waves_per_window(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_waves_per_window(self._h, C.byref(v)))
-        return v.value
+        return self._last_i32("fsmc_ctx_last_waves_per_window")
 
     def set_pairing(self, mode: int):
         """1 (default): half-full groups with nearby windows share a wavefront; 0: groups run as uploaded."""
         self._check(self._L.fsmc_ctx_set_pairing(self._h, mode))
 
     def last_items(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_items(self._h, C.byref(v)))
-        return v.value
+        return self._last_i32("fsmc_ctx_last_items")
 
     def last_segment_sums_in_lds(self) -> bool:
         """The last IBD launch kept the open segments' per-state sums in LDS (a launch smaller than the chip)."""
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_segment_sums_in_lds(self._h, C.byref(v)))
-        return bool(v.value)
+        return bool(self._last_i32("fsmc_ctx_last_segment_sums_in_lds"))
 
     def set_workspace_limit(self, nbytes: int):
         self._check(self._L.fsmc_ctx_set_workspace_limit(self._h, nbytes))
@@ -421,21 +420,10 @@ class Context:
             rows = np.zeros((self._n_pairs, model.K, model.S), np.float32)
             ptrs = (C.c_void_p * self._n_pairs)(*[rows.ctypes.data + i * rows.strides[0] for i in range(self._n_pairs)])
         if sum_into is not None:
-            if (sum_into.dtype != np.float32 or not sum_into.flags.c_contiguous or not sum_into.flags.writeable
-                    or sum_into.shape != (model.K, model.S)):
+            if not _writable(sum_into, np.float32, (model.K, model.S)):
                 raise ValueError("sum_into: a writable C-contiguous float32 array [K][S]")
         self._check(self._L.fsmc_decode_pair_posteriors(self._h, model._h, _p(et), ptrs, _p(sum_into)))
         return rows, sum_into
-
-    def set_pair_posterior_slice(self, groups: int):
-        """Groups fsmc_decode_pair_posteriors puts through the device at a time; 0 = automatic.  Results do not depend
-        on it."""
-        self._check(self._L.fsmc_ctx_set_pair_posterior_slice(self._h, groups))
-
-    def last_pair_posterior_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_posterior_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_minima(self, model: "Model", exp_coal_times, pair_base=0, want_mean=True, want_map=True, state=None):
         """Per site the smallest posterior mean / MAP over the pairs of the resident work list and the first pair that
@@ -458,22 +446,11 @@ class Context:
         if len(state) != 4:
             raise ValueError("state: (min_mean, argmin_mean, min_map, argmin_map)")
         for a, dt in zip(state, (np.float32, np.int32, np.int32, np.int32)):
-            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable
-                                  or a.shape != (model.S,)):
+            if a is not None and not _writable(a, dt, (model.S,)):
                 raise ValueError("state: writable C-contiguous arrays [S], float32 for min_mean, int32 for the others")
         self._check(self._L.fsmc_decode_pair_minima(self._h, model._h, _p(et), int(pair_base), _p(state[0]),
                                                     _p(state[1]), _p(state[2]), _p(state[3])))
         return state
-
-    def set_pair_minima_slice(self, groups: int):
-        """Groups fsmc_decode_pair_minima puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_minima_slice(self._h, groups))
-
-    def last_pair_minima_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_minima_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_bins(self, model: "Model", exp_coal_times, bin_edges, want_mean=True, want_min_mean=True,
                          want_min_map=True, out=None):
@@ -485,10 +462,7 @@ class Context:
         et = np.ascontiguousarray(exp_coal_times, np.float32)
         if et.shape != (model.K,):
             raise ValueError(f"exp_coal_times: shape {et.shape}, expected {(model.K,)}")
-        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
-        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
-        if edges is not None and edges.size == 0:
-            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        edges, n_bins = _bin_edges(bin_edges)
         n = self._n_pairs
         dtypes = (np.float32, np.float32, np.int32, np.int32, np.int32)
         if out is None:
@@ -498,22 +472,11 @@ class Context:
         if len(out) != 5:
             raise ValueError("out: (bin_mean, bin_min_mean, bin_argmin_mean, bin_min_map, bin_argmin_map)")
         for a, dt in zip(out, dtypes):
-            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 2
-                                  or a.shape[0] < n or a.shape[1] != n_bins):
+            if a is not None and not _writable(a, dt, (n, n_bins), at_least=0):
                 raise ValueError("out: writable C-contiguous arrays [>= n_pairs][B], float32 for bin_mean and "
                                  "bin_min_mean, int32 for the others")
         self._check(self._L.fsmc_decode_pair_bins(self._h, model._h, _p(et), _p(edges), n_bins, *[_p(a) for a in out]))
         return out
-
-    def set_pair_bins_slice(self, groups: int):
-        """Groups fsmc_decode_pair_bins puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_bins_slice(self._h, groups))
-
-    def last_pair_bins_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_bins_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_loglik(self, model: "Model", bin_edges=None, want_total=True, out=None):
         """Per pair of the resident work list, the likelihood of its observations from the forward sweep alone
@@ -522,10 +485,7 @@ class Context:
         first site -- come with ``bin_edges``, the totals with ``want_total``; None for what was not asked for.
         ``log_likelihood(mant, expo)`` gives the natural logarithm.  ``out``: four such arrays (None where not wanted, at
         least n_pairs rows), written in place and returned as they are -- ``want_total`` is ignored then."""
-        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
-        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
-        if edges is not None and edges.size == 0:
-            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        edges, n_bins = _bin_edges(bin_edges)
         n = self._n_pairs
         dtypes = (np.float64, np.int32, np.float64, np.int32)
         if out is None:
@@ -535,25 +495,12 @@ class Context:
         out = tuple(out)
         if len(out) != 4:
             raise ValueError("out: (mant, expo, bin_mant, bin_expo)")
-        for i, (a, dt) in enumerate(zip(out, dtypes)):
-            if a is None:
-                continue
-            shape_ok = (a.ndim == 1) if i < 2 else (a.ndim == 2 and a.shape[1] == n_bins)
-            if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or not shape_ok or a.shape[0] < n:
+        for a, dt, shape in zip(out, dtypes, ((n,), (n,), (n, n_bins), (n, n_bins))):
+            if a is not None and not _writable(a, dt, shape, at_least=0):
                 raise ValueError("out: writable C-contiguous arrays, float64 mantissas and int32 exponents, [>= n_pairs] "
                                  "and [>= n_pairs][B]")
         self._check(self._L.fsmc_decode_pair_loglik(self._h, model._h, _p(edges), n_bins, *[_p(a) for a in out]))
         return out
-
-    def set_pair_loglik_slice(self, groups: int):
-        """Groups fsmc_decode_pair_loglik puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_loglik_slice(self._h, groups))
-
-    def last_pair_loglik_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_loglik_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_viterbi(self, model: "Model", want_states=True, want_prob=True, out=None):
         """Per pair of the resident work list, the most probable joint state sequence and its probability
@@ -568,25 +515,12 @@ class Context:
         out = tuple(out)
         if len(out) != 3:
             raise ValueError("out: (states, mant, expo)")
-        for i, (a, dt) in enumerate(zip(out, (np.uint8, np.float64, np.int32))):
-            if a is None:
-                continue
-            shape_ok = (a.ndim == 2 and a.shape[1] == S) if i == 0 else a.ndim == 1
-            if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or not shape_ok or a.shape[0] < n:
+        for a, dt, shape in zip(out, (np.uint8, np.float64, np.int32), ((n, S), (n,), (n,))):
+            if a is not None and not _writable(a, dt, shape, at_least=0):
                 raise ValueError("out: writable C-contiguous arrays, uint8 states [>= n_pairs][S], float64 mantissas and "
                                  "int32 exponents [>= n_pairs]")
         self._check(self._L.fsmc_decode_pair_viterbi(self._h, model._h, *[_p(a) for a in out]))
         return out
-
-    def set_pair_viterbi_slice(self, groups: int):
-        """Groups fsmc_decode_pair_viterbi puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_viterbi_slice(self._h, groups))
-
-    def last_pair_viterbi_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_viterbi_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_samples(self, model: "Model", n_samples, seed=0, out=None):
         """Per pair of the resident work list, ``n_samples`` (1 ... 64) state sequences drawn from the joint posterior over
@@ -602,21 +536,10 @@ class Context:
         rows = min(max(n_samples, 1), 64)  # (outside 1 ... 64 the library refuses the call)
         if out is None:
             out = np.zeros((n, rows, S), np.uint8)
-        if (not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous
-                or not out.flags.writeable or out.ndim != 3 or out.shape[1:] != (rows, S) or out.shape[0] < n):
+        if not isinstance(out, np.ndarray) or not _writable(out, np.uint8, (n, rows, S), at_least=0):
             raise ValueError("out: a writable C-contiguous uint8 array [>= n_pairs][n_samples][S]")
         self._check(self._L.fsmc_decode_pair_samples(self._h, model._h, n_samples, seed, _p(out)))
         return out
-
-    def set_pair_samples_slice(self, groups: int):
-        """Groups fsmc_decode_pair_samples puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_samples_slice(self._h, groups))
-
-    def last_pair_samples_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_samples_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_transitions(self, model: "Model", bin_edges=None, want_rows=True, out=None):
         """Per pair of the resident work list and site t, the posterior probability that the state at t is lower / higher
@@ -626,10 +549,7 @@ class Context:
         come with ``bin_edges``, the rows with ``want_rows``; None for what was not asked for.  ``out``: four such arrays
         (None where not wanted, at least n_pairs rows), written in place and returned as they are -- ``want_rows`` is
         ignored then."""
-        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
-        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
-        if edges is not None and edges.size == 0:
-            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        edges, n_bins = _bin_edges(bin_edges)
         n, S = self._n_pairs, model.S
         if out is None:
             out = (np.zeros((n, S), np.float32) if want_rows else None, np.zeros((n, S), np.float32) if want_rows else None,
@@ -645,22 +565,11 @@ class Context:
                 continue
             if i >= 2 and edges is None:
                 raise ValueError("out: the bin outputs need bin_edges")
-            if (not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or not a.flags.writeable
-                    or a.ndim != 2 or a.shape[1] != (S if i < 2 else n_bins) or a.shape[0] < n):
+            if not isinstance(a, np.ndarray) or not _writable(a, np.float32, (n, S if i < 2 else n_bins), at_least=0):
                 raise ValueError("out: writable C-contiguous float32 arrays, [>= n_pairs][S] rows and [>= n_pairs][B] bins")
         self._check(self._L.fsmc_decode_pair_transitions(self._h, model._h, _p(out[0]), _p(out[1]), _p(edges), n_bins,
                                                          _p(out[2]), _p(out[3])))
         return out
-
-    def set_pair_transitions_slice(self, groups: int):
-        """Groups fsmc_decode_pair_transitions puts through the device at a time; 0 = automatic.  Results do not depend
-        on it."""
-        self._check(self._L.fsmc_ctx_set_pair_transitions_slice(self._h, groups))
-
-    def last_pair_transitions_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_transitions_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_cdf(self, model: "Model", tail_states=(), quantiles=(), out=None):
         """Per pair of the resident work list and site, the running sum of the posterior over the states in ascending
@@ -675,8 +584,7 @@ class Context:
             out = (np.zeros((cuts.size, n, S), np.float32), np.zeros((qs.size, n, S), np.int32))
         tail, qstate = out
         for a, dt, m in ((tail, np.float32, cuts.size), (qstate, np.int32, qs.size)):
-            if (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 3 or a.shape[0] != m
-                    or a.shape[1] < n or a.shape[2] != S):
+            if not _writable(a, dt, (m, n, S), at_least=1):
                 raise ValueError("out: writable C-contiguous arrays (tail float32 [n_tail][>= n_pairs][S], qstate int32 "
                                  "[n_q][>= n_pairs][S])")
         tp = (C.c_void_p * max(cuts.size, 1))(*[tail[j].ctypes.data for j in range(cuts.size)])
@@ -686,16 +594,6 @@ class Context:
                                                  _p(qs) if qs.size else None, qs.size,
                                                  C.cast(qp, C.c_void_p) if qs.size else None))
         return tail, qstate
-
-    def set_pair_cdf_slice(self, groups: int):
-        """Groups fsmc_decode_pair_cdf puts through the device at a time; 0 = automatic.  Results do not depend on
-        it."""
-        self._check(self._L.fsmc_ctx_set_pair_cdf_slice(self._h, groups))
-
-    def last_pair_cdf_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_cdf_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_pair_tail_summaries(self, model: "Model", tail_states, bin_edges=None, site_weights=None, want_sum=True,
                                    want_bin_mean=None, want_bin_length=None, out=None):
@@ -708,10 +606,7 @@ class Context:
         such arrays (None where not wanted), written in place and returned as they are -- the ``want_*`` switches are
         ignored then, and tail_sum CONTINUES from what the array holds (zeros start a sum)."""
         cuts = np.ascontiguousarray(tail_states, np.int32).reshape(-1)
-        edges = None if bin_edges is None else np.ascontiguousarray(bin_edges, np.int32).reshape(-1)
-        n_bins = 0 if edges is None else max(int(edges.size) - 1, 0)
-        if edges is not None and edges.size == 0:
-            edges = np.zeros(1, np.int32)  # (no edge at all: the library sees n_bins == 0)
+        edges, n_bins = _bin_edges(bin_edges)
         w = None if site_weights is None else np.ascontiguousarray(site_weights, np.float32).reshape(-1)
         n, S = self._n_pairs, model.S
         if w is not None and w.shape != (S,):
@@ -729,7 +624,7 @@ class Context:
             raise ValueError("out: (tail_sum, bin_tail_mean, bin_tail_length)")
         for a, dt, shape in zip(out, (np.float64, np.float32, np.float32),
                                 ((cuts.size, S), (cuts.size, n, n_bins), (cuts.size, n, n_bins))):
-            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.shape != shape):
+            if a is not None and not _writable(a, dt, shape):
                 raise ValueError("out: writable C-contiguous arrays (tail_sum float64 [n_tail][S], bin_tail_mean and "
                                  "bin_tail_length float32 [n_tail][n_pairs][B])")
         # (an empty array has no address worth passing: the library sees NULL only where the output is not wanted)
@@ -737,16 +632,6 @@ class Context:
         self._check(self._L.fsmc_decode_pair_tail_summaries(self._h, model._h, _p(cuts) if cuts.size else None, cuts.size,
                                                             ptr[0], _p(edges), n_bins, ptr[1], _p(w), ptr[2]))
         return out
-
-    def set_pair_tail_slice(self, groups: int):
-        """Groups fsmc_decode_pair_tail_summaries puts through the device at a time; 0 = automatic.  Results do not
-        depend on it."""
-        self._check(self._L.fsmc_ctx_set_pair_tail_slice(self._h, groups))
-
-    def last_pair_tail_slices(self) -> int:
-        v = C.c_int32(0)
-        self._check(self._L.fsmc_ctx_last_pair_tail_slices(self._h, C.byref(v)))
-        return v.value
 
     def decode_sums(self, model: "Model", major_minor: bool = False, sums: bool = True, into=None, batch_first_group=None):
         """augmentSumOverPairs for the resident work list: arrays [S][K] (sum, and 00/01/11 when asked).  ``into`` =
@@ -779,6 +664,27 @@ class Context:
             res.append(out[o:o + n].reshape(int(g["to"] - g["from"]), model.K, 64))
             o += n
         return res
+
+
+def _pair_slice_methods(kind: str, entry: str):
+    """Context.set_pair_<kind>_slice and Context.last_pair_<kind>_slices of the entry point ``entry``."""
+    setter, getter = f"fsmc_ctx_set_pair_{kind}_slice", f"fsmc_ctx_last_pair_{kind}_slices"
+
+    def set_slice(self, groups: int):
+        self._check(getattr(self._L, setter)(self._h, groups))
+
+    def last_slices(self) -> int:
+        return self._last_i32(getter)
+
+    set_slice.__doc__ = f"Groups {entry} puts through the device at a time; 0 = automatic.  Results do not depend on it."
+    last_slices.__doc__ = f"Slices the last successful call of {entry} sent the work list through the device in."
+    for fn, name in ((set_slice, f"set_pair_{kind}_slice"), (last_slices, f"last_pair_{kind}_slices")):
+        fn.__name__, fn.__qualname__ = name, f"Context.{name}"
+        setattr(Context, name, fn)
+
+
+for _kind, _entry in PAIR_ENTRY_POINTS.items():
+    _pair_slice_methods(_kind, _entry)
 
 
 class Model:

@@ -728,34 +728,6 @@ int planOneWave(const fsmc_ctx* ctx, const fsmc_model* m, int mode, const Kernel
                            readDiag(), plan, why);
 }
 
-// plan::planViterbi for the Viterbi kernel `k`.  Computes only, like planOneWave.
-int planViterbi(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups, bool wantStates,
-                const plan::WsBudget& budget, LaunchPlan& plan, std::string& why)
-{
-  int perCU = 0;
-  const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
-  if (e != hipSuccess) {
-    why = std::string("occupancy query of the Viterbi kernel: ") + hipGetErrorString(e);
-    return FSMC_EHIP;
-  }
-  plan.k = k;
-  return plan::planViterbi(settingsOf(ctx), m->S, k.member, perCU, nGroups, wantStates, budget, plan, why);
-}
-
-// plan::planSamples for the sampling kernel `k`.  Computes only, like planViterbi.
-int planSamples(const fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups,
-                const plan::WsBudget& budget, LaunchPlan& plan, std::string& why)
-{
-  int perCU = 0;
-  const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
-  if (e != hipSuccess) {
-    why = std::string("occupancy query of the sampling kernel: ") + hipGetErrorString(e);
-    return FSMC_EHIP;
-  }
-  plan.k = k;
-  return plan::planSamples(settingsOf(ctx), m->S, k.member, perCU, nGroups, budget, plan, why);
-}
-
 // Two waves per window (plan::planTwoWaves).  twoWavesWanted: what can be said before the budget is read.
 bool twoWavesWanted(const fsmc_ctx* ctx, const KernelChoice& k2, size_t nItems)
 {
@@ -809,6 +781,41 @@ int planAndHold(fsmc_ctx* ctx, const fsmc_model* m, int mode, const KernelChoice
     FSMC_TRY(ensure(ctx, ctx->poolState, (kPoolClaims + (size_t)plan.poolBuffers) * sizeof(unsigned)));
   }
   return holdWorkspace(ctx, buf, plan.bytes);
+}
+
+// The launch of sweep kernel `k` (the `name` kernel, in the occupancy message) planned into the decode's workspace and
+// that workspace held: the credit the launch earns, then `planFn(perCU, budget, plan, why)` -- plan::planViterbi or
+// plan::planSamples with what the entry point knows -- over the kernel's workgroups a CU.
+template <typename PlanFn>
+int planSweepAndHold(fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, const char* name, PlanFn planFn,
+                     LaunchPlan& plan)
+{
+  earnWorkspace(ctx, m, kModePerPair);
+  const plan::WsBudget budget = workspaceBudget(ctx, ctx->ws);
+  int perCU = 0;
+  const hipError_t e = workgroupsPerCU(k, 8, 1, perCU);
+  if (e != hipSuccess) {
+    return fail(ctx, FSMC_EHIP, std::string("occupancy query of the ") + name + " kernel: " + hipGetErrorString(e));
+  }
+  plan.k = k;
+  std::string why;
+  const int rc = planFn(perCU, budget, plan, why);
+  if (rc != FSMC_OK) {
+    return fail(ctx, rc, why);
+  }
+  return holdWorkspace(ctx, ctx->ws, plan.bytes);
+}
+
+// planSweepAndHold with the sampling kernel's plan (fsmc_decode_pair_transitions' kernel takes the same workspace and
+// reports its occupancy as the sampling kernel's).
+int planSamplingSweep(fsmc_ctx* ctx, const fsmc_model* m, const KernelChoice& k, size_t nGroups, LaunchPlan& plan)
+{
+  return planSweepAndHold(
+      ctx, m, k, "sampling",
+      [&](int perCU, const plan::WsBudget& budget, LaunchPlan& pl, std::string& why) {
+        return plan::planSamples(settingsOf(ctx), m->S, k.member, perCU, nGroups, budget, pl, why);
+      },
+      plan);
 }
 
 // The launch the getters describe (fsmc_ctx_last_kernel, _last_beta_stride, _last_plan, _last_resident_chunks,
@@ -1073,10 +1080,7 @@ int prepareDecode(fsmc_ctx* ctx, const fsmc_model* m, int mode, uint32_t wantStr
 {
   const KernelChoice k = chooseKernel(m, mode, false, false, wantStride);
   earnWorkspace(ctx, m, mode);
-  int rc = planAndHold(ctx, m, mode, k, list, false, 1, ctx->ws, plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(planAndHold(ctx, m, mode, k, list, false, 1, ctx->ws, plan));
   size_t staged = nItems;
   if (stagingPerItem) {
     staged = plan::stagedItems(stagingLimit(ctx, ctx->out.bytes, 1), stagingPerItem, readDiag());
@@ -1090,10 +1094,7 @@ int prepareDecode(fsmc_ctx* ctx, const fsmc_model* m, int mode, uint32_t wantStr
       plan = plan2;
     } else {
       ctx->err.clear();
-      rc = holdWorkspace(ctx, ctx->ws, plan.bytes);
-      if (rc != FSMC_OK) {
-        return rc;
-      }
+      FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
     }
   }
   recordLaunch(ctx, plan.k, plan);
@@ -1144,12 +1145,12 @@ int checkWholeSequence(fsmc_ctx* ctx, const fsmc_model* m, const char* what)
 }
 
 // The slices of a call and its decode plan, `mode` kModeDump or kModePerPair -- or kNoDecode: the slices alone, for an
-// entry point that launches a kernel of its own: fsmc_decode_pair_loglik, which needs no workspace, and
-// fsmc_decode_pair_viterbi, which plans its own (planViterbi).  The slice is the caller's setting, or
-// what stagingLimit holds of `groupBytes` a group, of half the room the card has free with the `held` bytes this entry
-// point's buffers hold already counted as free -- the decode's workspace is allocated after this -- and `sliceMost`
-// groups at the most.  One wave per window: planned from the first slice's groups; two waves: a workgroup for each group
-// of a slice.
+// entry point that launches a sweep kernel of its own: fsmc_decode_pair_loglik, which needs no workspace, and
+// fsmc_decode_pair_viterbi, _samples and _transitions, which plan their own (planSweepAndHold).  The slice is the
+// caller's setting, or what stagingLimit holds of `groupBytes` a group, of half the room the card has free with the
+// `held` bytes this entry point's buffers hold already counted as free -- the decode's workspace is allocated after
+// this -- and `sliceMost` groups at the most.  One wave per window: planned from the first slice's groups; two waves: a
+// workgroup for each group of a slice.
 constexpr int kNoDecode = -1;
 int planSlices(fsmc_ctx* ctx, const fsmc_model* m, int mode, PairSlicing kind, uint64_t held, size_t groupBytes,
                WorkSlices& ws, size_t sliceMost = SIZE_MAX)
@@ -1231,6 +1232,44 @@ template <typename Params> void fillSweepParams(const fsmc_ctx* ctx, const fsmc_
   p.counter = ctx->dCounters;
 }
 
+// The sweep kernel of an entry point (`what`, as its messages begin) for a model: chooseSweepKernel's, or the refusal.
+// A kernel without a sequence mode (`sequenceMode` false) refuses more than 128 states, then a sequence-mode model, and
+// reports a member that was not built as FSMC_EUNSUPPORTED; the forward kernel, which has both modes, has one refusal.
+// `name`: the kernel, as the refusals call it.
+template <typename Params, typename Pick>
+int sweepKernelFor(fsmc_ctx* ctx, const fsmc_model* m, const char* what, const char* name, bool sequenceMode, Pick pick,
+                   SweepKernel<Params>& kern)
+{
+  const std::string noKernel = std::string(what) + ": no " + name + " kernel for a ";
+  const std::string tooManyStates = noKernel + "model of more than 128 states (" + std::to_string(m->K) + ")";
+  if (!sequenceMode && m->K > 128) {
+    return fail(ctx, FSMC_EINVAL, tooManyStates);
+  }
+  if (!sequenceMode && m->sequence) {
+    return fail(ctx, FSMC_EINVAL, noKernel + "sequence-mode model");
+  }
+  kern = chooseSweepKernel<Params>(m, pick);
+  if (!kern.fn) {
+    return sequenceMode ? fail(ctx, FSMC_EINVAL, tooManyStates)
+                        : fail(ctx, FSMC_EUNSUPPORTED, std::string(what) + ": no kernel for this model");
+  }
+  return FSMC_OK;
+}
+
+// The argument of a sweep kernel whose launch planSweepAndHold planned: zero but for fillSweepParams' fields and the
+// plan's -- the entry point adds its own --, and the record of the launch.
+template <typename Params> void plannedSweepParams(fsmc_ctx* ctx, const fsmc_model* m, const LaunchPlan& plan, Params& p)
+{
+  std::memset(&p, 0, sizeof(p));
+  fillSweepParams(ctx, m, p);
+  p.K = m->K;
+  p.chunk = plan.chunk;
+  p.nChunks = plan.maxChunks;
+  p.ws = (char*)ctx->ws.p;
+  p.slotBytes = plan.wsSlot * sizeof(float4);
+  recordLaunch(ctx, plan.k, plan);
+}
+
 // The sweep of slice `sl`: min(slots, groups) workgroups pull the slice's groups from the queue.  The call's timed span
 // runs from the first slice's launch to the last one's end.
 template <typename Params>
@@ -1297,6 +1336,22 @@ template <typename Chunk, typename Sink> int drainRows(fsmc_ctx* ctx, size_t nCh
   return FSMC_OK;
 }
 
+// A slice whose rows are one span on the device and one span of the caller's array: `bytes` from `src` leave for `dst`
+// through drainRows in copies of `copyBytes` -- spanCopyBytes' -- that need not end with a row.  (evRows is the entry
+// point's to record: once a slice, however many spans leave.)
+size_t spanCopyBytes(size_t slicePairsMax, size_t bytesPerPair)
+{
+  return std::max<size_t>(1, std::min(rowCopyBytes(), slicePairsMax * bytesPerPair));
+}
+int drainSpan(fsmc_ctx* ctx, const void* src, void* dst, size_t bytes, size_t copyBytes)
+{
+  auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
+  return drainRows(
+      ctx, (bytes + copyBytes - 1) / copyBytes,
+      [&](size_t c) { return RowChunk{(const char*)src + c * copyBytes, span(c)}; },
+      [&](size_t c, const char* host) { std::memcpy((char*)dst + c * copyBytes, host, span(c)); });
+}
+
 // The slice loop of the entry points whose rows leave through drainRows: slice by slice the decode, `reduce(sl)` -- the
 // launches that turn the slice's dump into rows -- and the end of the call's timed span (every decode and every
 // reduction).  `wantRows`: `drain(sl)` takes the rows of a slice to the caller while the next slice decodes, and
@@ -1355,6 +1410,48 @@ int tailSpecs(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, si
     }
     spec.push_back(PairCdfSpec{tail_states[j], 0.f});
   }
+  return FSMC_OK;
+}
+
+// The B + 1 edges of B bins of sites, to `dst` on the device; the caller's array is the source until the entry point
+// synchronises the stream.
+int uploadBinEdges(fsmc_ctx* ctx, void* dst, const int32_t* bin_edges, size_t B)
+{
+  FSMC_HIP(ctx, hipMemcpyAsync(dst, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  return FSMC_OK;
+}
+
+// Workgroups of pair_bins_kernel / pair_tail_bins_kernel over `cells` cells (pair x bin): a wave per cell, no more than
+// fill the chip `wavesDeep` deep over the `cuts` the grid's y dimension repeats them for.
+unsigned binBlocks(const fsmc_ctx* ctx, size_t wavesDeep, size_t cuts, size_t cells)
+{
+  const size_t wavesPerBlock = kPairBinsThreads / kWave;
+  const size_t blocksMax = std::max<size_t>(1, wavesDeep * (size_t)std::max(ctx->nCU, 1) / cuts);
+  return (unsigned)std::min(blocksMax, (cells + wavesPerBlock - 1) / wavesPerBlock);
+}
+
+// pair_cdf_kernel reduces a slice's dump in ppStage into ppRows, [output][pair of slice][S], the `nOut` outputs pcSpec
+// names: the argument but for the slice's fields, and the launch of slice `sl` -- a workgroup per group and site block.
+PairCdfParams cdfParams(const fsmc_ctx* ctx, const fsmc_model* m, const WorkSlices& ws, size_t nOut)
+{
+  PairCdfParams q;
+  q.stage = (const float*)ctx->ppStage.p;
+  q.K = m->K;
+  q.S = m->S;
+  q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
+  q.nOut = (int)nOut;
+  q.rows = (int*)ctx->ppRows.p;
+  q.rowsPerOut = ws.slicePairsMax;
+  return q;
+}
+int launchCdf(fsmc_ctx* ctx, const WorkSlices& ws, size_t sl, PairCdfParams& q)
+{
+  q.groups = ctx->dGroups + ws.firstGroup(sl);
+  q.nGroups = (int)ws.groups(sl);
+  q.firstPair = (unsigned)ws.firstPair(sl);
+  hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(ws.groups(sl) * layout::siteBlocks((size_t)q.S))),
+                     dim3(kPairCdfThreads), 0, ctx->stream, q);
+  FSMC_HIP(ctx, hipGetLastError());
   return FSMC_OK;
 }
 
@@ -1749,10 +1846,7 @@ int fsmc_haps_upload(fsmc_ctx* ctx, const uint64_t* bits, uint32_t n_haps, uint3
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t W = (n_sites + 63u) / 64u;
-  int rc = upload(ctx, &ctx->dHaps, (const unsigned long long*)bits, (size_t)n_haps * W);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(upload(ctx, &ctx->dHaps, (const unsigned long long*)bits, (size_t)n_haps * W));
   ctx->nHaps = n_haps;
   ctx->nSites = n_sites;
   ctx->W = W;
@@ -1771,13 +1865,8 @@ int fsmc_worklist_upload(fsmc_ctx* ctx, const fsmc_pair* pairs, size_t n_pairs, 
     return fail(ctx, checked, why);
   }
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = upload(ctx, &ctx->dPairs, pairs, n_pairs);
-  if (rc == FSMC_OK) {
-    rc = upload(ctx, &ctx->dGroups, groups, n_groups);
-  }
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(upload(ctx, &ctx->dPairs, pairs, n_pairs));
+  FSMC_TRY(upload(ctx, &ctx->dGroups, groups, n_groups));
   ctx->nPairs = n_pairs;
   ctx->nGroups = n_groups;
   ctx->hPairs.assign(pairs, pairs + n_pairs);
@@ -1834,10 +1923,7 @@ int fsmc_ctx_last_segment_sums_in_lds(const fsmc_ctx* ctx, int32_t* in_lds)
 
 int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   FSMC_HIP(ctx, hipSetDevice(ctx->device));
   const bool track = (flags & (FSMC_WANT_MEAN | FSMC_WANT_MAP)) != 0;
   earnWorkspace(ctx, m, kModeIbd);
@@ -1865,16 +1951,10 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
     }
     q.reordered = plan::longestFirst(q.rest) || q.dual;
     if (q.dual) {
-      rc = upload(ctx, &ctx->dItems, q.items.data(), q.items.size());
-      if (rc != FSMC_OK) {
-        return rc;
-      }
+      FSMC_TRY(upload(ctx, &ctx->dItems, q.items.data(), q.items.size()));
     }
     if (q.reordered && !q.rest.empty()) {
-      rc = upload(ctx, &ctx->dRest, q.rest.data(), q.rest.size());
-      if (rc != FSMC_OK) {
-        return rc;
-      }
+      FSMC_TRY(upload(ctx, &ctx->dRest, q.rest.data(), q.rest.size()));
     }
     q.serial = ctx->worklistSerial;
     q.pairing = pairing;
@@ -1884,18 +1964,12 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   const bool beside = q.dual && haveRest;
   LaunchPlan planDual, plan;
   if (q.dual) {
-    rc = planAndHold(ctx, m, kModeIbd, kDual, q.unions, true, q.alone ? 1 : 2, ctx->ws, planDual);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(planAndHold(ctx, m, kModeIbd, kDual, q.unions, true, q.alone ? 1 : 2, ctx->ws, planDual));
   }
   const KernelChoice k = chooseKernel(m, kModeIbd, track, false, ctx->betaStride);
   if (haveRest) {
-    rc = planAndHold(ctx, m, kModeIbd, k, q.reordered ? q.rest : ctx->hGroups, false, beside ? 2 : 1,
-                     beside ? ctx->wsSide : ctx->ws, plan);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(planAndHold(ctx, m, kModeIbd, k, q.reordered ? q.rest : ctx->hGroups, false, beside ? 2 : 1,
+                         beside ? ctx->wsSide : ctx->ws, plan));
   }
   // The getters describe the one-group-per-wave kernel (member, stride; also when every group rides in the paired
   // kernel) and its plan -- the paired kernel's plan where there is no other -- with the workgroups of both kernels.
@@ -1904,10 +1978,7 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
   if (ctx->recCap == 0) {
     ctx->recCap = std::max<size_t>(1u << 16, 8 * ctx->nPairs);
   }
-  rc = ensure(ctx, ctx->recs, ctx->recCap * sizeof(fsmc_ibd_record));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(ensure(ctx, ctx->recs, ctx->recCap * sizeof(fsmc_ibd_record)));
   KParams pDual, p;
   if (q.dual) {
     fillParams(ctx, m, planDual, flags, pDual);
@@ -1941,12 +2012,9 @@ int fsmc_decode_ibd_launch(fsmc_ctx* ctx, const fsmc_model* m, uint32_t flags)
     }
   }
   ctx->lastSpsLds = spsLdsBytes != 0;
-  rc = beside ? launchBeside(ctx, k, p, plan.slots, plan, kDual, pDual, planDual.slots)
-              : q.dual ? launch(ctx, kDual, pDual, planDual.slots)
-                       : launch(ctx, k, p, plan.slots, spsLdsBytes, false, &plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(beside ? launchBeside(ctx, k, p, plan.slots, plan, kDual, pDual, planDual.slots)
+                  : q.dual ? launch(ctx, kDual, pDual, planDual.slots)
+                           : launch(ctx, k, p, plan.slots, spsLdsBytes, false, &plan));
   ctx->ibdModel = m;
   ctx->ibdFlags = flags;
   ctx->ibdPending = true;
@@ -2225,10 +2293,7 @@ int fsmc_decode_ibd_fetch(fsmc_ctx* ctx, fsmc_ibd_record* out, size_t cap, size_
     }
     // the device buffer was too small: grow it and decode again (results are deterministic)
     ctx->recCap = (size_t)counters[1] + (size_t)counters[1] / 8 + 1024;
-    int rc = fsmc_decode_ibd_launch(ctx, ctx->ibdModel, ctx->ibdFlags);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(fsmc_decode_ibd_launch(ctx, ctx->ibdModel, ctx->ibdFlags));
   }
   const size_t n = counters[1];
   if (n > ctx->recCap) {
@@ -2265,10 +2330,7 @@ int fsmc_decode_ibd(fsmc_ctx* ctx, const fsmc_model* m, const fsmc_pair* pairs, 
 
 int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_t out_floats)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   if (!out) {
     return fail(ctx, FSMC_EINVAL, "out is null");
   }
@@ -2283,22 +2345,16 @@ int fsmc_decode_posteriors(fsmc_ctx* ctx, const fsmc_model* m, float* out, size_
     return fail(ctx, FSMC_EOVERFLOW, "posterior dump needs " + std::to_string(total) + " floats");
   }
   LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModeDump, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan);
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->aux, offsets.size() * sizeof(size_t));
-  if (rc == FSMC_OK) rc = ensure(ctx, ctx->out, total * sizeof(float));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(prepareDecode(ctx, m, kModeDump, ctx->betaStride, ctx->hGroups, ctx->nGroups, 0, plan));
+  FSMC_TRY(ensure(ctx, ctx->aux, offsets.size() * sizeof(size_t)));
+  FSMC_TRY(ensure(ctx, ctx->out, total * sizeof(float)));
   FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, offsets.data(), offsets.size() * sizeof(size_t), hipMemcpyHostToDevice,
                                ctx->stream));
   KParams p;
   fillParams(ctx, m, plan, 0, p);
   p.dumpOut = (float*)ctx->out.p;
   p.dumpOffsets = (const size_t*)ctx->aux.p;
-  rc = launch(ctx, plan.k, p, plan.slots);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(launch(ctx, plan.k, p, plan.slots));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   FSMC_HIP(ctx, hipMemcpy(out, ctx->out.p, total * sizeof(float), hipMemcpyDeviceToHost));
   return FSMC_OK;
@@ -2341,8 +2397,13 @@ int fsmc_decode_per_pair(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_co
 // (planSlices): the consumers of the decode kernel write a slice into ppStage -- the dump (dumpSetup) or the mean / MAP
 // rows (perPairSetup) -- the entry point's own kernels reduce it, and what is left of the slice goes to the caller before
 // the next slice overwrites it.  Rows leave through drainRows while the next slice decodes (decodeSlicesDrained); small
-// outputs by a blocking copy.  The stream is synchronised after the small uploads, whose sources are locals or the
-// caller's arrays, and at the end; the slice count of the call is recorded only then, on success.
+// outputs by a blocking copy (sliceToCaller).  The entry points that launch a sweep kernel instead of the decode
+// (kNoDecode) take the kernel from sweepKernelFor; the three that need a workspace plan it with planSweepAndHold, fill the
+// kernel's argument with plannedSweepParams, launch a slice with launchSweepSlice and send its rows, one span of the
+// caller's array, through drainSpan before the next launch.  What several entry points reduce a slice with is set up
+// once: the bin edges (uploadBinEdges), the grid of the bin kernels (binBlocks), pair_cdf_kernel (cdfParams, launchCdf).
+// The stream is synchronised after the small uploads, whose sources are locals or the caller's arrays, and at the end;
+// the slice count of the call is recorded only then, on success.
 
 // writePerPairOutput's posterior tables (HMM.cpp:1378-1392): pair_posteriors_kernel turns a slice's dump into rows,
 // [pair][K][S], and continues the sum over pairs.
@@ -2554,7 +2615,7 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   char* const acc = (char*)ctx->pbAcc.p;
   KParams p;
   FSMC_TRY(perPairSetup(ctx, m, exp_coal_times, acc + L.offCoal, wantMean, wantMap, ws, p));
-  FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, L.edgeBytes, hipMemcpyHostToDevice, ctx->stream));
+  FSMC_TRY(uploadBinEdges(ctx, acc + L.offEdges, bin_edges, B));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
   void* dOut[5];
@@ -2572,16 +2633,13 @@ int fsmc_decode_pair_bins(fsmc_ctx* ctx, const fsmc_model* m, const float* exp_c
   q.binArgMean = (int*)dOut[2];
   q.binMinMap = (int*)dOut[3];
   q.binArgMap = (int*)dOut[4];
-  // waves of the reduction: one per cell, no more than fill the chip eight deep
-  const size_t wavesPerBlock = kPairBinsThreads / kWave;
-  const size_t blocksMax = (size_t)8 * (size_t)std::max(ctx->nCU, 1);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     FSMC_TRY(launchSlice(ctx, ws, sl, p));
     const size_t n = ws.pairs(sl);
     q.n = (int)n;
-    const size_t blocks = std::min(blocksMax, (n * B + wavesPerBlock - 1) / wavesPerBlock);
-    hipLaunchKernelGGL(pair_bins_kernel, dim3((unsigned)blocks), dim3(kPairBinsThreads), 0, ctx->stream, q);
+    // (waves of the reduction: eight deep)
+    hipLaunchKernelGGL(pair_bins_kernel, dim3(binBlocks(ctx, 8, 1, n * B)), dim3(kPairBinsThreads), 0, ctx->stream, q);
     FSMC_HIP(ctx, hipGetLastError());
     FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every decode and every reduction)
     // the slice's outputs go to the caller before the next slice overwrites them (20 bytes a cell at most against the
@@ -2615,13 +2673,13 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
     FSMC_TRY(checkBinEdges(ctx, m, bin_edges, n_bins));
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "per-pair log-likelihoods"));
-  const SweepKernel<FwdParams> kern = chooseSweepKernel<FwdParams>(m, [&](auto kt) {
-    return m->sequence ? forward_kernel<decltype(kt)::value, true> : forward_kernel<decltype(kt)::value, false>;
-  });
-  if (!kern.fn) {
-    return fail(ctx, FSMC_EINVAL, "per-pair log-likelihoods: no forward kernel for a model of more than 128 states (" +
-                                      std::to_string(m->K) + ")");
-  }
+  SweepKernel<FwdParams> kern;
+  FSMC_TRY(sweepKernelFor(ctx, m, "per-pair log-likelihoods", "forward", true,
+                          [&](auto kt) {
+                            return m->sequence ? forward_kernel<decltype(kt)::value, true>
+                                               : forward_kernel<decltype(kt)::value, false>;
+                          },
+                          kern));
   const size_t B = bin_mant ? n_bins : 0;
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceLoglik, ctx->plAcc.bytes, layout::loglikGroupBytes(B), ws));
@@ -2639,7 +2697,7 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
   FSMC_TRY(ensure(ctx, ctx->plAcc, L.accBytes));
   char* const acc = (char*)ctx->plAcc.p;
   if (B) {
-    FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, L.edgeBytes, hipMemcpyHostToDevice, ctx->stream));
+    FSMC_TRY(uploadBinEdges(ctx, acc + L.offEdges, bin_edges, B));
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   FwdParams p;
@@ -2668,9 +2726,9 @@ int fsmc_decode_pair_loglik(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* b
 }
 
 // Per pair, the most probable joint state sequence and its probability (fsmc_pair_viterbi.h): one launch of
-// viterbi_kernel a slice, planned by planViterbi into the decode's workspace.  A slice's state rows, [pair][S] bytes in
-// ppRows, are one span of the caller's array: they leave through drainRows in copies that need not end with a row; the
-// mantissas and exponents by a blocking copy.  Slices are independent; a slice's rows have left before the next launch.
+// viterbi_kernel a slice, planned by plan::planViterbi into the decode's workspace (planSweepAndHold).  A slice's state
+// rows, [pair][S] bytes in ppRows, are one span of the caller's array: they leave through drainSpan; the mantissas and
+// exponents by a blocking copy.  Slices are independent; a slice's rows have left before the next launch.
 int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states, double* mant, int32_t* expo)
 {
   FSMC_TRY(checkReady(ctx, m));
@@ -2681,18 +2739,9 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
     return fail(ctx, FSMC_EINVAL, "need at least one output (states, or mant and expo)");
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "per-pair Viterbi paths"));
-  if (m->K > 128) {
-    return fail(ctx, FSMC_EINVAL, "per-pair Viterbi paths: no Viterbi kernel for a model of more than 128 states (" +
-                                      std::to_string(m->K) + ")");
-  }
-  if (m->sequence) {
-    return fail(ctx, FSMC_EINVAL, "per-pair Viterbi paths: no Viterbi kernel for a sequence-mode model");
-  }
-  const SweepKernel<VitParams> kern =
-      chooseSweepKernel<VitParams>(m, [](auto kt) { return viterbi_kernel<decltype(kt)::value>; });
-  if (!kern.fn) {
-    return fail(ctx, FSMC_EUNSUPPORTED, "per-pair Viterbi paths: no kernel for this model");
-  }
+  SweepKernel<VitParams> kern;
+  FSMC_TRY(sweepKernelFor(ctx, m, "per-pair Viterbi paths", "Viterbi", false,
+                          [](auto kt) { return viterbi_kernel<decltype(kt)::value>; }, kern));
   const size_t S = (size_t)m->S;
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceViterbi, ctx->ppRows.bytes + ctx->pvAcc.bytes,
@@ -2705,45 +2754,32 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
   if (mant) {
     FSMC_TRY(ensure(ctx, ctx->pvAcc, L.accBytes));
   }
-  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), n * S));
+  const size_t copyBytes = spanCopyBytes(n, S);
   if (states) {
     FSMC_TRY(ensureRowCopies(ctx, copyBytes));
   }
-  earnWorkspace(ctx, m, kModePerPair);
   LaunchPlan plan;
-  std::string why;
-  const int rc = planViterbi(ctx, m, kern.k, ws.slice, states != nullptr, workspaceBudget(ctx, ctx->ws), plan, why);
-  if (rc != FSMC_OK) {
-    return fail(ctx, rc, why);
-  }
-  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+  FSMC_TRY(planSweepAndHold(
+      ctx, m, kern.k, "Viterbi",
+      [&](int perCU, const plan::WsBudget& budget, LaunchPlan& pl, std::string& why) {
+        return plan::planViterbi(settingsOf(ctx), m->S, kern.k.member, perCU, ws.slice, states != nullptr, budget, pl,
+                                 why);
+      },
+      plan));
 
   char* const acc = (char*)ctx->pvAcc.p;
   VitParams p;
-  std::memset(&p, 0, sizeof(p));
-  fillSweepParams(ctx, m, p);
-  p.K = m->K;
-  p.chunk = plan.chunk;
-  p.nChunks = plan.maxChunks;
-  p.ws = (char*)ctx->ws.p;
-  p.slotBytes = plan.wsSlot * sizeof(float4);
+  plannedSweepParams(ctx, m, plan, p);
   p.states = states ? (unsigned char*)ctx->ppRows.p : nullptr;
   p.mant = mant ? (double*)(acc + L.offMant) : nullptr;
   p.expo = mant ? (int*)(acc + L.offExpo) : nullptr;
-  recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     const size_t first = ws.firstPair(sl), nP = ws.pairs(sl);
     FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     if (states && nP > 0) {
       FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
-      const size_t bytes = nP * S;
-      uint8_t* const dst = states + first * S;
-      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
-      FSMC_TRY(drainRows(
-          ctx, (bytes + copyBytes - 1) / copyBytes,
-          [&](size_t c) { return RowChunk{(const char*)ctx->ppRows.p + c * copyBytes, span(c)}; },
-          [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
+      FSMC_TRY(drainSpan(ctx, ctx->ppRows.p, states + first * S, nP * S, copyBytes));
     }
     // the slice's values go to the caller before the next slice overwrites them
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2755,8 +2791,8 @@ int fsmc_decode_pair_viterbi(fsmc_ctx* ctx, const fsmc_model* m, uint8_t* states
 }
 
 // Per pair, n_samples state sequences drawn from the joint posterior (fsmc_pair_samples.h): one launch of sample_kernel
-// a slice, planned by planSamples into the decode's workspace.  A slice's state rows, [pair][sample][S] bytes in ppRows,
-// are one span of the caller's array and leave through drainRows in copies that need not end with a row.  Slices are
+// a slice, planned by plan::planSamples into the decode's workspace (planSamplingSweep).  A slice's state rows,
+// [pair][sample][S] bytes in ppRows, are one span of the caller's array and leave through drainSpan.  Slices are
 // independent; a slice's rows have left before the next launch.
 int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_samples, uint64_t seed, uint8_t* states)
 {
@@ -2768,60 +2804,32 @@ int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_sampl
     return fail(ctx, FSMC_EINVAL, "sampled paths: states is null");
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "sampled paths"));
-  if (m->K > 128) {
-    return fail(ctx, FSMC_EINVAL, "sampled paths: no sampling kernel for a model of more than 128 states (" +
-                                      std::to_string(m->K) + ")");
-  }
-  if (m->sequence) {
-    return fail(ctx, FSMC_EINVAL, "sampled paths: no sampling kernel for a sequence-mode model");
-  }
-  const SweepKernel<SmpParams> kern =
-      chooseSweepKernel<SmpParams>(m, [](auto kt) { return sample_kernel<decltype(kt)::value>; });
-  if (!kern.fn) {
-    return fail(ctx, FSMC_EUNSUPPORTED, "sampled paths: no kernel for this model");
-  }
+  SweepKernel<SmpParams> kern;
+  FSMC_TRY(sweepKernelFor(ctx, m, "sampled paths", "sampling", false,
+                          [](auto kt) { return sample_kernel<decltype(kt)::value>; }, kern));
   const size_t S = (size_t)m->S, nS = (size_t)n_samples;
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceSamples, ctx->ppRows.bytes, layout::samplesGroupBytes(S, nS), ws));
   const layout::Samples L = layout::samples(S, nS, ws.slicePairsMax);
   FSMC_TRY(ensure(ctx, ctx->ppRows, L.rowsBytes));
-  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), ws.slicePairsMax * L.pairBytes));
+  const size_t copyBytes = spanCopyBytes(ws.slicePairsMax, L.pairBytes);
   FSMC_TRY(ensureRowCopies(ctx, copyBytes));
-  earnWorkspace(ctx, m, kModePerPair);
   LaunchPlan plan;
-  std::string why;
-  const int rc = planSamples(ctx, m, kern.k, ws.slice, workspaceBudget(ctx, ctx->ws), plan, why);
-  if (rc != FSMC_OK) {
-    return fail(ctx, rc, why);
-  }
-  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+  FSMC_TRY(planSamplingSweep(ctx, m, kern.k, ws.slice, plan));
 
   SmpParams p;
-  std::memset(&p, 0, sizeof(p));
-  fillSweepParams(ctx, m, p);
-  p.K = m->K;
-  p.chunk = plan.chunk;
-  p.nChunks = plan.maxChunks;
+  plannedSweepParams(ctx, m, plan, p);
   p.nSamples = n_samples;
   p.seedLo = (unsigned)(seed & 0xffffffffull);
   p.seedHi = (unsigned)(seed >> 32);
-  p.ws = (char*)ctx->ws.p;
-  p.slotBytes = plan.wsSlot * sizeof(float4);
   p.states = (unsigned char*)ctx->ppRows.p;
-  recordLaunch(ctx, kern.k, plan);
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     const size_t first = ws.firstPair(sl), nP = ws.pairs(sl);
     FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     if (nP > 0) {
       FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
-      const size_t bytes = nP * L.pairBytes;
-      uint8_t* const dst = states + first * L.pairBytes;
-      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
-      FSMC_TRY(drainRows(
-          ctx, (bytes + copyBytes - 1) / copyBytes,
-          [&](size_t c) { return RowChunk{(const char*)ctx->ppRows.p + c * copyBytes, span(c)}; },
-          [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
+      FSMC_TRY(drainSpan(ctx, ctx->ppRows.p, states + first * L.pairBytes, nP * L.pairBytes, copyBytes));
     }
     // the slice's rows have left before the next slice overwrites them
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2831,9 +2839,10 @@ int fsmc_decode_pair_samples(fsmc_ctx* ctx, const fsmc_model* m, int32_t n_sampl
 }
 
 // Per pair and site, the posterior probability that the state is lower / higher than at the site before
-// (fsmc_pair_transitions.h): one launch of transition_kernel a slice, planned by planSamples into the decode's workspace
-// (the workspace is the sampling kernel's).  A slice's rows, [down | up][pair][S] floats in ppRows, are two spans of the
-// caller's arrays and leave through drainRows; its bin sums are pair_tail_bins_kernel's bin_tail_length over weights of
+// (fsmc_pair_transitions.h): one launch of transition_kernel a slice, planned by planSamplingSweep into the decode's
+// workspace (the workspace is the sampling kernel's).  A slice's rows, [down | up][pair][S] floats in ppRows, are two spans
+// of the caller's arrays and leave through drainSpan, one after the other behind one record of evRows; its bin sums are
+// pair_tail_bins_kernel's bin_tail_length (binBlocks, four deep for each of the two outputs) over weights of
 // 1.f -- (double)p * 1.0 is p -- and leave by a blocking copy.  Slices are independent; a slice's rows have left before
 // the next launch.
 int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down_rows, float* up_rows,
@@ -2854,18 +2863,9 @@ int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down
     FSMC_TRY(checkBinEdges(ctx, m, bin_edges, (size_t)n_bins));
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "change probabilities"));
-  if (m->K > 128) {
-    return fail(ctx, FSMC_EINVAL, "change probabilities: no transition kernel for a model of more than 128 states (" +
-                                      std::to_string(m->K) + ")");
-  }
-  if (m->sequence) {
-    return fail(ctx, FSMC_EINVAL, "change probabilities: no transition kernel for a sequence-mode model");
-  }
-  const SweepKernel<TrnParams> kern =
-      chooseSweepKernel<TrnParams>(m, [](auto kt) { return transition_kernel<decltype(kt)::value>; });
-  if (!kern.fn) {
-    return fail(ctx, FSMC_EUNSUPPORTED, "change probabilities: no kernel for this model");
-  }
+  SweepKernel<TrnParams> kern;
+  FSMC_TRY(sweepKernelFor(ctx, m, "change probabilities", "transition", false,
+                          [](auto kt) { return transition_kernel<decltype(kt)::value>; }, kern));
   const size_t S = (size_t)m->S, B = wantBins ? (size_t)n_bins : 0;
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kNoDecode, kSliceTransitions, ctx->ppRows.bytes + ctx->pxAcc.bytes,
@@ -2879,41 +2879,27 @@ int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down
     FSMC_TRY(ensure(ctx, ctx->pxAcc, L.accBytes));
   }
   const bool wantRows = down_rows || up_rows;
-  const size_t copyBytes = std::max<size_t>(1, std::min(rowCopyBytes(), ws.slicePairsMax * S * sizeof(float)));
+  const size_t copyBytes = spanCopyBytes(ws.slicePairsMax, S * sizeof(float));
   if (wantRows) {
     FSMC_TRY(ensureRowCopies(ctx, copyBytes));
   }
-  earnWorkspace(ctx, m, kModePerPair);
   LaunchPlan plan;
-  std::string why;
-  const int rc = planSamples(ctx, m, kern.k, ws.slice, workspaceBudget(ctx, ctx->ws), plan, why);
-  if (rc != FSMC_OK) {
-    return fail(ctx, rc, why);
-  }
-  FSMC_TRY(holdWorkspace(ctx, ctx->ws, plan.bytes));
+  FSMC_TRY(planSamplingSweep(ctx, m, kern.k, ws.slice, plan));
 
   float* const dRows[2] = {(float*)ctx->ppRows.p, (float*)ctx->ppRows.p + L.rowsPerOut * S};
   char* const acc = (char*)ctx->pxAcc.p;
   std::vector<float> ones;
   if (wantBins) {
     ones.assign(S, 1.f);
-    FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 ctx->stream));
+    FSMC_TRY(uploadBinEdges(ctx, acc + L.offEdges, bin_edges, B));
     FSMC_HIP(ctx, hipMemcpyAsync(acc + L.offWeights, ones.data(), S * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   TrnParams p;
-  std::memset(&p, 0, sizeof(p));
-  fillSweepParams(ctx, m, p);
-  p.K = m->K;
+  plannedSweepParams(ctx, m, plan, p);
   p.ghostMask = m->ghostMask;
-  p.chunk = plan.chunk;
-  p.nChunks = plan.maxChunks;
-  p.ws = (char*)ctx->ws.p;
-  p.slotBytes = plan.wsSlot * sizeof(float4);
   p.down = dRows[0];
   p.up = dRows[1];
-  recordLaunch(ctx, kern.k, plan);
 
   PairTailParams r;
   std::memset(&r, 0, sizeof(r));
@@ -2926,8 +2912,6 @@ int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down
   r.weights = wantBins ? (const float*)(acc + L.offWeights) : nullptr;
   r.B = (int)B;
   r.binLength = dBins;
-  const size_t wavesPerBlock = kPairBinsThreads / kWave;
-  const size_t blocksMax = std::max<size_t>(1, (size_t)4 * (size_t)std::max(ctx->nCU, 1));
   float* const hRows[2] = {down_rows, up_rows};
   float* const hBins[2] = {bin_down, bin_up};
 
@@ -2936,24 +2920,18 @@ int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down
     FSMC_TRY(launchSweepSlice(ctx, ws, sl, kern, plan.slots, p));
     if (wantBins && nP > 0) {
       r.n = (int)nP;
-      const size_t blocks = std::min(blocksMax, (nP * B + wavesPerBlock - 1) / wavesPerBlock);
-      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3((unsigned)blocks, 2u), dim3(kPairBinsThreads), 0, ctx->stream, r);
+      // (waves of the reduction: four deep for each of the two outputs)
+      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3(binBlocks(ctx, 4, 1, nP * B), 2u), dim3(kPairBinsThreads), 0,
+                         ctx->stream, r);
       FSMC_HIP(ctx, hipGetLastError());
       FSMC_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); // (the call's timed span: every sweep and every reduction)
     }
     if (wantRows && nP > 0) {
       FSMC_HIP(ctx, hipEventRecord(ctx->evRows, ctx->stream));
-      const size_t bytes = nP * S * sizeof(float);
-      auto span = [&](size_t c) { return std::min(copyBytes, bytes - c * copyBytes); };
       for (int o = 0; o < 2; ++o) {
-        if (!hRows[o]) {
-          continue;
+        if (hRows[o]) {
+          FSMC_TRY(drainSpan(ctx, dRows[o], hRows[o] + first * S, nP * S * sizeof(float), copyBytes));
         }
-        char* const dst = (char*)(hRows[o] + first * S);
-        const char* const src = (const char*)dRows[o];
-        FSMC_TRY(drainRows(
-            ctx, (bytes + copyBytes - 1) / copyBytes, [&](size_t c) { return RowChunk{src + c * copyBytes, span(c)}; },
-            [&](size_t c, const char* host) { std::memcpy(dst + c * copyBytes, host, span(c)); }));
       }
     }
     // the slice's rows and cells have left before the next slice overwrites them
@@ -2969,7 +2947,7 @@ int fsmc_decode_pair_transitions(fsmc_ctx* ctx, const fsmc_model* m, float* down
 
 // Per pair and site, tail probabilities at state cuts and quantile states of the posterior (fsmc_pair_cdf.h), without the
 // [K][S] tables leaving the device: pair_cdf_kernel reduces a slice's dump into ppRows, [output][pair of slice][S], one
-// launch of a workgroup per group and site block.  Slices are independent.
+// launch of a workgroup per group and site block (cdfParams, launchCdf).  Slices are independent.
 int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
                          float* const* tail_rows, const float* quantiles, size_t n_quantiles,
                          int32_t* const* quantile_rows)
@@ -3008,7 +2986,6 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
   }
   FSMC_TRY(checkWholeSequence(ctx, m, "per-pair tails and quantiles"));
   const size_t K = (size_t)m->K, S = (size_t)m->S, nOut = spec.size();
-  const size_t siteBlocks = layout::siteBlocks(S);
   WorkSlices ws;
   FSMC_TRY(planSlices(ctx, m, kModeDump, kSliceCdf, ctx->ppStage.bytes + ctx->ppRows.bytes,
                       layout::cdfGroupBytes(K, S, nOut), ws, layout::sliceMostBySiteBlocks(S)));
@@ -3027,23 +3004,8 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
   FSMC_HIP(ctx, hipMemcpyAsync(ctx->pcSpec.p, spec.data(), L.specBytes, hipMemcpyHostToDevice, ctx->stream));
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  PairCdfParams q;
-  q.stage = (const float*)ctx->ppStage.p;
-  q.K = m->K;
-  q.S = m->S;
-  q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
-  q.nOut = (int)nOut;
-  q.rows = (int*)ctx->ppRows.p;
-  q.rowsPerOut = ws.slicePairsMax;
-  auto reduce = [&](size_t sl) -> int {
-    q.groups = ctx->dGroups + ws.firstGroup(sl);
-    q.nGroups = (int)ws.groups(sl);
-    q.firstPair = (unsigned)ws.firstPair(sl);
-    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(ws.groups(sl) * siteBlocks)), dim3(kPairCdfThreads), 0,
-                       ctx->stream, q);
-    FSMC_HIP(ctx, hipGetLastError());
-    return FSMC_OK;
-  };
+  PairCdfParams q = cdfParams(ctx, m, ws, nOut);
+  auto reduce = [&](size_t sl) -> int { return launchCdf(ctx, ws, sl, q); };
   // the slice's pairs are rows 0 ... of every output on the device, `outCells` apart: output by output, runs of cells
   // into the caller's matrix
   auto drain = [&](size_t sl) -> int {
@@ -3065,10 +3027,12 @@ int fsmc_decode_pair_cdf(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail
 }
 
 // The tail probabilities of fsmc_decode_pair_cdf reduced over pairs per site and over bins of sites per pair
-// (fsmc_pair_tail.h), without the tail rows leaving the device: pair_cdf_kernel -- as it is -- reduces a slice's dump into
-// ppRows, [cut][pair of slice][S]; then pair_tail_sum_kernel continues the fp64 chain of every site in the device copy of
-// the accumulator and pair_tail_bins_kernel reduces the rows cell by cell, and the slice's [cut][pairs][B] outputs are
-// copied to the caller's arrays at the slice's first pair.  Only the sum is carried from slice to slice.
+// (fsmc_pair_tail.h), without the tail rows leaving the device: pair_cdf_kernel -- as it is, through the cdfParams and
+// launchCdf of fsmc_decode_pair_cdf -- reduces a slice's dump into ppRows, [cut][pair of slice][S]; then
+// pair_tail_sum_kernel continues the fp64 chain of every site in the device copy of the accumulator and
+// pair_tail_bins_kernel (binBlocks, eight deep over the cuts) reduces the rows cell by cell, and the slice's
+// [cut][pairs][B] outputs are copied to the caller's arrays at the slice's first pair.  Only the sum is carried from
+// slice to slice.
 int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const int32_t* tail_states, size_t n_tail,
                                     double* tail_sum, const int32_t* bin_edges, size_t n_bins, float* bin_tail_mean,
                                     const float* site_weights, float* bin_tail_length)
@@ -3133,21 +3097,14 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
     FSMC_HIP(ctx, hipMemcpyAsync(dSum, tail_sum, sumBytes, hipMemcpyHostToDevice, ctx->stream));
   }
   if (wantBins) {
-    FSMC_HIP(ctx, hipMemcpyAsync(dEdges, bin_edges, (B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    FSMC_TRY(uploadBinEdges(ctx, dEdges, bin_edges, B));
   }
   if (bin_tail_length) {
     FSMC_HIP(ctx, hipMemcpyAsync(dWeights, site_weights, S * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   }
   FSMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  PairCdfParams q;
-  q.stage = (const float*)ctx->ppStage.p;
-  q.K = m->K;
-  q.S = m->S;
-  q.spec = (const PairCdfSpec*)ctx->pcSpec.p;
-  q.nOut = (int)nT;
-  q.rows = (int*)ctx->ppRows.p;
-  q.rowsPerOut = ws.slicePairsMax;
+  PairCdfParams q = cdfParams(ctx, m, ws, nT);
   PairTailParams r;
   r.rows = (const float*)ctx->ppRows.p;
   r.rowsPerOut = ws.slicePairsMax;
@@ -3159,28 +3116,21 @@ int fsmc_decode_pair_tail_summaries(fsmc_ctx* ctx, const fsmc_model* m, const in
   r.B = (int)B;
   r.binMean = dMean;
   r.binLength = dLength;
-  // waves of the bin reduction: one per cell, no more than fill the chip eight deep over the cuts
-  const size_t wavesPerBlock = kPairBinsThreads / kWave;
-  const size_t blocksMax = std::max<size_t>(1, (size_t)8 * (size_t)std::max(ctx->nCU, 1) / nT);
   float* const hOut[2] = {bin_tail_mean, bin_tail_length};
   const float* const dOut[2] = {dMean, dLength};
 
   for (size_t sl = 0; sl < ws.nSlices; ++sl) {
     FSMC_TRY(launchSlice(ctx, ws, sl, p));
-    const size_t nG = ws.groups(sl), firstPair = ws.firstPair(sl), n = ws.pairs(sl);
-    q.groups = ctx->dGroups + ws.firstGroup(sl);
-    q.nGroups = (int)nG;
-    q.firstPair = (unsigned)firstPair;
-    hipLaunchKernelGGL(pair_cdf_kernel, dim3((unsigned)(nG * siteBlocks)), dim3(kPairCdfThreads), 0, ctx->stream, q);
-    FSMC_HIP(ctx, hipGetLastError());
+    const size_t n = ws.pairs(sl);
+    FSMC_TRY(launchCdf(ctx, ws, sl, q));
     r.n = (int)n;
     if (tail_sum) {
       hipLaunchKernelGGL(pair_tail_sum_kernel, dim3((unsigned)siteBlocks, (unsigned)nT), dim3(kWave), 0, ctx->stream, r);
       FSMC_HIP(ctx, hipGetLastError());
     }
     if (wantBins) {
-      const size_t blocks = std::min(blocksMax, (n * B + wavesPerBlock - 1) / wavesPerBlock);
-      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3((unsigned)blocks, (unsigned)nT), dim3(kPairBinsThreads), 0,
+      // (waves of the bin reduction: eight deep over the cuts)
+      hipLaunchKernelGGL(pair_tail_bins_kernel, dim3(binBlocks(ctx, 8, nT, n * B), (unsigned)nT), dim3(kPairBinsThreads), 0,
                          ctx->stream, r);
       FSMC_HIP(ctx, hipGetLastError());
     }
@@ -3213,10 +3163,7 @@ int fsmc_decode_sums(fsmc_ctx* ctx, const fsmc_model* m, float* sums, float* sum
 int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t* batch_first_group, size_t n_batches,
                              float* sums, float* sums00, float* sums01, float* sums11)
 {
-  int rc = checkReady(ctx, m);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(checkReady(ctx, m));
   if (batch_first_group) {
     // batch b = groups batch_first_group[b] .. batch_first_group[b + 1] - 1: a partition of the group list, in order
     if (n_batches == 0 || batch_first_group[0] != 0 || batch_first_group[n_batches] != ctx->nGroups) {
@@ -3263,15 +3210,9 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   const int nP = mm ? 4 : 1; // planes per group: the sum, or the sum and its 00 / 01 / 11 split
   const size_t slotFloats = (size_t)nP * plane; // a slot holds the planes the launch was asked for
   LaunchPlan plan;
-  rc = prepareDecode(ctx, m, kModeSums, wantStride, ctx->hGroups, n_batches, slotFloats * sizeof(float), plan);
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(prepareDecode(ctx, m, kModeSums, wantStride, ctx->hGroups, n_batches, slotFloats * sizeof(float), plan));
   const size_t slots = (size_t)plan.slots;
-  rc = ensure(ctx, ctx->out, (slots + 1) * slotFloats * sizeof(float));
-  if (rc != FSMC_OK) {
-    return rc;
-  }
+  FSMC_TRY(ensure(ctx, ctx->out, (slots + 1) * slotFloats * sizeof(float)));
   float* const acc = (float*)ctx->out.p + slots * slotFloats;
   float* dst[4] = {sums, sums00, sums01, sums11};
   for (int q = 0; q < 4; ++q) {
@@ -3286,10 +3227,7 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   p.sumsPlane = plane;
   p.sumsSlot = slotFloats;
   if (batch_first_group) {
-    rc = ensure(ctx, ctx->aux, (n_batches + 1) * sizeof(uint32_t));
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(ensure(ctx, ctx->aux, (n_batches + 1) * sizeof(uint32_t)));
     FSMC_HIP(ctx, hipMemcpyAsync(ctx->aux.p, batch_first_group, (n_batches + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
                                  ctx->stream));
     p.batchFirst = (const unsigned*)ctx->aux.p;
@@ -3297,10 +3235,7 @@ int fsmc_decode_sums_batches(fsmc_ctx* ctx, const fsmc_model* m, const uint32_t*
   for (size_t base = 0; base < n_batches; base += slots) {
     const size_t n = std::min(slots, n_batches - base);
     p.groupBase = (int)base;
-    rc = launch(ctx, plan.k, p, (int)n, 0, base != 0, &plan);
-    if (rc != FSMC_OK) {
-      return rc;
-    }
+    FSMC_TRY(launch(ctx, plan.k, p, (int)n, 0, base != 0, &plan));
     // (planes the launch did not ask for hold stale values: they are added to accumulator planes nobody reads)
     hipLaunchKernelGGL(add_planes_in_order_kernel, dim3(1024), dim3(256), 0, ctx->stream, (const float*)ctx->out.p, acc,
                        slotFloats, (int)n, slotFloats);
