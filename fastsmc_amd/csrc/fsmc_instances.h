@@ -32,7 +32,9 @@
 // What the families share is defined once: fsmc_lane_scaffold.h (a lane's pair and haplotype rows, the next group of a
 //   sums batch, the row-index block),
 //   fsmc_site_consumers.h (the per-pair mean / MAP consumer, the IBD record writer), both included by fsmc_kernels.h;
-//   fsmc_pair_sweep.h (what only the two sweep kernels need).
+//   fsmc_pair_sweep.h (what only the four per-pair sweep kernels above need: the group queue, observation words and
+//   emission ring, their constants, the forward step, the packing of state rows, and the one description of the
+//   checkpointed replay that the Viterbi, sampling and transition kernels run).
 // (The runtime-K instantiation KT = 0 and the four-lanes-per-pair kernel of earlier builds are gone: every model of at
 //  most 256 states, in every mode, runs one of the two families above.)
 #pragma once

@@ -76,13 +76,11 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
 {
   static_assert(KT >= 2 && KT <= 128, "a lane-per-pair member (fsmc_instances.h)");
   constexpr int KA = KT;
+  using Sh = SweepShape<KT, SEQ ? 4 : 3>; // rows per site: the observation classes (+ the gap)
   constexpr int K = KT;
-  constexpr int E4 = ((KT + kKPad - 1) / kKPad) * (kKPad / 4); // float4 per emission row: KP / 4 of the member's models
-  constexpr int NC = SEQ ? 4 : 3;                              // rows per site: the observation classes (+ the gap)
-  constexpr int NL = (NC * E4 + kWave - 1) / kWave;            // DMA requests per site
   constexpr bool SY = kFwdSyncLoads<KT, SEQ>;
 
-  __shared__ float4 ring[2][NC * E4];
+  __shared__ float4 ring[2][Sh::NC * Sh::E4];
 
   const int lane = threadIdx.x;
   const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
     RowIndexBlock stepRows, gapRows;
     // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
+      stageRows<Sh::NL>(sp.emis3 + (size_t)q * (Sh::NC * Sh::E4), ring[q & 1], Sh::NC * Sh::E4, lane, laneOff);
     };
 
     // the open bin: [lo, hi) = edges[bin], edges[bin + 1]; beyond the last bin lo = INT_MAX
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
         stage(pos + 1); // into the slot of site pos - 1, whose steps are over
       }
       const int c = obs.classAt(pos);
-      const float4* er = &ring[pos & 1][c * E4];
+      const float4* er = &ring[pos & 1][c * Sh::E4];
       float sum;
       if (__builtin_expect(pos == 0, 0)) {
         sum = forwardInit<KT, KA>(a, tPi, er);
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void forward_kernel(con
         if (pos + 1 < S) {
           landedRows(); // the rows of site pos + 1: its fourth row is the homozygous emission of the gap before it
           alpha_step<KT, KA, false, SY>(K, a, w, tabs, gapRows.at(p.rowGapF, S, lane, pos + 1),
-                                        &ring[(pos + 1) & 1][3 * E4], dg);
+                                        &ring[(pos + 1) & 1][3 * Sh::E4], dg);
         }
       }
     }

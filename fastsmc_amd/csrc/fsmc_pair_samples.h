@@ -36,19 +36,15 @@
 // value itself.  c[0] is w[0] itself (0.f + w[0]).
 //
 // sample_kernel<KT>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue.  The
-// surroundings of the forward step are fsmc_pair_sweep.h's, the step is forward_kernel's (alpha_step, the ascending
-// sum, scale_pk).
+// surroundings of the forward step are fsmc_pair_sweep.h's, the step is forward_kernel's (forwardStep, scale_pk).
 // Workspace of a wave: [chunk sites][KT4][64 lanes] float4 of delta rows (KT4 = ceil(KT / 4), coalesced 1-KiB stores),
-// then [chunks][KT4][64] float4 of checkpoints.  Sweep 1 runs the whole sequence and leaves delta of the site before
-// each chunk as a checkpoint and the rows of the LAST chunk in the buffer (the rows of earlier chunks all land on the
-// buffer's first row: no branch in the step).  Chunk by chunk descending: every chunk but the last is swept again from
-// its checkpoint for its rows, then walked down.  The walk is site-outer and sample-inner: a delta row is loaded once
+// then [chunks][KT4][64] float4 of checkpoints: the checkpointed replay of fsmc_pair_sweep.h, a row being delta of its
+// site.  The walk is site-outer and sample-inner: a delta row is loaded once
 // for all n samples.  A sample and site take three passes over the K registers: the weights descending with the
 // predicated g chain (U and cR as scalar operand blocks like alpha_step's; D[j] and B[j] gathered per lane, the next
 // sample's one sample ahead), the running sums ascending in place, the count.
 // A lane's n samples each keep one dword in LDS: the bytes of the output dword under construction, among them the state
-// of site t+1.  State rows leave as aligned dwords of four sites with single bytes at a row's two ends (rows are S bytes
-// apart, so neighbouring rows share dwords where S % 4 != 0).  Vector stores only.
+// of site t+1.  The states leave through packState (fsmc_pair_sweep.h); the dword stays in LDS beyond its store.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -156,15 +152,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
 {
   static_assert(KT >= 2 && KT <= 128, "a lane-per-pair member (fsmc_instances.h)");
   constexpr int KA = KT;
-  constexpr int KPc = ((KT + kKPad - 1) / kKPad) * kKPad;
-  constexpr int E4 = KPc / 4;                       // float4 per emission row: KP / 4 of the member's models
-  constexpr int NC = 3;                             // rows per site: the observation classes
-  constexpr int NL = (NC * E4 + kWave - 1) / kWave; // DMA requests per site
-  constexpr int K4 = (KT + 3) / 4;
+  using Sh = SweepShape<KT, 3>;
   constexpr bool SY = kSmpSyncLoads<KT>;
-  constexpr size_t kRow = (size_t)K4 * kWave * sizeof(float4); // bytes of a stored vector
 
-  __shared__ float4 ring[2][NC * E4];
+  __shared__ float4 ring[2][Sh::NC * Sh::E4];
   __shared__ unsigned accs[kMaxSamples][kWave]; // a sample's output dword under construction, per lane
 
   const int lane = threadIdx.x;
@@ -178,7 +169,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
   const int n = p.nSamples;
   char* const slot = p.ws + (size_t)blockIdx.x * p.slotBytes;
   char* const rowBuf = slot;
-  char* const ckptBuf = slot + (size_t)C * kRow;
+  char* const ckptBuf = slot + (size_t)C * Sh::kVecBytes;
   const int lastStart = (nChunks - 1) * C; // sweep 1 keeps the rows from this site on
   const unsigned kTop = (unsigned)(p.K - 1);
   unsigned char* const out = p.states;
@@ -194,7 +185,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
     RowIndexBlock stepRows;
     // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
+      stageRows<Sh::NL>(sp.emis3 + (size_t)q * (Sh::NC * Sh::E4), ring[q & 1], Sh::NC * Sh::E4, lane, laneOff);
     };
 
     float a[KA], w[KA];
@@ -203,20 +194,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
     // one site of a forward sweep: delta of site pos in a, stored as row `r` of the buffer
     auto forwardSite = [&](const int pos, const int r) {
       const int c = obs.classAt(pos);
-      const float4* er = &ring[pos & 1][c * E4];
-      float sum;
-      if (__builtin_expect(pos == 0, 0)) {
-        sum = forwardInit<KT, KA>(a, tPi, er);
-      } else {
-        alpha_step<KT, KA, false, SY>(KT, a, w, tabs, stepRows.at(sp.stepRow, S, lane, pos), er, dg);
-        sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-          sum = sum + a[k];
-        }
-      }
+      const float4* er = &ring[pos & 1][c * Sh::E4];
+      const float sum = forwardStep<KT, KA, SY>(a, w, er, tPi, tabs, stepRows, sp.stepRow, S, lane, pos, dg);
       scale_pk<KT, KA>(a, a, sum);
-      store_vec<KT, KA>(KT, (float4*)(rowBuf + (size_t)r * kRow), laneOff, a);
+      store_vec<KT, KA>(KT, (float4*)(rowBuf + (size_t)r * Sh::kVecBytes), laneOff, a);
     };
 
     // ---- sweep 1: the whole sequence
@@ -227,7 +208,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         stage(pos + 1); // into the slot of site pos - 1, whose step is over
       }
       if (pos > 0 && pos % C == 0) { // delta of the site before chunk pos / C
-        store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * kRow), laneOff, a);
+        store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * Sh::kVecBytes), laneOff, a);
       }
       forwardSite(pos, pos >= lastStart ? pos - lastStart : 0);
     }
@@ -245,7 +226,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         waitVm0(); // (nothing of the walk before is in flight when the ring is restarted)
         stage(lo);
         if (lo > 0) {
-          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * kRow), laneOff, a);
+          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * Sh::kVecBytes), laneOff, a);
         }
         for (int pos = lo; pos <= hi; ++pos) {
           landedRows();
@@ -257,12 +238,12 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
       }
       waitVm0(); // the chunk's rows are written
       for (int t = hi; t >= lo; --t) {
-        load_vec<KT, KA>(KT, (const float4*)(rowBuf + (size_t)(t - lo) * kRow), laneOff, a);
+        load_vec<KT, KA>(KT, (const float4*)(rowBuf + (size_t)(t - lo) * Sh::kVecBytes), laneOff, a);
         const bool top = t == S - 1;
         const int row = top ? 0 : stepRows.at(sp.stepRow, S, lane, t + 1);
         const cfloat_p rowSet = rowSetOf<KT>(tabs, row);
-        const float* const rowD = p.rowSets + (size_t)row * (kRowSetParts * KPc) + kRowD * KPc;
-        const float* const rowB = p.rowSets + (size_t)row * (kRowSetParts * KPc) + kRowB * KPc;
+        const float* const rowD = p.rowSets + (size_t)row * (kRowSetParts * Sh::KPc) + kRowD * Sh::KPc;
+        const float* const rowB = p.rowSets + (size_t)row * (kRowSetParts * Sh::KPc) + kRowB * Sh::KPc;
         // the state of site t + 1 of sample r and its two table entries, one sample ahead
         auto carried = [&](const int r, unsigned& acc, unsigned& j, float& dj, float& bj) {
           acc = accs[r][lane];
@@ -292,27 +273,8 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
           const float u = sampleUniform(p.seedLo, p.seedHi, pr.hap_a, pr.hap_b, (unsigned)r, (unsigned)t);
           unsigned x = sample_pick<KT, KA>(w, u);
           x = x < kTop ? x : kTop;
-          // the state of site t into its byte of the output
-          const size_t rowByte = (pairRow + (size_t)r) * (size_t)S;
-          const size_t A = rowByte + (size_t)t;
-          const unsigned sh = 8u * ((unsigned)A & 3u);
-          acc = (acc & ~(0xffu << sh)) | (x << sh);
-          if (((unsigned)A & 3u) == 0u || t == 0) {
-            const size_t D4 = A & ~(size_t)3;
-            if (pl.valid) {
-              if (((unsigned)A & 3u) == 0u && t + 3 < S) {
-                *(unsigned*)(out + D4) = acc;
-              } else {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                  const long long site = (long long)(D4 + (size_t)b) - (long long)rowByte;
-                  if (site >= (long long)t && site < (long long)S) {
-                    out[D4 + (size_t)b] = (unsigned char)((acc >> (8 * b)) & 0xffu);
-                  }
-                }
-              }
-            }
-          }
+          // (the dword stays in LDS beyond its store: the state of site t is the next site's j)
+          (void)packState(acc, x, out, (pairRow + (size_t)r) * (size_t)S, t, S, pl.valid);
           accs[r][lane] = acc;
         }
       }

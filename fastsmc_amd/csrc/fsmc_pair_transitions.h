@@ -34,10 +34,10 @@
 //
 // transition_kernel<KT>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue
 // (fsmc_pair_sweep.h).  The workspace of a wave is sample_kernel's (planSamples): [chunk sites][KT4][64 lanes] float4
-// of delta rows, then [chunks][KT4][64] float4 of checkpoints.  Sweep 1 is sample_kernel's: the whole sequence, delta of
-// the site before each chunk as a checkpoint, the rows of the last chunk in the buffer.  Then chunk by chunk descending:
-// every chunk but the last is swept again from its checkpoint for its rows (b waits in checkpoint slot 0, which no chunk
-// uses: a lane holds two K-vectors at any time), then walked down with b in registers.  A site of the walk is one
+// of delta rows, then [chunks][KT4][64] float4 of checkpoints: the checkpointed replay of fsmc_pair_sweep.h with
+// sample_kernel's site step (forwardStep, scale_pk, the row stored).  While a chunk is swept again b waits in
+// checkpoint slot 0, which no chunk uses (a lane holds two K-vectors at any time); a chunk that holds site 0 alone is
+// neither swept nor walked.  Then the chunk is walked down with b in registers.  A site of the walk is one
 // backward step (transition_core_pk: beta_core_pk's recurrences with the three accumulators in the ascending pass, where
 // BL, D * vec and BU are live); the row of t-1 is not held but read in blocks of sixteen states one block ahead of the
 // ascending pass.  At a chunk's first site the row of t-1 is the chunk's checkpoint.
@@ -300,15 +300,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
 {
   static_assert(KT >= 2 && KT <= 128, "a lane-per-pair member (fsmc_instances.h)");
   constexpr int KA = KT;
-  constexpr int KPc = ((KT + kKPad - 1) / kKPad) * kKPad;
-  constexpr int E4 = KPc / 4;                       // float4 per emission row: KP / 4 of the member's models
-  constexpr int NC = 3;                             // rows per site: the observation classes
-  constexpr int NL = (NC * E4 + kWave - 1) / kWave; // DMA requests per site
-  constexpr int K4 = (KT + 3) / 4;
+  using Sh = SweepShape<KT, 3>;
   constexpr bool SY = kTrnSyncLoads<KT>;
-  constexpr size_t kRow = (size_t)K4 * kWave * sizeof(float4); // bytes of a stored vector
 
-  __shared__ float4 ring[2][NC * E4];
+  __shared__ float4 ring[2][Sh::NC * Sh::E4];
 
   const int lane = threadIdx.x;
   const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
@@ -320,7 +315,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
   const int nChunks = p.nChunks;
   char* const slot = p.ws + (size_t)blockIdx.x * p.slotBytes;
   char* const rowBuf = slot;
-  char* const ckptBuf = slot + (size_t)C * kRow; // (slot 0 belongs to no chunk: b waits there during a chunk's sweep)
+  char* const ckptBuf = slot + (size_t)C * Sh::kVecBytes; // (slot 0 belongs to no chunk: b waits there during a chunk's sweep)
   const int lastStart = (nChunks - 1) * C;       // sweep 1 keeps the rows from this site on
 
   for (;;) {
@@ -333,7 +328,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
     RowIndexBlock stepRows;
     // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
+      stageRows<Sh::NL>(sp.emis3 + (size_t)q * (Sh::NC * Sh::E4), ring[q & 1], Sh::NC * Sh::E4, lane, laneOff);
     };
 
     float a[KA], w[KA]; // a: delta in the sweeps, b in the walk
@@ -342,20 +337,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
     // one site of a forward sweep: delta of site pos in a, stored as row `r` of the buffer
     auto forwardSite = [&](const int pos, const int r) {
       const int c = obs.classAt(pos);
-      const float4* er = &ring[pos & 1][c * E4];
-      float sum;
-      if (__builtin_expect(pos == 0, 0)) {
-        sum = forwardInit<KT, KA>(a, tPi, er);
-      } else {
-        alpha_step<KT, KA, false, SY>(KT, a, w, tabs, stepRows.at(sp.stepRow, S, lane, pos), er, dg);
-        sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-          sum = sum + a[k];
-        }
-      }
+      const float4* er = &ring[pos & 1][c * Sh::E4];
+      const float sum = forwardStep<KT, KA, SY>(a, w, er, tPi, tabs, stepRows, sp.stepRow, S, lane, pos, dg);
       scale_pk<KT, KA>(a, a, sum);
-      store_vec<KT, KA>(KT, (float4*)(rowBuf + (size_t)r * kRow), laneOff, a);
+      store_vec<KT, KA>(KT, (float4*)(rowBuf + (size_t)r * Sh::kVecBytes), laneOff, a);
     };
 
     // the values of site t into this lane's two rows: four sites of each in registers, out as aligned float4 where the
@@ -400,7 +385,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         stage(pos + 1); // into the slot of site pos - 1, whose step is over
       }
       if (pos > 0 && pos % C == 0) { // delta of the site before chunk pos / C
-        store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * kRow), laneOff, a);
+        store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * Sh::kVecBytes), laneOff, a);
       }
       forwardSite(pos, pos >= lastStart ? pos - lastStart : 0);
     }
@@ -420,7 +405,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         waitVm0(); // (nothing of the walk before is in flight when the ring is restarted)
         stage(lo);
         if (lo > 0) {
-          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * kRow), laneOff, a);
+          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * Sh::kVecBytes), laneOff, a);
         }
         for (int pos = lo; pos <= hi; ++pos) {
           landedRows();
@@ -440,10 +425,10 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
           stage(t - 1); // into the slot of site t + 1, whose step is over
         }
         const int c = obs.classAt(t);
-        const float4* er = &ring[t & 1][c * E4];
+        const float4* er = &ring[t & 1][c * Sh::E4];
         const cfloat_p rowSet = rowSetOf<KT>(tabs, stepRows.at(sp.stepRow, S, lane, t));
         // delta of site t - 1: a row of the chunk, or the checkpoint in front of it
-        const char* const fr = t > lo ? rowBuf + (size_t)(t - 1 - lo) * kRow : ckptBuf + (size_t)ch * kRow;
+        const char* const fr = t > lo ? rowBuf + (size_t)(t - 1 - lo) * Sh::kVecBytes : ckptBuf + (size_t)ch * Sh::kVecBytes;
         BetaOps<KT> ops;
         beta_issue_pk<KT, SY>(ops, rowSet, er);
         float down, stay, up;

@@ -40,22 +40,17 @@
 //
 // viterbi_kernel<KT>: lane = pair, one wave per group, the waves of the launch pull groups from an atomic queue.  The
 // surroundings of the step -- the group queue, observation classes, the two-slot LDS-DMA emission ring one site ahead,
-// the table rows of 64 consecutive sites in one register, the first site -- are fsmc_pair_sweep.h's, shared with
-// forward_kernel (fsmc_pair_loglik.h); the step, the checkpoints, the second sweep and the traceback are this file's.
-// viterbi_step takes its
+// the table rows of 64 consecutive sites in one register, the first site, the packing of the state rows -- are
+// fsmc_pair_sweep.h's, shared with the other sweep kernels; the step and the traceback are this file's.  viterbi_step takes its
 // operand blocks by scalar loads one block ahead like alpha_step.  Registers: p and the vector under construction (the
 // suffix maxima one slot down, as alpha_step keeps alphaC: w[k] = mC[k+1] until state k is done, then v[k]), cI packed
 // four bytes to a register, the back-pointers of four states packed to one dword and stored as they complete.
 //
 // Workspace of a wave: [chunk sites][KT4][64 lanes] u32 of back-pointers (KT4 = ceil(KT / 4): 256-byte coalesced rows, KT
-// bytes a pair and site), then [chunks][KT4][64] float4 of checkpoints.  Sweep 1 runs the whole sequence: sums, the
-// mantissa chain, x[S-1]; it leaves delta of the site before each chunk as a checkpoint and the back-pointers of the LAST
-// chunk in the buffer (the rows of earlier chunks all land on the buffer's first row, which is rewritten later: no
-// branch in the step).  With one chunk the traceback follows directly.  Otherwise, chunk by chunk descending, sweep 2
-// runs the chunk again from its checkpoint for its back-pointers and the traceback walks it down; sums and
-// probabilities come from sweep 1 only.  The traceback is one dependent dword load a site and lane (row x >> 2, byte
-// x & 3); four sites of the state row are packed to an aligned dword of the output, single bytes at a row's two ends
-// (rows are S bytes apart, so neighbouring pairs share dwords where S % 4 != 0).  Vector stores only.
+// bytes a pair and site), then [chunks][KT4][64] float4 of checkpoints: the checkpointed replay of fsmc_pair_sweep.h.
+// Sweep 1 also gives the sums, the mantissa chain and x[S-1]; sums and probabilities come from sweep 1 only.  With one
+// chunk the traceback follows directly.  The traceback is one dependent dword load a site and lane (row x >> 2, byte
+// x & 3); the states leave through packState, the dword under construction reset after each store.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -217,15 +212,11 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
 {
   static_assert(KT >= 2 && KT <= 128, "a lane-per-pair member (fsmc_instances.h)");
   constexpr int KA = KT;
-  constexpr int E4 = ((KT + kKPad - 1) / kKPad) * (kKPad / 4); // float4 per emission row: KP / 4 of the member's models
-  constexpr int NC = 3;                                        // rows per site: the observation classes
-  constexpr int NL = (NC * E4 + kWave - 1) / kWave;            // DMA requests per site
-  constexpr int K4 = (KT + 3) / 4;
+  using Sh = SweepShape<KT, 3>;
   constexpr bool SY = kVitSyncLoads<KT>;
-  constexpr size_t kPsiRow = (size_t)K4 * kWave * sizeof(unsigned);  // bytes of a site's back-pointers
-  constexpr size_t kCkptRow = (size_t)K4 * kWave * sizeof(float4);   // bytes of a checkpoint
+  constexpr size_t kPsiRow = (size_t)Sh::K4 * kWave * sizeof(unsigned);  // bytes of a site's back-pointers
 
-  __shared__ float4 ring[2][NC * E4];
+  __shared__ float4 ring[2][Sh::NC * Sh::E4];
 
   const int lane = threadIdx.x;
   const unsigned laneOff = threadIdx.x * (unsigned)sizeof(float4);
@@ -252,7 +243,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
     RowIndexBlock stepRows;
     // site q's rows into ring slot (q & 1)
     auto stage = [&](const int q) {
-      stageRows<NL>(sp.emis3 + (size_t)q * (NC * E4), ring[q & 1], NC * E4, lane, laneOff);
+      stageRows<Sh::NL>(sp.emis3 + (size_t)q * (Sh::NC * Sh::E4), ring[q & 1], Sh::NC * Sh::E4, lane, laneOff);
     };
 
     float a[KA], w[KA];
@@ -268,13 +259,13 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         stage(pos + 1); // into the slot of site pos - 1, whose step is over
       }
       const int c = obs.classAt(pos);
-      const float4* er = &ring[pos & 1][c * E4];
+      const float4* er = &ring[pos & 1][c * Sh::E4];
       float sum;
       if (__builtin_expect(pos == 0, 0)) {
         sum = firstSite<KT, KA>(a, tPi, er);
       } else {
         if (trace && pos % C == 0) { // delta of the site before chunk pos / C
-          store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * kCkptRow), laneOff, a);
+          store_vec<KT, KA>(KT, (float4*)(ckptBuf + (size_t)(pos / C) * Sh::kVecBytes), laneOff, a);
         }
         const int r = pos >= lastStart ? pos - lastStart : 0;
         sum = viterbi_step<KT, KA, SY>(a, w, rowSetOf<KT>(tabs, stepRows.at(sp.stepRow, S, lane, pos)), tabs.cR, er,
@@ -315,7 +306,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
         waitVm0(); // (nothing of the traceback before is in flight when the ring is restarted)
         stage(lo);
         if (lo > 0) {
-          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * kCkptRow), laneOff, a);
+          load_vec<KT, KA>(KT, (const float4*)(ckptBuf + (size_t)ch * Sh::kVecBytes), laneOff, a);
         }
         for (int pos = lo; pos <= hi; ++pos) {
           landedRows();
@@ -323,7 +314,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
             stage(pos + 1);
           }
           const int c = obs.classAt(pos);
-          const float4* er = &ring[pos & 1][c * E4];
+          const float4* er = &ring[pos & 1][c * Sh::E4];
           if (__builtin_expect(pos == 0, 0)) {
             (void)firstSite<KT, KA>(a, tPi, er);
           } else {
@@ -335,25 +326,7 @@ template <int KT> __global__ __launch_bounds__(kWave, minWavesPerSimd(KT)) void 
       const gchar_p psiBase = uniformPtr(psiBuf);
       for (int t = hi; t >= lo; --t) {
         x = x < kTop ? x : kTop; // (a no-op for every pair with a finite, non-zero probability)
-        // the state of site t into its byte of the output
-        const size_t A = rowByte + (size_t)t;
-        const unsigned sh = 8u * ((unsigned)A & 3u);
-        acc |= x << sh;
-        if (((unsigned)A & 3u) == 0u || t == 0) {
-          const size_t D4 = A & ~(size_t)3;
-          if (pl.valid) {
-            if (((unsigned)A & 3u) == 0u && t + 3 < S) {
-              *(unsigned*)(out + D4) = acc;
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const long long site = (long long)(D4 + (size_t)j) - (long long)rowByte;
-                if (site >= 0 && site < (long long)S) {
-                  out[D4 + (size_t)j] = (unsigned char)((acc >> (8 * j)) & 0xffu);
-                }
-              }
-            }
-          }
+        if (packState(acc, x, out, rowByte, t, S, pl.valid)) {
           acc = 0u;
         }
         if (t >= 1) {

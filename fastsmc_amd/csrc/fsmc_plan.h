@@ -341,31 +341,30 @@ inline int planOneWave(const Settings& set, const KernelTraits& k, bool ibd, con
   return FSMC_OK;
 }
 
-// The launch of the Viterbi kernel (fsmc_pair_viterbi.h) over slices of at most `nGroups` whole-sequence groups of `S`
-// sites.  A wave's workspace is `chunk` rows of back-pointers (KT4 x 64 dwords a site) and a checkpoint (KT4 x 64
-// float4) a chunk; without state rows (`wantStates` false) one row of back-pointers that nobody reads.  The waves: what
-// is resident, the groups, and what the hard budget holds of the smallest slot any chunk length gives (about 2 sqrt(S)
-// sites a chunk: memory is chunk + 4 x S / chunk rows).  The chunk: the caller's (set_chunk_sites), otherwise
-// the whole sequence -- one sweep instead of two -- halved until the waves' slots fit what the context may spend (the
-// soft budget; the hard one for sequences of at most 512 sites, as planOneWave keeps short windows whole).
-// `member`: the kernel's family member; `perCU`: its workgroups a CU, as queried.
-inline int planViterbi(const Settings& set, int S, int member, int perCU, size_t nGroups, bool wantStates,
-                       const WsBudget& budget, LaunchPlan& plan, std::string& why)
+// The launch of a checkpointed pair sweep (the Viterbi, sampling and transition kernels) over slices of at most `nGroups`
+// whole-sequence groups of `S` sites.  A wave's workspace is `chunk` rows of `rowBytes` and a checkpoint of `ckptBytes` a
+// chunk; without rows (`keepRows` false) one row that nobody reads.  The waves: what is resident, the groups, and what
+// the hard budget holds of the smallest slot any chunk length gives (about `cMinFactor` x sqrt(S) sites a chunk).  The
+// chunk: the caller's (set_chunk_sites), otherwise the whole sequence -- one sweep instead of two -- halved until the
+// waves' slots fit what the context may spend (the soft budget; the hard one for sequences of at most 512 sites, as
+// planOneWave keeps short windows whole).  `perCU`: the kernel's workgroups a CU, as queried; `refusal`: what `why`
+// says when the hard budget does not hold one wave's smallest slot.
+inline int planReplay(const Settings& set, int S, int perCU, size_t nGroups, size_t rowBytes, size_t ckptBytes,
+                      double cMinFactor, bool keepRows, const char* refusal, const WsBudget& budget, LaunchPlan& plan,
+                      std::string& why)
 {
   size_t slots = std::max<size_t>(1, std::min((size_t)set.nCU * (size_t)std::max(perCU, 1), nGroups));
   const size_t L = (size_t)S;
-  const size_t K4 = (size_t)(member + 3) / 4;
-  const size_t psiRow = K4 * kWave * sizeof(uint32_t), ckptRow = K4 * kWave * kFloat4Bytes;
-  auto slotBytes = [&](size_t c) { return c * psiRow + (L + c - 1) / c * ckptRow; };
-  size_t C = L, bytes = psiRow;
-  if (wantStates) {
-    size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(2.0 * std::sqrt((double)L))));
+  auto slotBytes = [&](size_t c) { return c * rowBytes + (L + c - 1) / c * ckptBytes; };
+  size_t C = L, bytes = rowBytes;
+  if (keepRows) {
+    size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(cMinFactor * std::sqrt((double)L))));
     if (set.chunkSites) {
       cMin = std::min<size_t>(set.chunkSites, L);
     }
     slots = std::min<size_t>(slots, (size_t)(budget.hard / slotBytes(cMin)));
     if (slots == 0) {
-      why = "workspace limit too small for the back-pointers of one wave";
+      why = refusal;
       return FSMC_ENOMEM;
     }
     if (set.chunkSites) {
@@ -389,49 +388,26 @@ inline int planViterbi(const Settings& set, int S, int member, int perCU, size_t
   return FSMC_OK;
 }
 
-// The launch of the sampling kernel (fsmc_pair_samples.h) over slices of at most `nGroups` whole-sequence groups of `S`
-// sites.  A wave's workspace is `chunk` rows of forward vectors (KT4 x 64 float4 a site) and a checkpoint of the same
-// size a chunk.  The waves: what is resident, the groups, and what the hard budget holds of the smallest slot any chunk
-// length gives (about sqrt(S) sites a chunk: memory is chunk + S / chunk rows).  The chunk: the caller's
-// (set_chunk_sites), otherwise the whole sequence -- one sweep instead of two -- halved until the waves' slots fit what
-// the context may spend (the soft budget; the hard one for sequences of at most 512 sites, as planViterbi).
-// `member`: the kernel's family member; `perCU`: its workgroups a CU, as queried.
+// The Viterbi kernel (fsmc_pair_viterbi.h): rows of back-pointers (KT4 x 64 dwords a site) and a checkpoint (KT4 x 64
+// float4) a chunk, so memory is chunk + 4 x S / chunk rows and the smallest slot has about 2 sqrt(S) sites a chunk;
+// without state rows (`wantStates` false) one row.  `member`: the kernel's family member.
+inline int planViterbi(const Settings& set, int S, int member, int perCU, size_t nGroups, bool wantStates,
+                       const WsBudget& budget, LaunchPlan& plan, std::string& why)
+{
+  const size_t K4 = (size_t)(member + 3) / 4;
+  return planReplay(set, S, perCU, nGroups, K4 * kWave * sizeof(uint32_t), K4 * kWave * kFloat4Bytes, 2.0, wantStates,
+                    "workspace limit too small for the back-pointers of one wave", budget, plan, why);
+}
+
+// The sampling kernel (fsmc_pair_samples.h) and the transition kernel (fsmc_pair_transitions.h): rows of forward vectors
+// (KT4 x 64 float4 a site) and a checkpoint of the same size a chunk, so memory is chunk + S / chunk rows and the
+// smallest slot has about sqrt(S) sites a chunk.
 inline int planSamples(const Settings& set, int S, int member, int perCU, size_t nGroups, const WsBudget& budget,
                        LaunchPlan& plan, std::string& why)
 {
-  size_t slots = std::max<size_t>(1, std::min((size_t)set.nCU * (size_t)std::max(perCU, 1), nGroups));
-  const size_t L = (size_t)S;
-  const size_t K4 = (size_t)(member + 3) / 4;
-  const size_t row = K4 * kWave * kFloat4Bytes;
-  auto slotBytes = [&](size_t c) { return (c + (L + c - 1) / c) * row; };
-  size_t cMin = std::min(L, std::max<size_t>(1, (size_t)std::ceil(std::sqrt((double)L))));
-  if (set.chunkSites) {
-    cMin = std::min<size_t>(set.chunkSites, L);
-  }
-  slots = std::min<size_t>(slots, (size_t)(budget.hard / slotBytes(cMin)));
-  if (slots == 0) {
-    why = "workspace limit too small for the forward rows of one wave";
-    return FSMC_ENOMEM;
-  }
-  size_t C = L;
-  if (set.chunkSites) {
-    C = cMin;
-  } else {
-    const uint64_t room = L <= 512 ? budget.hard : budget.soft;
-    while (C > cMin && (uint64_t)slots * slotBytes(C) > room) {
-      C = std::max(cMin, (C + 1) / 2);
-    }
-  }
-  const size_t bytes = slotBytes(C);
-  plan = LaunchPlan();
-  plan.chunk = (int)C;
-  plan.chunkRows = (int)C;
-  plan.maxChunks = (int)((L + C - 1) / C);
-  plan.wsSlot = bytes / kFloat4Bytes;
-  plan.slots = (int)slots;
-  plan.wavesPerWindow = 1;
-  plan.bytes = bytes * slots;
-  return FSMC_OK;
+  const size_t row = (size_t)(member + 3) / 4 * kWave * kFloat4Bytes;
+  return planReplay(set, S, perCU, nGroups, row, row, 1.0, true,
+                    "workspace limit too small for the forward rows of one wave", budget, plan, why);
 }
 
 // A launch of the two-waves-per-window kernel, if this one qualifies: `nItems` workgroups (groups; batches of the sums)

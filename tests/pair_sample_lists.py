@@ -24,7 +24,7 @@ import numpy as np
 
 from pair_loglik_lists import (ALL_PAIRS, CASES as LL_CASES, PAIR_COUNTS, _problem, forward,  # noqa: F401
                                case as ll_case, zero_sum_problem)
-from pair_viterbi_lists import CASES as V_CASES, CHUNKS_RICH, _rich_problem  # noqa: F401
+from pair_viterbi_lists import CASES as V_CASES, CHUNKS_RICH, CHUNKS_S65, _rich_problem  # noqa: F401
 
 F32 = np.float32
 U32 = np.uint32

@@ -4,6 +4,7 @@
 //   philox c0 c1 c2 c3 k0 k1          (hexadecimal)  -> the four output words of Philox4x32-10 (fsmc_philox.h)
 //   uniform seed hap_a hap_b r t      (decimal)      -> the bits of the float32 uniform and its value
 //   planSamples key=value ...         -> plan::planSamples (fsmc_plan.h); keys left out have the defaults below
+//   planViterbi key=value ...         -> plan::planViterbi with state rows, the same keys: the other caller of planReplay
 //   layout S n slicePairsMax          -> layout::samples (fsmc_pair_layout.h)
 #include <cinttypes>
 #include <cstdio>
@@ -40,7 +41,7 @@ int main()
       uint32_t bits;
       std::memcpy(&bits, &u, sizeof(bits));
       std::printf("%08x %.9g\n", bits, (double)u);
-    } else if (fn == "planSamples") {
+    } else if (fn == "planSamples" || fn == "planViterbi") {
       std::map<std::string, uint64_t> kv = {{"nCU", 256}, {"perCU", 8},        {"S", 640},      {"member", 69},
                                             {"nGroups", 10}, {"chunkSites", 0}, {"hard", 1ull << 40}, {"soft", 0}};
       std::string tok;
@@ -54,8 +55,11 @@ int main()
       const fsmc::plan::WsBudget budget{kv["hard"], kv["soft"] ? kv["soft"] : kv["hard"]};
       fsmc::plan::LaunchPlan p;
       std::string why;
-      const int rc = fsmc::plan::planSamples(set, (int)kv["S"], (int)kv["member"], (int)kv["perCU"], (size_t)kv["nGroups"],
-                                             budget, p, why);
+      const int rc = fn == "planSamples"
+                         ? fsmc::plan::planSamples(set, (int)kv["S"], (int)kv["member"], (int)kv["perCU"],
+                                                   (size_t)kv["nGroups"], budget, p, why)
+                         : fsmc::plan::planViterbi(set, (int)kv["S"], (int)kv["member"], (int)kv["perCU"],
+                                                   (size_t)kv["nGroups"], true, budget, p, why);
       if (rc != FSMC_OK) {
         std::printf("rc=%d why=\"%s\"\n", rc, why.c_str());
       } else {

@@ -27,6 +27,8 @@ F32 = np.float32
 # the lane-per-pair members at 129 sites; the site counts at K = 69; the rich 700-site case
 MODEL_CASES = ("K2", "K3", "K20", "dense40", "K64", "K69", "K50", "K100", "K128")
 SITE_CASES = ("S1", "S2", "S3", "S4", "S5", "S63", "S64", "S65", "S200")
+from pair_viterbi_lists import CHUNKS_S65  # noqa: E402,F401  (the chunk lengths of the GPU test on the 65-site case)
+
 CHUNKS_RICH = (1, 2, 27, 699, 700)  # chunk lengths of the GPU test on the rich case: an edge at t = 1 (1), at S - 1 (1, 699)
 
 # the largest |statement - fp64 yardstick| over YARDSTICK (three pairs each), measured on the CPU with the code of this

@@ -236,6 +236,10 @@ CASES["rich"] = (69, 700, 70)
 CASES["dense40"] = (40, 300, 70)
 RICH = ("rich", "dense40")
 CHUNKS_RICH = (16, 64, 150, 700, 0)  # chunk lengths of the GPU test on the rich case: 150 does not divide 700, 0 = automatic
+# ... and on the 65-site case, whose 200 rows each start at another phase of the output's groups of four sites and share
+# groups with their neighbours: a chunk that ends at t = 1 (2), edges inside a group (2, 3, 7) and on group boundaries of
+# the aligned rows (4, 64), a last chunk shorter than the others in every one
+CHUNKS_S65 = (2, 3, 4, 7, 64)
 
 LIMITS_RICH = (1 << 20, 600 << 10)  # workspace limits of the GPU test on the rich case (two groups: two waves wanted)
 

@@ -203,6 +203,12 @@ void run(const std::string& fn, const Case& c)
     const int rc = planViterbi(c.settings(), (int)c.i("S", 640), (int)c.i("member", 69), (int)c.i("perCU", 8),
                                (size_t)c.u("nGroups", 10), c.i("states", 1) != 0, c.budget(), p, why);
     printPlan(rc, p, why);
+  } else if (fn == "planSamples") {
+    LaunchPlan p;
+    std::string why;
+    const int rc = planSamples(c.settings(), (int)c.i("S", 640), (int)c.i("member", 69), (int)c.i("perCU", 8),
+                               (size_t)c.u("nGroups", 10), c.budget(), p, why);
+    printPlan(rc, p, why);
   } else if (fn == "planTwoWaves") {
     LaunchPlan p;
     const size_t nItems = (size_t)c.u("nItems", 10);

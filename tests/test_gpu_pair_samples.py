@@ -149,8 +149,12 @@ def rich():
     ctx.close()
 
 
-def test_chunk_lengths(rich):
-    """Chunks of 16, 64, 150 (does not divide 700), 700 sites and automatic: the same bytes throughout."""
+def test_chunk_lengths(rich, s65):
+    """Chunks of 16, 64, 150 (does not divide 700), 700 sites and automatic: the same bytes throughout.  Then the 65-site
+    case, whose rows start at every phase of the output's dwords and share dwords with their neighbours, in chunks of 2, 3,
+    4, 7 and 64 sites: edges inside a dword and on dword boundaries, a chunk that ends at t = 1, a ragged last chunk
+    (tests/test_pair_sample_lists.py shows that samples change state across every one of these edges); in chunks of 3 the
+    rows beyond the list stay untouched."""
     ctx, model, pm, pairs, want = rich
     for C in SL.CHUNKS_RICH:
         ctx.set_chunk_sites(C)
@@ -159,6 +163,22 @@ def test_chunk_lengths(rich):
         chunk = C if C else pm.S
         assert info["chunk_sites"] == chunk and info["max_chunks"] == -(-pm.S // chunk), (C, info)
         _assert_equal(got, want, f"chunk {C}")
+    ctx, model, pm, pairs = s65
+    want = SL.case("S65")[4]
+    _upload(ctx, pm, pairs)
+    for C in SL.CHUNKS_S65:
+        ctx.set_chunk_sites(C)
+        got = ctx.decode_pair_samples(model, SL.N_MODELS, SL.SEED_MODELS)
+        info = ctx.info()
+        assert info["chunk_sites"] == C and info["max_chunks"] == -(-pm.S // C), (C, info)
+        _assert_equal(got, want, f"65 sites, chunk {C}")
+    ctx.set_chunk_sites(3)
+    for n in SL.PAIR_COUNTS:
+        _upload(ctx, pm, pairs[:n])
+        buf = np.full((n + 3, SL.N_MODELS, pm.S), 255, np.uint8)
+        got = ctx.decode_pair_samples(model, SL.N_MODELS, SL.SEED_MODELS, out=buf)
+        _assert_equal(got[:n], want[:n], f"65 sites, chunk 3, {n} pairs")
+        assert (got[n:] == 255).all(), n
 
 
 def test_workspace_limit_forces_chunks(rich):

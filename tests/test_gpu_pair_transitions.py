@@ -106,8 +106,11 @@ def rich():
     ctx.close()
 
 
-def test_chunk_lengths(rich):
-    """Chunks of 1, 2, 27, 699 and 700 sites: a chunk edge at t = 1 and at S - 1, a ragged last chunk, one chunk."""
+def test_chunk_lengths(rich, s65):
+    """Chunks of 1, 2, 27, 699 and 700 sites: a chunk edge at t = 1 and at S - 1, a ragged last chunk, one chunk.  Then the
+    65-site case, whose rows start at every phase of the output's float4s and share float4s with their neighbours, in
+    chunks of 2, 3, 4, 7 and 64 sites: edges inside a float4 and on float4 boundaries, a ragged last chunk; in chunks of 3
+    the rows beyond the list stay untouched."""
     ctx, model, pm, pairs, wd, wu = rich
     for C in TL.CHUNKS_RICH:
         ctx.set_chunk_sites(C)
@@ -116,6 +119,24 @@ def test_chunk_lengths(rich):
         assert info["chunk_sites"] == C and info["max_chunks"] == -(-pm.S // C), (C, info)
         _assert_equal(down, wd, f"chunk {C} down")
         _assert_equal(up, wu, f"chunk {C} up")
+    ctx, model, pm, pairs = s65
+    _, _, _, _, wd, wu = TL.case("S65")
+    _upload(ctx, pm, pairs)
+    for C in TL.CHUNKS_S65:
+        ctx.set_chunk_sites(C)
+        down, up = _rows(ctx, model)
+        info = ctx.info()
+        assert info["chunk_sites"] == C and info["max_chunks"] == -(-pm.S // C), (C, info)
+        _assert_equal(down, wd, f"65 sites, chunk {C} down")
+        _assert_equal(up, wu, f"65 sites, chunk {C} up")
+    ctx.set_chunk_sites(3)
+    for n in TL.PAIR_COUNTS:
+        _upload(ctx, pm, pairs[:n])
+        bd, bu = np.full((n + 3, pm.S), -7, np.float32), np.full((n + 3, pm.S), -7, np.float32)
+        ctx.decode_pair_transitions(model, out=(bd, bu, None, None))
+        _assert_equal(bd[:n], wd[:n], f"65 sites, chunk 3, {n} pairs down")
+        _assert_equal(bu[:n], wu[:n], f"65 sites, chunk 3, {n} pairs up")
+        assert (bd[n:] == -7).all() and (bu[n:] == -7).all(), n
 
 
 def test_workspace_limit_forces_chunks(rich):

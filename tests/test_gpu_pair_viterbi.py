@@ -215,8 +215,11 @@ def rich():
     ctx.close()
 
 
-def test_chunk_lengths(rich):
-    """Chunks of 16, 64, 150 (does not divide 700), 700 sites and automatic: the same bytes throughout."""
+def test_chunk_lengths(rich, s65):
+    """Chunks of 16, 64, 150 (does not divide 700), 700 sites and automatic: the same bytes throughout.  Then the 65-site
+    case, whose rows start at every phase of the output's dwords and share dwords with their neighbours, in chunks of 2, 3,
+    4, 7 and 64 sites: edges inside a dword and on dword boundaries, a chunk that ends at t = 1, a ragged last chunk; in
+    chunks of 3 the rows beyond the list stay untouched."""
     ctx, model, pm, pairs, want = rich
     for C in VL.CHUNKS_RICH:
         ctx.set_chunk_sites(C)
@@ -225,6 +228,21 @@ def test_chunk_lengths(rich):
         chunk = C if C else pm.S
         assert info["chunk_sites"] == chunk and info["max_chunks"] == -(-pm.S // chunk), (C, info)
         _assert_equal(got, want, f"chunk {C}")
+    ctx, model, pm, pairs, want = s65
+    _upload(ctx, pm, pairs)
+    for C in VL.CHUNKS_S65:
+        ctx.set_chunk_sites(C)
+        got = ctx.decode_pair_viterbi(model)
+        info = ctx.info()
+        assert info["chunk_sites"] == C and info["max_chunks"] == -(-pm.S // C), (C, info)
+        _assert_equal(got, want, f"65 sites, chunk {C}")
+    ctx.set_chunk_sites(3)
+    for n in VL.PAIR_COUNTS:
+        _upload(ctx, pm, pairs[:n])
+        got = ctx.decode_pair_viterbi(model, out=_sentinels(n + 3, pm.S))
+        for name, g, w in zip(NAMES, got, want):
+            assert np.array_equal(g[:n], w[:n]), (n, name)
+            assert _untouched(g[n:]), (n, name)
 
 
 def test_workspace_limit_forces_chunks(rich):

@@ -42,6 +42,12 @@ PLAN_TABLE = [
     ("planSamples S=129 member=128 nGroups=3 perCU=4 nCU=1",
      "rc=0 chunk=129 chunkRows=129 maxChunks=1 resident=0 wsSlot=266240 slots=3 waves=1 bytes=12779520"),
     ("planSamples S=1 nGroups=1", "rc=0 chunk=1 chunkRows=1 maxChunks=1 resident=0 wsSlot=2304 slots=1 waves=1 bytes=36864"),
+    # the two callers of planReplay side by side at equal inputs (the second line of each pair stands above as well):
+    # rows of 256 bytes a float4 group against 1 KiB, a smallest chunk of 2 sqrt(S) against sqrt(S)
+    ("planViterbi S=700 nGroups=2 hard=2097152",
+     "rc=0 chunk=175 chunkRows=175 maxChunks=4 resident=0 wsSlot=55008 slots=2 waves=1 bytes=1760256"),
+    ("planViterbi S=700 nGroups=2 chunkSites=150",
+     "rc=0 chunk=150 chunkRows=150 maxChunks=5 resident=0 wsSlot=48960 slots=2 waves=1 bytes=1566720"),
 ]
 LAYOUT_TABLE = [
     ("layout 700 2 70", "groupBytes=89600 pairBytes=1400 rowsBytes=98000"),
@@ -190,6 +196,14 @@ def test_regimes_of_the_gpu_inputs():
         for b in range(C, S, C):
             assert changed[b - 1], (C, b)
     assert (rich == 0).any() and (rich == 68).any()
+    # the 65-site case in the chunks of the GPU test: some sample changes state across every chunk boundary; one length is
+    # no multiple of four and the last chunk is ragged in all of them
+    prev, cur = _moves(SL.case("S65")[4])
+    changed = (prev != cur).any(axis=(0, 1))
+    for C in SL.CHUNKS_S65:
+        for b in range(C, 65, C):
+            assert changed[b - 1], (C, b)
+    assert any(C % 4 for C in SL.CHUNKS_S65) and all(65 % C for C in SL.CHUNKS_S65)
     # at the sizes of the model cases states change too, in both directions; the smallest models reach both ends
     for name in ("K2", "K3", "K16", "K20", "K64", "K128", "K50", "K69", "K100"):
         pm, _, _, _, states = SL.case(name, first=70)

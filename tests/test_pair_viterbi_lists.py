@@ -141,6 +141,23 @@ def test_rich_case_moves_across_chunk_boundaries():
     assert any(C and S % C for C in VL.CHUNKS_RICH) and S in VL.CHUNKS_RICH and 0 in VL.CHUNKS_RICH
 
 
+def test_s65_case_in_chunks():
+    """The 65-site case in the chunks of the GPU test.  Its most probable paths move between five pairs of sites only
+    (into t = 4, 51, 52, 56 and 62), so no chunk length puts a move on EVERY boundary -- none of 2, 3, 4, 5, 7 and 64 does;
+    what holds, and is asserted: the chunks of 2, 3, 4 and 7 sites each have a boundary that some path moves across (the
+    traceback's hand-over with a change of state), one of the lengths is no multiple of four, and the last chunk is ragged
+    in every one.  What this case adds on the GPU is the rows' phases (65 bytes a row), not moving paths; those are the
+    rich case's above."""
+    _, _, _, _, states, _, _ = VL.case("S65")
+    S = states.shape[1]
+    moved = np.flatnonzero((states[:, 1:] != states[:, :-1]).any(axis=0)) + 1
+    assert moved.tolist() == [4, 51, 52, 56, 62], moved
+    for C in VL.CHUNKS_S65:
+        if C != 64:
+            assert set(range(C, S, C)) & set(moved.tolist()), C
+    assert any(C % 4 for C in VL.CHUNKS_S65) and all(S % C for C in VL.CHUNKS_S65)
+
+
 def test_small_models_move_too():
     for name, lo in (("K2", 1), ("K3", 2)):
         _, _, _, _, states, _, _ = VL.case(name)

@@ -254,6 +254,21 @@ TABLE = [
      'NW=4 KH=64'),
     ('w2Member K=300 w2nw=5 w2kh=64',
      'NW=4 KH=80'),
+    # planSamples, the other caller of planReplay, at the inputs of the planViterbi lines above (printed by the two functions
+    # as they stood apart; at the table's end, so that every earlier case keeps its number):
+    # the whole sequence, a caller's chunk, S = 512 (hard) / 513 (soft), slots cut by the hard budget, no room
+    ('planSamples',
+     'rc=0 chunk=640 chunkRows=640 maxChunks=1 resident=0 wsSlot=738432 slots=10 waves=1 bytes=118149120 poolOff=0 poolBuffers=0 poolCap=0'),
+    ('planSamples chunkSites=100',
+     'rc=0 chunk=100 chunkRows=100 maxChunks=7 resident=0 wsSlot=123264 slots=10 waves=1 bytes=19722240 poolOff=0 poolBuffers=0 poolCap=0'),
+    ('planSamples S=512 hard=1073741824 soft=4194304',
+     'rc=0 chunk=512 chunkRows=512 maxChunks=1 resident=0 wsSlot=590976 slots=10 waves=1 bytes=94556160 poolOff=0 poolBuffers=0 poolCap=0'),
+    ('planSamples S=513 hard=1073741824 soft=4194304',
+     'rc=0 chunk=23 chunkRows=23 maxChunks=23 resident=0 wsSlot=52992 slots=10 waves=1 bytes=8478720 poolOff=0 poolBuffers=0 poolCap=0'),
+    ('planSamples S=513 hard=1073741824 soft=4194304 nGroups=100000',
+     'rc=0 chunk=23 chunkRows=23 maxChunks=23 resident=0 wsSlot=52992 slots=1266 waves=1 bytes=1073405952 poolOff=0 poolBuffers=0 poolCap=0'),
+    ('planSamples hard=1000',
+     'rc=-4 why="workspace limit too small for the forward rows of one wave"'),
 ]
 
 
